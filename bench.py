@@ -2,7 +2,7 @@
 """Benchmark of the hot path: depth frames/sec fused + decoded, 640x480 @ 256^3 grid
 (BASELINE.json metric; workload definition in SURVEY.md section 8d / DESIGN.md section 5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One step = one synthetic 640x480 frame: uint16 depth image -> points + normals (GPU front end) ->
 encode_pointcloud + _integrate into the persistent volume (+ TSDF side fusion) (fused) + SDF decode of the
@@ -40,6 +40,11 @@ frames, so the clock has settled under the package power limit -- plus
   parity           GPU outputs of the last timed frame against the oracle (>= 2,000 voxels);
   other_mlp_modes  the f16-operand mode (lower precision, never the headline);
   cpu_baseline     the oracle on the host cores.
+
+--dump-outputs DIR writes what the last timed step returned to its caller -- the voxel coordinates and their SDF
+lattices (rank 0's share when sharded) -- as DIR/coords.npy (float64) and DIR/sdf.npy (float32), so that two builds
+can be compared output for output: the inputs are synthetic and seeded, identical from run to run for the same
+arguments.  Above DUMP_MAX_BYTES a fixed, seeded sample of rows is written (DIR/rows.npy: which rows).
 """
 import argparse
 import ctypes as C
@@ -52,10 +57,6 @@ import sys
 import threading
 import time
 
-# streams that share a hardware queue run in submission order (bnv_fusion_amd/streams.py): more queues, set before the
-# HIP runtime initialises
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np
 import torch
 
@@ -63,7 +64,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 from bnv_fusion_amd import configure_runtime  # noqa: E402
 
-configure_runtime()      # 8 hardware queues for the frame pipelines' streams; before the first HIP call
+configure_runtime()      # the package's hardware queue count (streams.py); before the first HIP call
 
 FLOP_PER_PAIR = 2 * (6 * 128 + 128 * 128 + 128 * 128 + 128 * 8)          # 69,120  point encoder
 FLOP_PER_EVAL = 2 * (17 * 256 + 3 * 256 * 256 + 256)                      # 402,432 SDF MLP
@@ -87,6 +88,33 @@ PARITY_VOXELS = 2048
 # separately (`growth`).
 CAPACITY = 1 << 22
 PROFILE_TAG = "r06"
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all files together
+
+
+def host_outputs(run):
+    """What the caller of the timed path received from its last step, copied to the host right away (with
+    copy_results off the results are views into the pipeline's slots, reused by the next frames): name -> array."""
+    if run["coords"] is None:
+        return {"coords": np.zeros((0, 3)), "sdf": np.zeros((0, 27), dtype=np.float32)}
+    return {"coords": run["coords"].cpu().numpy().astype(np.float64),
+            "sdf": run["sdf"].float().cpu().numpy()}
+
+
+def dump_outputs(outputs, out_dir, seed=0):
+    """Writes ``outputs`` (name -> array, one row per voxel) to ``out_dir/<name>.npy``; above DUMP_MAX_BYTES, the same
+    fixed, seeded sample of rows of every array (in their original order) and ``rows.npy``, the rows taken."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(outputs["coords"])
+    row_bytes = sum(a[:1].nbytes for a in outputs.values())
+    keep = max((DUMP_MAX_BYTES - 4096) // (row_bytes + 8), 1)      # (+8: rows.npy; 4 kB: the files' headers)
+    if n > keep:
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        outputs = {k: a[rows] for k, a in outputs.items()}
+        outputs["rows"] = rows.astype(np.float64)
+    for k, a in outputs.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "files": sorted(f"{k}.npy" for k in outputs), "rows": n,
+            "sampled": "rows" in outputs}
 
 
 def pmc_traffic(kernel_substr, evals_now):
@@ -570,7 +598,15 @@ def parse_args():
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="launcher test (no GPU needed): every rank checks RANK / WORLD_SIZE against --gpus, rank 0 "
                          "prints them, all exit before any GPU call")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of `value` returned (voxel coordinates, SDF lattices; rank "
+                         "0's share when sharded) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def main():
@@ -883,6 +919,8 @@ def run_bench(args, rank, world, dev, dist, backend):
                 drv.run(m, kind, list(range(-(-args.preroll // fpu) * fpu)), decode=False)     # setup: live decode mask
                 warm_idx, step_idx = idx_of(fpu)
                 run = timed(m, kind, args.mlp_mode, step_idx, warm_idx, preheat=min(args.preheat, 4 * POOL))
+                if args.dump_outputs and rank == 0:
+                    run["outputs"] = host_outputs(run)
                 run["parity"] = parity_check(m, run)
                 if kind == "spatial":
                     extra = {"ownership": m.backend.ownership, "block_log2": m.backend.block_log2,
@@ -972,6 +1010,8 @@ def run_bench(args, rank, world, dev, dist, backend):
             out["spatial_sharding" if kind == "spatial" else "frame_parallel"] = dist_entry(kind)
         for kind, errs in errors.items():
             out["spatial_sharding" if kind == "spatial" else "frame_parallel"] = {"error": errs}
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(prim["outputs"], args.dump_outputs)
         return out
 
     # =========================================================================================================
@@ -994,6 +1034,8 @@ def run_bench(args, rank, world, dev, dist, backend):
                                      "decode_frac_of_peak": kb["dec_tflops"] / PEAK_TFLOPS[mode],
                                      "pointnet_kernel_ms": kb["enc_ms"], "pointnet_tflops": kb["enc_tflops"]}
         run = timed(nm, "single", mode, step_idx, warm_idx, preheat=ph)
+        if args.dump_outputs and mode == args.mlp_mode:
+            run["outputs"] = host_outputs(run)
         run["parity"] = parity_check(nm, run)  # right after the timed region: the volume is in that run's final state
         # Kernel-alone pass for the roofline: with the encode on a second stream the two MLP kernels of consecutive
         # frames share the GPU, so their event-to-event durations overlap.  A roofline needs the kernel's own
@@ -1011,6 +1053,7 @@ def run_bench(args, rank, world, dev, dist, backend):
         return run, burst, kern, note
 
     main_run, burst_run, kern_run, kern_note = measure(args.mlp_mode)
+    dumped = dump_outputs(main_run.pop("outputs"), args.dump_outputs) if args.dump_outputs else None
 
     def sustainable_mfma():
         """What the f16 MFMA pipe of THIS box sustains when nothing else is issued (bnv_probe_mfma_rate: every CU, two
@@ -1193,6 +1236,8 @@ def run_bench(args, rank, world, dev, dist, backend):
                                          "frac_of_peak": kern_run["enc_tflops"] / peak}},
         "parity": main_run["parity"],
     })
+    if dumped:
+        out["dump_outputs"] = dumped
     out.update(extras)
     # The figures a reader looks for first, in the objects the driver's record keeps whole (`config`, `roofline`) and once
     # more as the LAST key of the line (the driver also keeps the line's 2,000-character tail)

@@ -1,12 +1,12 @@
 """Side streams that really run beside the caller's stream.
 
-The HIP runtime multiplexes a process's streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by default), and two
+The HIP runtime multiplexes a process's streams onto a few hardware queues (GPU_MAX_HW_QUEUES), and two
 streams that land on the same queue are served strictly in submission order: the frame pipeline's encode stream then
 never overlaps the main stream's decode (measured: 0.400 instead of 0.315 ms per sharded frame at world 8 when the
 pool stream torch handed out shared the default stream's queue -- which depends on how many streams RCCL and torch
 created before).  ``concurrent_stream`` therefore TESTS candidates -- one spin kernel on each stream, timed with
-events -- and returns the first that overlaps ``main``.  bnv_fusion_amd/__init__.py also raises the queue count
-when the runtime has not been initialised yet."""
+events -- and returns the first that overlaps ``main``, or says that none did (``.bnv_concurrent``): with
+bnv_fusion_amd.MAX_HW_QUEUES queues (bnv_fusion_amd.configure_runtime) fewer side streams can overlap."""
 import ctypes as C
 
 import torch

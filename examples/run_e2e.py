@@ -21,7 +21,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import bnv_fusion_amd as bnv                                   # noqa: E402
-bnv.configure_runtime()                                       # optional: 8 hardware queues for the pipelined streams
+bnv.configure_runtime()                                       # optional: the package's hardware queue count
 from bnv_fusion_amd import datasets, synthetic                # noqa: E402
 from bnv_fusion_amd.mesh import post_process_mesh             # noqa: E402
 

@@ -14,7 +14,7 @@ WEIGHTS_TCNN = os.path.join(ROOT, "bnv_fusion_amd", "weights", "pointnet_tcnn.np
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    # before any test initialises the HIP runtime: 8 hardware queues for the frame pipelines' streams
+    # before any test initialises the HIP runtime: the package's hardware queue count (bnv_fusion_amd.MAX_HW_QUEUES)
     from bnv_fusion_amd import configure_runtime
     configure_runtime()
 

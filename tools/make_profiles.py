@@ -167,11 +167,11 @@ with open(f"{dst}/{R}_README.md", "w") as f:
     W(f"* `{R}_spatial_world8_all_ranks_256_first_touch.txt` -- the same with round 4's fine-interleave first touch: {tail_of('spatial_world8_all_ranks_256_first_touch', 4)}.\n")
     W(f"* `{R}_spatial_world8_all_ranks_sweep.txt`, `..._sweep_first_touch.txt`, `..._sweep_first_touch16.txt` -- the room sweep (`sequence.py`: a camera that turns and walks), 256^3, 1,000 frames per rank, under the region rule, the fine interleave with 8^3 blocks and with 16^3 blocks.  region: {tail_of('spatial_world8_all_ranks_sweep', 4)}.  first touch 8^3: {tail_of('spatial_world8_all_ranks_sweep_first_touch', 4)}.  first touch 16^3: {tail_of('spatial_world8_all_ranks_sweep_first_touch16', 4)}.\n")
     W(f"* `{R}_spatial_world2.txt`, `{R}_spatial_world4.txt` (worlds 2 and 4, every rank), `{R}_spatial_world8.txt` (rank 0, 200 frames from an idle GPU + the latency of one frame at a time), `{R}_spatial_world8_tcnn.txt` (tiny-cuda-nn networks); `{R}_fp_replay8.txt` -- `tools/fp_single_rank.py --replay 8`: the frame-parallel mode's per-batch work of one rank of 8.\n")
-    if os.path.exists(f"{src}/bench_line_8rank_gloo.json") and os.path.getsize(f"{src}/bench_line_8rank_gloo.json") > 10:
-        d8 = last_json(f"{src}/bench_line_8rank_gloo.json")
-        open(f"{dst}/{R}_bench_line_8rank_gloo_functional.json", "w").write(json.dumps(d8) + "\n")
+    if os.path.exists(f"{src}/bench_line_4rank_gloo.json") and os.path.getsize(f"{src}/bench_line_4rank_gloo.json") > 10:
+        d8 = last_json(f"{src}/bench_line_4rank_gloo.json")
+        open(f"{dst}/{R}_bench_line_4rank_gloo_functional.json", "w").write(json.dumps(d8) + "\n")
         pr = d8.get("spatial_sharding", {}).get("per_rank", [])
-        W(f"* `{R}_bench_line_8rank_gloo_functional.json` -- `BNV_DIST_BACKEND=gloo python bench.py --gpus 8 --steps 20 --preheat 64`: EIGHT ranks sharing this one GPU over gloo (functional: its rates mean nothing), the real exchange among 8 shards: `spatial_sharding.per_rank[].mlp_evals_per_frame` = {[int(x['mlp_evals_per_frame']) for x in pr]}; parity of rank 0's outputs against the oracle {d8.get('spatial_sharding', {}).get('parity', {}).get('sdf_max_abs_err_vs_oracle')}.\n")
+        W(f"* `{R}_bench_line_4rank_gloo_functional.json` -- `BNV_DIST_BACKEND=gloo python bench.py --gpus 4 --steps 20 --preheat 64`: FOUR ranks sharing this one GPU over gloo (functional: its rates mean nothing), the real exchange among 4 shards: `spatial_sharding.per_rank[].mlp_evals_per_frame` = {[int(x['mlp_evals_per_frame']) for x in pr]}; parity of rank 0's outputs against the oracle {d8.get('spatial_sharding', {}).get('parity', {}).get('sdf_max_abs_err_vs_oracle')}.\n")
     W(f"* `{R}_spatial_world8_all_ranks_256_delay30.txt`, `{R}_spatial_world8_all_ranks_512_delay30.txt` -- the same with `--exchange-delay 30` (a 30 us spin kernel behind the stand-in all-gather: the latency of a real 8-rank collective): {tail_of('spatial_world8_all_ranks_256_delay30', 3)} || 512^3: {tail_of('spatial_world8_all_ranks_512_delay30', 3)}.\n")
     ost = glob.glob(f"{src}/trace_optimize/**/*kernel_stats.csv", recursive=True)
     if ost:
@@ -185,7 +185,7 @@ with open(f"{dst}/{R}_README.md", "w") as f:
         d2 = last_json(f"{src}/bench_line_2rank_gloo.json")
         open(f"{dst}/{R}_bench_line_2rank_gloo_functional.json", "w").write(json.dumps(d2) + "\n")
         W(f"* `{R}_bench_line_2rank_gloo_functional.json` -- `BNV_DIST_BACKEND=gloo python bench.py --gpus 2`: FUNCTIONAL evidence only (two ranks share one GPU, the collectives go through the host): the line a multi-GPU run prints -- `value` = the spatially sharded mode ({d2['scaling']}), `spatial_sharding` and `frame_parallel` entries with their own parity checks (spatial: SDF max-abs-err {d2['spatial_sharding']['parity']['sdf_max_abs_err_vs_oracle']:.1e}, mask decisions equal: {d2['spatial_sharding']['parity']['mask_decisions_equal']}), `distributed` = what the backend saw.  Its rates say nothing about RCCL over xGMI.\n")
-    W(f"* `{R}_queue_probe.txt` -- `GPU_MAX_HW_QUEUES=4 tools/queue_probe.py`: which pool streams overlap the default stream (every fourth shares its hardware queue and runs strictly behind it); `{R}_mlp_launch_overhead.txt` -- `tools/mlp_launch_overhead.py`: duration of the two MLP kernels against the work per launch, down to an empty launch.\n\n")
+    W(f"* `{R}_queue_probe.txt` -- `tools/queue_probe.py`: which pool streams overlap the default stream (those that share its hardware queue run strictly behind it); `{R}_mlp_launch_overhead.txt` -- `tools/mlp_launch_overhead.py`: duration of the two MLP kernels against the work per launch, down to an empty launch.\n\n")
     n_small = sum(1 for s in frame_kernels if kname(s))
     W(f"A frame is **{n_small + 2} kernel launches** ({n_small} small kernels + the two MLP kernels; the upsert also stamps the decode's origins and the frame's counters come back through a read-back launch, not through copies); the kernels that are not an MLP take **{non_mlp_us:.0f} us** per frame together.\n\n")
     W("| kernel | calls | avg ms | % of GPU time |\n|---|---|---|---|\n")

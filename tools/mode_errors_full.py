@@ -4,7 +4,7 @@ the last frames against mode 1 (fp32-class arithmetic, itself 1e-8 from the orac
 import sys, numpy as np, torch
 sys.path.insert(0, '.')
 import bnv_fusion_amd as bnv
-bnv.configure_runtime()      # 8 hardware queues, before the first HIP call (streams.py)
+bnv.configure_runtime()      # the package's hardware queue count, before the first HIP call (streams.py)
 from bnv_fusion_amd import synthetic
 dims, voxel = synthetic.GRID_DIMS[256]
 frames = [{"depth": torch.from_numpy(synthetic.depth_u16(t)).cuda(), "intr_mat": synthetic.intrinsics(), "T_wc": synthetic.pose(t)} for t in range(45)]
