@@ -31,6 +31,9 @@ from .sparse_volume import SparseVolume, VolumeList, get_world_range  # noqa: F4
 from .neural_map import NeuralMap  # noqa: F401
 from . import optimize  # noqa: F401
 from ._lib import BnvError  # noqa: F401
+from . import evaluate  # noqa: F401,E402
+from .evaluate import evaluate_meshes, nearest_neighbors, sample_surface  # noqa: F401,E402
+from .mesh import TriMesh, load_ply  # noqa: F401,E402
 
 
 MLP_MODE_FP32_EXACT = 0     # v_mfma_f32_32x32x2_f32

@@ -31,6 +31,7 @@ SYMBOLS = [
     "bnv_frame_pipe_create", "bnv_frame_pipe_destroy", "bnv_frame_begin_depth", "bnv_frame_begin_points",
     "bnv_frame_upsert", "bnv_frame_bound", "bnv_frame_finish", "bnv_frame_result", "bnv_frame_ready", "bnv_frame_pipe_timeline_enable", "bnv_frame_timeline",
     "bnv_frame_side_depth", "bnv_frame_cancel", "bnv_frame_pipe_forget_workspaces", "bnv_shard_state_configure",
+    "bnv_mesh_sample_surface_workspace", "bnv_mesh_sample_surface", "bnv_nn_workspace_bytes", "bnv_nn_query",
     
 ]
 
@@ -254,6 +255,10 @@ def load():
         "bnv_frame_cancel": (C.c_int, [vp, C.c_int]),
         "bnv_frame_pipe_forget_workspaces": (C.c_int, [vp]),
         "bnv_shard_state_configure": (C.c_int, [vp, i32, i32, vp]),
+        "bnv_mesh_sample_surface_workspace": (C.c_int, [i64, C.POINTER(i64)]),
+        "bnv_mesh_sample_surface": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
+        "bnv_nn_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+        "bnv_nn_query": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

@@ -1,0 +1,655 @@
+// Mesh evaluation: area-weighted surface sampling and exact nearest neighbours on a uniform grid -- the hot path of
+// the reference's mesh metric (src/scripts/evaluate_bnvf.py:9-31, src/scripts/compute_chamfer.py:36-75: trimesh
+// sample_surface + a ball-tree NN query in both directions; bnv_fusion_amd/evaluate.py turns the distances into the
+// figures).  Every result is bitwise reproducible from run to run: no float atomic feeds a result, the float64 area
+// prefix is a fixed left-to-right chain of tile sums, and the NN tie rule makes the answer independent of the order
+// the grid build's integer atomics happen to give the points inside a cell.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <atomic>
+
+#include "../../include/bnv_fusion.h"
+#include "bnv_common.hpp"
+
+namespace bnv {
+
+static inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+
+// =====================================================================================================================
+// Surface sampling (trimesh.sample.sample_surface)
+// =====================================================================================================================
+constexpr int kAreaThreads = 256, kAreaItems = 8, kAreaTile = kAreaThreads * kAreaItems;
+constexpr uint64_t kUnpublished = ~0ull;   // a NaN bit pattern no prefix of finite non-negative areas can take
+
+struct SampleStatus {
+  double total;        // sum of all face areas (the last prefix)
+  uint32_t bad_faces;  // faces with a vertex index outside [0, n_vertices)
+  uint32_t pad;
+};
+
+struct SampleWs {
+  double* prefix;        // [F] inclusive prefix of the face areas
+  uint64_t* tile_incl;   // [tiles] inclusive prefix up to each tile's last face (double bits), kUnpublished until set
+  SampleStatus* status;
+};
+
+static size_t sample_ws_layout(int64_t n_faces, char* base, SampleWs* w) {
+  const int64_t tiles = (n_faces + kAreaTile - 1) / kAreaTile;
+  size_t off = 0;
+  const size_t o_prefix = off;
+  off += align256((size_t)n_faces * 8);
+  const size_t o_tiles = off;
+  off += align256((size_t)tiles * 8);
+  const size_t o_status = off;
+  off += align256(sizeof(SampleStatus));
+  if (w) {
+    w->prefix = (double*)(base + o_prefix);
+    w->tile_incl = (uint64_t*)(base + o_tiles);
+    w->status = (SampleStatus*)(base + o_status);
+  }
+  return off;
+}
+
+// fp32 cross product e1 x e2 and its length sqrt((cx*cx + cy*cy) + cz*cz): one rounding per operation
+__device__ __forceinline__ void tri_cross(const float* __restrict__ V, int32_t i0, int32_t i1, int32_t i2, float e1[3],
+                                          float e2[3], float c[3], float v0[3], float* len) {
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    v0[d] = V[(int64_t)i0 * 3 + d];
+    e1[d] = __fsub_rn(V[(int64_t)i1 * 3 + d], v0[d]);
+    e2[d] = __fsub_rn(V[(int64_t)i2 * 3 + d], v0[d]);
+  }
+  c[0] = __fsub_rn(__fmul_rn(e1[1], e2[2]), __fmul_rn(e1[2], e2[1]));
+  c[1] = __fsub_rn(__fmul_rn(e1[2], e2[0]), __fmul_rn(e1[0], e2[2]));
+  c[2] = __fsub_rn(__fmul_rn(e1[0], e2[1]), __fmul_rn(e1[1], e2[0]));
+  // sqrt in float64 rounded once to fp32 is the correctly rounded fp32 sqrt (53 >= 2 * 24 + 2 bits)
+  *len = (float)sqrt((double)__fadd_rn(__fadd_rn(__fmul_rn(c[0], c[0]), __fmul_rn(c[1], c[1])), __fmul_rn(c[2], c[2])));
+}
+
+// Face areas (0.5 * |e1 x e2| in fp32; 0 for a face with a bad index or a non-finite area) and their inclusive
+// prefix in float64.  Inside a tile: a fixed tree (per-thread runs, wave shuffles, wave totals in order).  Across
+// tiles: the decoupled look-back pattern of bnv_common.hpp cut down to its immediate predecessor -- a tile waits for
+// the inclusive prefix of tile - 1 and adds its own sum -- because float64 addition is not associative: the prefix
+// of every face is then the same sum in the same order on every run.  Tiles are dispatched in index order, so the
+// predecessor is resident or finished when a tile waits for it.
+__global__ __launch_bounds__(kAreaThreads) void k_face_area_prefix(const float* __restrict__ V, int64_t n_vertices,
+                                                                   const int32_t* __restrict__ Fc, int64_t n_faces,
+                                                                   SampleWs ws) {
+  __shared__ double s_wave[kAreaThreads / 64];
+  __shared__ double s_excl;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * kAreaTile + (int64_t)threadIdx.x * kAreaItems;
+  double run[kAreaItems];
+  double acc = 0.0;
+  uint32_t bad = 0;
+#pragma unroll
+  for (int e = 0; e < kAreaItems; ++e) {
+    const int64_t f = base + e;
+    double a = 0.0;
+    if (f < n_faces) {
+      const int32_t i0 = Fc[f * 3], i1 = Fc[f * 3 + 1], i2 = Fc[f * 3 + 2];
+      if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= n_vertices || i1 >= n_vertices || i2 >= n_vertices) {
+        bad = 1;
+      } else {
+        float e1[3], e2[3], c[3], v0[3], len;
+        tri_cross(V, i0, i1, i2, e1, e2, c, v0, &len);
+        const float af = __fmul_rn(0.5f, len);
+        if (af > 0.0f && af <= 3.4028234663852886e38f) a = (double)af;   // NaN / inf count as degenerate
+      }
+    }
+    acc += a;
+    run[e] = acc;
+  }
+  if (bad) atomicOr(&ws.status->bad_faces, 1u);
+  // wave inclusive scan of the per-thread sums (Hillis-Steele: the same tree every run)
+  double incl = acc;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const double o = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += o;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  double wbase = 0.0, tile_sum = 0.0;
+#pragma unroll
+  for (int w = 0; w < kAreaThreads / 64; ++w) {
+    if (w == wave) wbase = tile_sum;
+    tile_sum += s_wave[w];
+  }
+  if (threadIdx.x == 0) {
+    double excl = 0.0;
+    if (blockIdx.x > 0) {
+      uint64_t w;
+      do {
+        w = __hip_atomic_load(&ws.tile_incl[blockIdx.x - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } while (w == kUnpublished);
+      excl = __builtin_bit_cast(double, w);
+    }
+    const double tile_incl = excl + tile_sum;
+    __hip_atomic_store(&ws.tile_incl[blockIdx.x], __builtin_bit_cast(uint64_t, tile_incl), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+    s_excl = excl;
+  }
+  __syncthreads();
+  const double pre = (s_excl + wbase) + (incl - acc);   // everything before this thread's first face
+#pragma unroll
+  for (int e = 0; e < kAreaItems; ++e)
+    if (base + e < n_faces) {
+      ws.prefix[base + e] = pre + run[e];
+      if (base + e == n_faces - 1) ws.status->total = pre + run[e];   // the total IS the last prefix
+    }
+}
+
+// first index i in [0, n) with prefix[i] > key (n if none): a zero-area face never qualifies
+__device__ __forceinline__ int64_t first_greater(const double* __restrict__ prefix, int64_t n, double key) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (prefix[mid] > key) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void k_sample_surface(const float* __restrict__ V, const int32_t* __restrict__ Fc,
+                                                        int64_t n_faces, const float* __restrict__ U, int64_t n,
+                                                        SampleWs ws, float* __restrict__ pts,
+                                                        int32_t* __restrict__ face_ids, float* __restrict__ normals) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double total = ws.status->total;
+  const float u0 = U[i * 3], u1 = U[i * 3 + 1], u2 = U[i * 3 + 2];
+  const double key = (double)(u0 > 0.0f ? u0 : 0.0f) * total;
+  int64_t f = first_greater(ws.prefix, n_faces, key);
+  // a uniform outside [0, 1) (or NaN): the last face of positive area -- the first whose prefix reaches the total
+  if (f >= n_faces) f = first_greater(ws.prefix, n_faces, nextafter(total, -1.0));
+  if (f >= n_faces) f = n_faces - 1;   // (unreachable: prefix[n_faces - 1] == total)
+  float e1[3], e2[3], c[3], v0[3], len;
+  tri_cross(V, Fc[f * 3], Fc[f * 3 + 1], Fc[f * 3 + 2], e1, e2, c, v0, &len);
+  float a = u1, b = u2;
+  if (__fadd_rn(a, b) > 1.0f) {   // fold the square onto the triangle (sample.py: random_lengths -= 1; abs)
+    a = __fsub_rn(1.0f, a);
+    b = __fsub_rn(1.0f, b);
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) pts[i * 3 + d] = __fadd_rn(__fadd_rn(v0[d], __fmul_rn(e1[d], a)), __fmul_rn(e2[d], b));
+  face_ids[i] = (int32_t)f;
+  if (normals) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) normals[i * 3 + d] = len > 0.0f ? (float)((double)c[d] / (double)len) : 0.0f;
+  }
+}
+
+// =====================================================================================================================
+// Exact nearest neighbour on a uniform grid
+// =====================================================================================================================
+// Cell size rule.  The inputs are surface samples: n points on an area A occupy ~A / h^2 cells of edge h, so
+// h = sqrt(kCellTarget * A / n) puts ~kCellTarget points in an occupied cell.  A is estimated by half the bounding
+// box's surface, Lx Ly + Ly Lz + Lz Lx (a height field: ~its area; a closed room: half of it).  A set with no area
+// (a line: h = kCellTarget * L / n; a point: h = 1) and volumetric sets (the estimate asks for far more cells than
+// points) are covered by the cap: h grows by 5/4 until the grid has at most max(n_ref, 1) cells.
+constexpr double kCellTarget = 4.0;
+constexpr double kStopSlack = 1e-5;    // relative slack of the stop test (fp32 d^2 carries ~4 ulp of rounding)
+constexpr int kFineRings = 8;          // rings of the fine grid before a query moves on to the coarse grid
+constexpr double kCoarse = 4.0;        // coarse cell edge / fine cell edge
+constexpr int kScanThreads = 256, kScanItems = 4, kScanTile = kScanThreads * kScanItems;
+constexpr uint32_t kNoCell = 0xffffffffu;
+
+struct NnParams {
+  uint32_t bmin[3], bmax[3];   // order-preserving encodings of the finite reference points' bounding box
+  int32_t dims[3];
+  int32_t n_cells;             // 0: no finite reference point
+  double lo[3], fmin[3], fmax[3];
+  double h, inv_h;
+};
+
+struct NnWs {
+  NnParams* P;           // [2]: the fine grid, the coarse grid
+  uint32_t* ref_count;   // [n_ref + 2]: per cell, then the scan's end sentinel
+  uint32_t* ref_start;   // [n_ref + 2]
+  uint32_t* q_count;     // [n_ref + 2]: per cell, + one bucket for non-finite queries
+  uint32_t* q_start;     // [n_ref + 2]
+  uint32_t* ref_cell;    // [n_ref]
+  uint32_t* ref_slot;
+  uint32_t* q_cell;      // [n_query]
+  uint32_t* q_slot;
+  uint64_t* scan_state;  // [3 * tiles] look-back words of the three scans
+  float4* ref_sorted;    // [n_ref] (x, y, z, bitcast(index)) in cell order
+  float4* q_sorted;      // [n_query]
+  uint32_t* rc_count;    // the coarse grid's: [n_ref + 2]
+  uint32_t* rc_start;    // [n_ref + 2]
+  uint32_t* rc_cell;     // [n_ref]
+  uint32_t* rc_slot;     // [n_ref]
+  float4* rc_sorted;     // [n_ref]
+};
+
+static size_t nn_ws_layout(int64_t n_ref, int64_t n_query, char* base, NnWs* w) {
+  const int64_t n_bins = n_ref + 2;
+  const int64_t tiles = (n_bins + kScanTile - 1) / kScanTile;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return base + o; };
+  char* p[17];
+  p[0] = take(2 * sizeof(NnParams));
+  p[1] = take((size_t)n_bins * 4);
+  p[2] = take((size_t)n_bins * 4);
+  p[3] = take((size_t)n_bins * 4);
+  p[4] = take((size_t)n_bins * 4);
+  p[5] = take((size_t)n_ref * 4);
+  p[6] = take((size_t)n_ref * 4);
+  p[7] = take((size_t)n_query * 4);
+  p[8] = take((size_t)n_query * 4);
+  p[9] = take((size_t)tiles * 3 * 8);
+  p[10] = take((size_t)n_ref * 16);
+  p[11] = take((size_t)n_query * 16);
+  p[12] = take((size_t)n_bins * 4);
+  p[13] = take((size_t)n_bins * 4);
+  p[14] = take((size_t)n_ref * 4);
+  p[15] = take((size_t)n_ref * 4);
+  p[16] = take((size_t)n_ref * 16);
+  if (w) {
+    w->P = (NnParams*)p[0];
+    w->ref_count = (uint32_t*)p[1];
+    w->ref_start = (uint32_t*)p[2];
+    w->q_count = (uint32_t*)p[3];
+    w->q_start = (uint32_t*)p[4];
+    w->ref_cell = (uint32_t*)p[5];
+    w->ref_slot = (uint32_t*)p[6];
+    w->q_cell = (uint32_t*)p[7];
+    w->q_slot = (uint32_t*)p[8];
+    w->scan_state = (uint64_t*)p[9];
+    w->ref_sorted = (float4*)p[10];
+    w->q_sorted = (float4*)p[11];
+    w->rc_count = (uint32_t*)p[12];
+    w->rc_start = (uint32_t*)p[13];
+    w->rc_cell = (uint32_t*)p[14];
+    w->rc_slot = (uint32_t*)p[15];
+    w->rc_sorted = (float4*)p[16];
+  }
+  return off;
+}
+
+__device__ __forceinline__ uint32_t f2ord(float x) {   // order-preserving float -> uint32
+  const uint32_t b = __builtin_bit_cast(uint32_t, x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t k) {
+  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+  return isfinite(x) && isfinite(y) && isfinite(z);
+}
+
+// bounding box of the finite reference points: a wave reduction, the block's waves through LDS, one integer-encoded
+// atomic min / max per component per block
+__global__ __launch_bounds__(256) void k_nn_bbox(const float* __restrict__ R, int64_t n, NnParams* __restrict__ P) {
+  uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float x = R[i * 3], y = R[i * 3 + 1], z = R[i * 3 + 2];
+    if (!finite3(x, y, z)) continue;
+    const uint32_t k[3] = {f2ord(x), f2ord(y), f2ord(z)};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      mn[d] = min(mn[d], k[d]);
+      mx[d] = max(mx[d], k[d]);
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+      mn[d] = min(mn[d], (uint32_t)__shfl_xor((int)mn[d], s, 64));
+      mx[d] = max(mx[d], (uint32_t)__shfl_xor((int)mx[d], s, 64));
+    }
+  __shared__ uint32_t s_mn[4][3], s_mx[4][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0)
+    for (int d = 0; d < 3; ++d) {
+      s_mn[wave][d] = mn[d];
+      s_mx[wave][d] = mx[d];
+    }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int d = threadIdx.x;
+    uint32_t a = s_mn[0][d], b = s_mx[0][d];
+    for (int w = 1; w < 4; ++w) {
+      a = min(a, s_mn[w][d]);
+      b = max(b, s_mx[w][d]);
+    }
+    atomicMin(&P->bmin[d], a);
+    atomicMax(&P->bmax[d], b);
+  }
+}
+
+// the grid of cell size h (grown by 5/4 until it has at most `cap` cells) over the bounding box in P
+__device__ void nn_grid(NnParams* __restrict__ P, const double L[3], double h, double cap) {
+  double dims[3];
+  for (;;) {
+    for (int d = 0; d < 3; ++d) dims[d] = fmin(floor(L[d] / h) + 1.0, 2147483647.0);
+    if (dims[0] * dims[1] * dims[2] <= cap) break;
+    h *= 1.25;
+  }
+  for (int d = 0; d < 3; ++d) P->dims[d] = (int32_t)dims[d];
+  P->n_cells = (int32_t)(dims[0] * dims[1] * dims[2]);
+  P->h = h;
+  P->inv_h = 1.0 / h;
+}
+
+// P[0]: the fine grid (the cell size rule above); P[1]: the coarse grid, cells kCoarse times larger
+__global__ void k_nn_params(NnParams* __restrict__ P, int64_t n_ref) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (P->bmin[0] > P->bmax[0]) {   // no finite reference point
+    for (int g = 0; g < 2; ++g) {
+      P[g].n_cells = 0;
+      for (int d = 0; d < 3; ++d) {
+        P[g].dims[d] = 1;
+        P[g].lo[d] = P[g].fmin[d] = P[g].fmax[d] = 0.0;
+      }
+      P[g].h = P[g].inv_h = 1.0;
+    }
+    return;
+  }
+  double L[3];
+  for (int d = 0; d < 3; ++d) {
+    P->fmin[d] = P->lo[d] = (double)ord2f(P->bmin[d]);
+    P->fmax[d] = (double)ord2f(P->bmax[d]);
+    L[d] = P->fmax[d] - P->fmin[d];
+  }
+  const double n = (double)n_ref;
+  const double S = L[0] * L[1] + L[1] * L[2] + L[2] * L[0];
+  const double Lmax = fmax(L[0], fmax(L[1], L[2]));
+  double h = S > 0.0 ? sqrt(kCellTarget * S / n) : (Lmax > 0.0 ? kCellTarget * Lmax / n : 1.0);
+  if (!(h > 0.0) || !isfinite(h)) h = Lmax > 0.0 && isfinite(Lmax) ? Lmax : 1.0;
+  const double cap = fmax(n, 1.0);
+  nn_grid(P, L, h, cap);
+  for (int d = 0; d < 3; ++d) {
+    P[1].bmin[d] = P->bmin[d];
+    P[1].bmax[d] = P->bmax[d];
+    P[1].lo[d] = P->lo[d];
+    P[1].fmin[d] = P->fmin[d];
+    P[1].fmax[d] = P->fmax[d];
+  }
+  nn_grid(P + 1, L, P->h * kCoarse, cap);
+}
+
+__device__ __forceinline__ int cell_axis(float x, double lo, double inv_h, int dim) {
+  double t = floor(((double)x - lo) * inv_h);
+  t = fmin(fmax(t, 0.0), (double)(dim - 1));
+  return (int)t;
+}
+
+// cell of every point (query: the clamped cell; non-finite: the extra bucket n_cells) and its slot in the cell.  The
+// slots follow the order the atomics happen in; results do not depend on it (tie rule), only the layout does.
+__global__ __launch_bounds__(256) void k_nn_count(const float* __restrict__ X, int64_t n, const NnParams* __restrict__ P,
+                                                  int is_query, uint32_t* __restrict__ count,
+                                                  uint32_t* __restrict__ cell_of, uint32_t* __restrict__ slot_of) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float x = X[i * 3], y = X[i * 3 + 1], z = X[i * 3 + 2];
+  uint32_t c;
+  if (!finite3(x, y, z) || P->n_cells == 0) {
+    c = is_query ? (uint32_t)P->n_cells : kNoCell;
+  } else {
+    const int cx = cell_axis(x, P->lo[0], P->inv_h, P->dims[0]);
+    const int cy = cell_axis(y, P->lo[1], P->inv_h, P->dims[1]);
+    const int cz = cell_axis(z, P->lo[2], P->inv_h, P->dims[2]);
+    c = (uint32_t)(((int64_t)cx * P->dims[1] + cy) * P->dims[2] + cz);
+  }
+  cell_of[i] = c;
+  if (c != kNoCell) slot_of[i] = atomicAdd(&count[c], 1u);
+}
+
+// exclusive scan of count[0 .. n_bins) -> start (bnv_common.hpp's uint32 block scan + decoupled look-back)
+__global__ __launch_bounds__(kScanThreads) void k_nn_scan(const uint32_t* __restrict__ count, int64_t n_bins,
+                                                          uint32_t* __restrict__ start, uint64_t* __restrict__ state,
+                                                          uint32_t epoch) {
+  __shared__ uint32_t wave_tot[kScanThreads / 64];
+  __shared__ uint32_t s_excl;
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  uint32_t v[kScanItems], s = 0;
+#pragma unroll
+  for (int e = 0; e < kScanItems; ++e) {
+    v[e] = base + e < n_bins ? count[base + e] : 0u;
+    s += v[e];
+  }
+  uint32_t total;
+  uint32_t run = block_exclusive_scan<kScanThreads>(s, wave_tot, &total);
+  if (threadIdx.x < 64) {
+    const uint32_t excl = lookback_exclusive(state, (int)blockIdx.x, total, epoch);
+    if (threadIdx.x == 0) s_excl = excl;
+  }
+  __syncthreads();
+  run += s_excl;
+#pragma unroll
+  for (int e = 0; e < kScanItems; ++e) {
+    if (base + e < n_bins) start[base + e] = run;
+    run += v[e];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_nn_scatter(const float* __restrict__ X, int64_t n,
+                                                    const uint32_t* __restrict__ cell_of,
+                                                    const uint32_t* __restrict__ slot_of,
+                                                    const uint32_t* __restrict__ start, float4* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t c = cell_of[i];
+  if (c == kNoCell) return;
+  out[start[c] + slot_of[i]] = make_float4(X[i * 3], X[i * 3 + 1], X[i * 3 + 2], __builtin_bit_cast(float, (int32_t)i));
+}
+
+// (d2, idx) lexicographic: the lowest reference index wins a tie
+__device__ __forceinline__ void nn_take(float d2, int32_t idx, float& best, int32_t& bi) {
+  if (d2 < best || (d2 == best && idx < bi)) {
+    best = d2;
+    bi = idx;
+  }
+}
+
+__device__ __forceinline__ float nn_d2(float qx, float qy, float qz, const float4 r) {
+  const float dx = __fsub_rn(qx, r.x), dy = __fsub_rn(qy, r.y), dz = __fsub_rn(qz, r.z);
+  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
+// Can the search stop after ring r?  A point of an unvisited cell lies beyond one face of the box of visited cells on
+// some axis a (by at least the query's distance to that face, minus a slack for the rounding of the cell assignment)
+// and inside the reference bounding box on the other axes.  Stop when that lower bound on the real d^2 exceeds the best
+// fp32 d^2 by the relative slack (continue while it is <=), or when the ring covers the grid.
+__device__ __forceinline__ bool nn_can_stop(const NnParams& P, const int c[3], int r, const double q[3], float best) {
+  double gd2[3], base = 0.0;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const double g = fmax(fmax(P.fmin[d] - q[d], q[d] - P.fmax[d]), 0.0);
+    gd2[d] = g * g;
+    base += gd2[d];
+  }
+  double lb = INFINITY;
+  bool open = false;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const double slack = 1e-12 * (fabs(q[d]) + fabs(P.lo[d]) + (double)P.dims[d] * P.h) + 1e-9 * P.h;
+    if (c[d] - r > 0) {
+      open = true;
+      const double f = fmax(q[d] - (P.lo[d] + (double)(c[d] - r) * P.h) - slack, 0.0);
+      lb = fmin(lb, f * f + (base - gd2[d]));
+    }
+    if (c[d] + r < P.dims[d] - 1) {
+      open = true;
+      const double f = fmax((P.lo[d] + (double)(c[d] + r + 1) * P.h) - q[d] - slack, 0.0);
+      lb = fmin(lb, f * f + (base - gd2[d]));
+    }
+  }
+  if (!open) return true;
+  return lb > (double)best * (1.0 + kStopSlack) + 1e-30;
+}
+
+// Ring search of one query on one grid, from ring 0 up to ring `rmax` or until the stop test proves (best, bi) final
+// (-> true).  A cell run is read straight from the cell-ordered copy of R (float4: one 16-byte load per point).
+__device__ __forceinline__ bool nn_rings(const NnParams& P, const uint32_t* __restrict__ rstart,
+                                         const float4* __restrict__ Rs, const float4 qv, const double q[3], int rmax,
+                                         float& best, int32_t& bi) {
+  const int c[3] = {cell_axis(qv.x, P.lo[0], P.inv_h, P.dims[0]), cell_axis(qv.y, P.lo[1], P.inv_h, P.dims[1]),
+                    cell_axis(qv.z, P.lo[2], P.inv_h, P.dims[2])};
+  for (int r = 0; r <= rmax; ++r) {
+    const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, P.dims[0] - 1);
+    const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, P.dims[1] - 1);
+    const int zl = c[2] - r, zh = c[2] + r;
+    for (int x = x0; x <= x1; ++x)
+      for (int y = y0; y <= y1; ++y) {
+        const bool shell = x == c[0] - r || x == c[0] + r || y == c[1] - r || y == c[1] + r;
+        // the ring's cells of this (x, y) column: a contiguous z-run on the shell, else its two ends
+        for (int part = 0; part < (shell ? 1 : 2); ++part) {
+          int za, zb;
+          if (shell) {
+            za = max(zl, 0);
+            zb = min(zh, P.dims[2] - 1);
+          } else {
+            za = zb = part == 0 ? zl : zh;
+            if (za < 0 || za >= P.dims[2]) continue;
+          }
+          if (za > zb) continue;
+          const int64_t col = ((int64_t)x * P.dims[1] + y) * P.dims[2];
+          const uint32_t e = rstart[col + zb + 1];
+          for (uint32_t k = rstart[col + za]; k < e; ++k) {
+            const float4 rv = Rs[k];
+            nn_take(nn_d2(qv.x, qv.y, qv.z, rv), __builtin_bit_cast(int32_t, rv.w), best, bi);
+          }
+        }
+      }
+    if (nn_can_stop(P, c, r, q, best)) return true;
+  }
+  return false;
+}
+
+// One thread per query (measured on the fine grid alone against one wave per query, whose lanes split every cell run
+// and reduce the best per ring: 3.0 against 2.4 ms at 1M x 1M, 0.22 against 0.18 ms at 100k x 100k; surface cells
+// hold a handful of points, too few for 64 lanes).  Queries arrive in the fine grid's cell order (q_sorted), so neighbouring threads
+// walk the same cells.  A query that the first kFineRings rings of the fine grid do not settle (a query far from
+// every reference point: the fine grid would visit ~(distance / h)^3 mostly empty cells) goes on with the best it
+// has on the coarse grid (cells kCoarse times larger): points seen twice change nothing under the tie rule, and the
+// coarse search is exact on its own.  kFineRings / kCoarse trade the two cases: 4 / 8 cost 1M x 1M 9.2 ms and a
+// 100k query set lying up to a metre off a 2.4M-point mesh 1.6 s; 8 / 4: 5.7 ms and 2.4 s; the fine grid alone:
+// 2.4 ms and 4.6 s.
+__global__ __launch_bounds__(256) void k_nn_query(const float4* __restrict__ Qs, int64_t n_query,
+                                                  const NnParams* __restrict__ Pp, const float4* __restrict__ Rs,
+                                                  const uint32_t* __restrict__ rstart, const float4* __restrict__ Rc,
+                                                  const uint32_t* __restrict__ cstart, float* __restrict__ d2_out,
+                                                  int32_t* __restrict__ idx_out) {
+  const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= n_query) return;
+  const float4 qv = Qs[item];
+  const int32_t qi = __builtin_bit_cast(int32_t, qv.w);
+  float best = INFINITY;
+  int32_t bi = -1;
+  if (Pp[0].n_cells > 0 && finite3(qv.x, qv.y, qv.z)) {
+    const double q[3] = {(double)qv.x, (double)qv.y, (double)qv.z};
+    const NnParams& F = Pp[0];
+    if (!nn_rings(F, rstart, Rs, qv, q, kFineRings, best, bi)) {
+      const NnParams& G = Pp[1];
+      nn_rings(G, cstart, Rc, qv, q, max(G.dims[0], max(G.dims[1], G.dims[2])), best, bi);
+    }
+  }
+  d2_out[qi] = best;
+  idx_out[qi] = bi;
+}
+
+}  // namespace bnv
+
+using namespace bnv;
+
+extern "C" {
+
+int bnv_mesh_sample_surface_workspace(int64_t n_faces, int64_t* bytes) {
+  if (!bytes || n_faces <= 0 || n_faces > INT32_MAX) return BNV_ERR_INVALID_ARGUMENT;
+  *bytes = (int64_t)sample_ws_layout(n_faces, nullptr, nullptr);
+  return BNV_OK;
+}
+
+int bnv_mesh_sample_surface(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                            const float* uniforms, int64_t n, void* workspace, int64_t ws_bytes, float* points_out,
+                            int32_t* face_ids_out, float* normals_out, bnv_stream_t stream) {
+  if (!vertices || !faces || !uniforms || !workspace || !points_out || !face_ids_out) return BNV_ERR_INVALID_ARGUMENT;
+  if (n_vertices <= 0 || n_vertices > INT32_MAX || n_faces <= 0 || n_faces > INT32_MAX || n <= 0 || n > INT32_MAX)
+    return BNV_ERR_INVALID_ARGUMENT;
+  if (ws_bytes < (int64_t)sample_ws_layout(n_faces, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  hipStream_t s = (hipStream_t)stream;
+  SampleWs ws;
+  sample_ws_layout(n_faces, (char*)workspace, &ws);
+  const int64_t tiles = (n_faces + kAreaTile - 1) / kAreaTile;
+  BNV_HIP_CHECK(hipMemsetAsync(ws.tile_incl, 0xff, (size_t)tiles * 8, s));
+  BNV_HIP_CHECK(hipMemsetAsync(ws.status, 0, sizeof(SampleStatus), s));
+  hipLaunchKernelGGL(k_face_area_prefix, dim3((unsigned)tiles), dim3(kAreaThreads), 0, s, vertices, n_vertices, faces,
+                     n_faces, ws);
+  BNV_LAUNCH_CHECK();
+  // the one read of device data: a mesh without area (or with a bad vertex index) cannot be sampled
+  SampleStatus st;
+  BNV_HIP_CHECK(hipMemcpyAsync(&st, ws.status, sizeof(st), hipMemcpyDeviceToHost, s));
+  BNV_HIP_CHECK(hipStreamSynchronize(s));
+  if (st.bad_faces || !(st.total > 0.0)) return BNV_ERR_INVALID_ARGUMENT;
+  hipLaunchKernelGGL(k_sample_surface, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, vertices, faces, n_faces,
+                     uniforms, n, ws, points_out, face_ids_out, normals_out);
+  BNV_LAUNCH_CHECK();
+  return BNV_OK;
+}
+
+int bnv_nn_workspace_bytes(int64_t n_ref, int64_t n_query, int64_t* bytes) {
+  if (!bytes || n_ref <= 0 || n_query <= 0 || n_ref > INT32_MAX - 2 || n_query > INT32_MAX)
+    return BNV_ERR_INVALID_ARGUMENT;
+  *bytes = (int64_t)nn_ws_layout(n_ref, n_query, nullptr, nullptr);
+  return BNV_OK;
+}
+
+int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_query, void* workspace,
+                 int64_t ws_bytes, float* d2_out, int32_t* idx_out, bnv_stream_t stream) {
+  if (!ref || !query || !workspace || !d2_out || !idx_out) return BNV_ERR_INVALID_ARGUMENT;
+  if (n_ref <= 0 || n_query <= 0 || n_ref > INT32_MAX - 2 || n_query > INT32_MAX) return BNV_ERR_INVALID_ARGUMENT;
+  if (ws_bytes < (int64_t)nn_ws_layout(n_ref, n_query, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  hipStream_t s = (hipStream_t)stream;
+  NnWs w;
+  nn_ws_layout(n_ref, n_query, (char*)workspace, &w);
+  const int64_t n_bins = n_ref + 2;
+  const int64_t tiles = (n_bins + kScanTile - 1) / kScanTile;
+  // everything the build accumulates into starts from a known state on every call (also when replayed from a graph):
+  // the bounding box, the counts, the look-back words (0 = an epoch next_epoch never hands out)
+  BNV_HIP_CHECK(hipMemsetAsync(w.P, 0, 2 * sizeof(NnParams), s));
+  BNV_HIP_CHECK(hipMemsetAsync(w.P, 0xff, 3 * sizeof(uint32_t), s));   // bmin (first member) = the largest key
+  BNV_HIP_CHECK(hipMemsetAsync(w.ref_count, 0, (size_t)n_bins * 4, s));
+  BNV_HIP_CHECK(hipMemsetAsync(w.q_count, 0, (size_t)n_bins * 4, s));
+  BNV_HIP_CHECK(hipMemsetAsync(w.rc_count, 0, (size_t)n_bins * 4, s));
+  BNV_HIP_CHECK(hipMemsetAsync(w.scan_state, 0, (size_t)tiles * 3 * 8, s));
+  const unsigned bbox_blocks = (unsigned)std::min<int64_t>((n_ref + 255) / 256, 2048);
+  const dim3 ref_blocks((unsigned)((n_ref + 255) / 256)), q_blocks((unsigned)((n_query + 255) / 256));
+  hipLaunchKernelGGL(k_nn_bbox, dim3(bbox_blocks), dim3(256), 0, s, ref, n_ref, w.P);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_nn_params, dim3(1), dim3(64), 0, s, w.P, n_ref);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_nn_count, ref_blocks, dim3(256), 0, s, ref, n_ref, w.P, 0, w.ref_count, w.ref_cell, w.ref_slot);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_nn_count, ref_blocks, dim3(256), 0, s, ref, n_ref, w.P + 1, 0, w.rc_count, w.rc_cell, w.rc_slot);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_nn_count, q_blocks, dim3(256), 0, s, query, n_query, w.P, 1, w.q_count, w.q_cell, w.q_slot);
+  BNV_LAUNCH_CHECK();
+  uint32_t* counts[3] = {w.ref_count, w.rc_count, w.q_count};
+  uint32_t* starts[3] = {w.ref_start, w.rc_start, w.q_start};
+  for (int k = 0; k < 3; ++k) {
+    hipLaunchKernelGGL(k_nn_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, counts[k], n_bins, starts[k],
+                       w.scan_state + k * tiles, next_epoch());
+    BNV_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_nn_scatter, ref_blocks, dim3(256), 0, s, ref, n_ref, w.ref_cell, w.ref_slot, w.ref_start,
+                     w.ref_sorted);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_nn_scatter, ref_blocks, dim3(256), 0, s, ref, n_ref, w.rc_cell, w.rc_slot, w.rc_start,
+                     w.rc_sorted);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_nn_scatter, q_blocks, dim3(256), 0, s, query, n_query, w.q_cell, w.q_slot, w.q_start,
+                     w.q_sorted);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_nn_query, q_blocks, dim3(256), 0, s, w.q_sorted, n_query, w.P, w.ref_sorted, w.ref_start,
+                     w.rc_sorted, w.rc_start, d2_out, idx_out);
+  BNV_LAUNCH_CHECK();
+  return BNV_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,191 @@
+"""Mesh quality against a ground-truth mesh: the reference's end metric (src/scripts/evaluate_bnvf.py:9-31,
+src/scripts/compute_chamfer.py:36-75) on the GPU.
+
+The reference samples 100,000 points on each mesh (trimesh ``sample_surface``), finds every point's nearest neighbour on
+the other side (sklearn ball tree) and reports the pred -> gt mean distance, precision at 2.5 cm, the gt -> pred mean
+distance, recall at 2.5 cm and F1.  Here the sampling and the exact nearest-neighbour search are HIP kernels
+(csrc/eval.hip; include/bnv_fusion.h: bnv_mesh_sample_surface, bnv_nn_query); only the reductions that turn
+distances into figures (a mean, a count under the threshold) run in torch, in float64.  Inputs live on the GPU: a CPU
+tensor is refused, there is no CPU fallback.
+
+    res = evaluate_meshes(pred_mesh, gt_mesh)               # TriMesh or (vertices, faces) device tensors
+    print(summary_line(res))                                # "{:.3f}/{:.4f}/{:.3f}/{:.4f}/{:.4f}", as the reference
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .mesh import TriMesh
+
+KEYS = ("pred_gt", "accuracy", "gt_pred", "recall", "F1")
+
+
+def _device(device):
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise ValueError(f"device {dev}: the mesh evaluation runs on the GPU only (no CPU fallback)")
+    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+
+
+def _on_gpu(t, what, dtype):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch tensor on the GPU, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: a CPU tensor; the mesh evaluation runs on the GPU only (no CPU fallback)")
+    return t.detach().to(dtype).contiguous()
+
+
+def _points(t, what):
+    t = _on_gpu(t, what, torch.float32)
+    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] == 0:
+        raise ValueError(f"{what}: expected a non-empty [N, 3] tensor, got {tuple(t.shape)}")
+    return t
+
+
+def _mesh_tensors(mesh, faces=None, device=None):
+    """TriMesh (host) -> device tensors; (vertices, faces) device tensors are checked and passed through."""
+    if isinstance(mesh, TriMesh):
+        if faces is not None:
+            raise ValueError("a TriMesh carries its faces: do not pass `faces` with it")
+        dev = _device(device)
+        return (torch.from_numpy(np.ascontiguousarray(mesh.vertices, dtype=np.float32)).to(dev),
+                torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int32)).to(dev))
+    if faces is None:
+        raise ValueError("faces are needed with a vertex tensor")
+    v = _points(mesh, "vertices")
+    f = _on_gpu(faces, "faces", torch.int32)
+    if f.device != v.device:
+        raise ValueError(f"faces on {f.device}, vertices on {v.device}")
+    if f.dim() != 2 or f.shape[1] != 3 or f.shape[0] == 0:
+        raise ValueError(f"faces: expected a non-empty [T, 3] tensor, got {tuple(f.shape)}")
+    return v, f
+
+
+def _uniforms(n, generator, dev):
+    if generator is not None and generator.device.type != "cuda":
+        return torch.rand((n, 3), generator=generator, dtype=torch.float32).to(dev)
+    return torch.rand((n, 3), generator=generator, dtype=torch.float32, device=dev)
+
+
+def sample_surface_uniforms(vertices, faces, uniforms, return_normals=False):
+    """trimesh's ``sample_surface`` with the uniforms given: ``uniforms`` fp32 [n, 3] in [0, 1) on the mesh's device ->
+    (points fp32 [n, 3], face_ids int64 [n][, unit face normals fp32 [n, 3]]).  Deterministic: the same inputs give the
+    same bits (include/bnv_fusion.h: bnv_mesh_sample_surface)."""
+    v, f = _mesh_tensors(vertices, faces)
+    u = _points(uniforms, "uniforms")
+    if u.device != v.device:
+        raise ValueError(f"uniforms on {u.device}, mesh on {v.device}")
+    lib = _lib.load()
+    n = int(u.shape[0])
+    ws_bytes = C.c_int64()
+    _lib.check(lib.bnv_mesh_sample_surface_workspace(int(f.shape[0]), C.byref(ws_bytes)),
+               "bnv_mesh_sample_surface_workspace")
+    with torch.cuda.device(v.device):
+        ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=v.device)
+        pts = torch.empty((n, 3), dtype=torch.float32, device=v.device)
+        ids = torch.empty(n, dtype=torch.int32, device=v.device)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=v.device) if return_normals else None
+        _lib.check(lib.bnv_mesh_sample_surface(_lib.ptr(v), int(v.shape[0]), _lib.ptr(f), int(f.shape[0]), _lib.ptr(u),
+                                               n, _lib.ptr(ws), int(ws_bytes.value), _lib.ptr(pts), _lib.ptr(ids),
+                                               _lib.ptr(nrm), _lib.stream_ptr()),
+                   "bnv_mesh_sample_surface (a mesh without area, or a face index out of range?)")
+    return (pts, ids.long(), nrm) if return_normals else (pts, ids.long())
+
+
+def sample_surface(vertices, faces=None, n=100000, generator=None, return_normals=False, device=None):
+    """``n`` area-weighted samples on a mesh (trimesh.sample.sample_surface, which the reference calls): ``vertices``
+    fp32 [V, 3] and ``faces`` int [T, 3] device tensors, or a TriMesh (uploaded to ``device``, default the current
+    GPU).  The uniforms come from ``torch.rand(generator=generator)``.  -> (points [n, 3], face_ids [n][, normals])."""
+    v, f = _mesh_tensors(vertices, faces, device)
+    return sample_surface_uniforms(v, f, _uniforms(int(n), generator, v.device), return_normals)
+
+
+def nn_d2(query, ref):
+    """Exact nearest neighbour in ``ref`` of every point of ``query`` (fp32 [N, 3] device tensors) -> (d2 fp32 [N], idx
+    int32 [N]): d2 is bitwise the minimum over ``ref`` of the fp32 (dx*dx + dy*dy) + dz*dz, idx the lowest reference
+    index attaining it.  A reference point with a NaN / Inf coordinate is never returned; such a query gets (+inf, -1)."""
+    q = _points(query, "query")
+    r = _points(ref, "ref")
+    if q.device != r.device:
+        raise ValueError(f"query on {q.device}, ref on {r.device}")
+    lib = _lib.load()
+    ws_bytes = C.c_int64()
+    _lib.check(lib.bnv_nn_workspace_bytes(int(r.shape[0]), int(q.shape[0]), C.byref(ws_bytes)), "bnv_nn_workspace_bytes")
+    with torch.cuda.device(q.device):
+        ws = torch.empty(int(ws_bytes.value), dtype=torch.uint8, device=q.device)
+        d2 = torch.empty(q.shape[0], dtype=torch.float32, device=q.device)
+        idx = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
+        _lib.check(lib.bnv_nn_query(_lib.ptr(r), int(r.shape[0]), _lib.ptr(q), int(q.shape[0]), _lib.ptr(ws),
+                                    int(ws_bytes.value), _lib.ptr(d2), _lib.ptr(idx), _lib.stream_ptr()), "bnv_nn_query")
+    return d2, idx
+
+
+def nearest_neighbors(query, ref):
+    """-> (dist float64 [N] = sqrt(d2) taken in float64, idx int64 [N]); see ``nn_d2``."""
+    d2, idx = nn_d2(query, ref)
+    return torch.sqrt(d2.double()), idx.long()
+
+
+def metrics_from_distances(d_pred_gt, d_gt_pred, threshold=0.025):
+    """The five figures of evaluate_bnvf.py:9-31 from the two distance vectors (float64 on the device): means, strict
+    ``<`` counts, F1 = 2PR / (P + R) -- nan when P + R = 0, as the reference's numpy gives."""
+    a = d_pred_gt.double()
+    b = d_gt_pred.double()
+    vals = torch.stack([a.mean(), (a < threshold).double().sum() / a.numel(),
+                        b.mean(), (b < threshold).double().sum() / b.numel()]).tolist()
+    p, r = vals[1], vals[3]
+    f1 = 2 * p * r / (p + r) if (p + r) != 0 else float("nan")
+    return dict(zip(KEYS, vals[:4] + [f1]))
+
+
+def evaluate(pred_points, gt_points, threshold=0.025):
+    """evaluate_bnvf.py:9-31: nearest neighbours both ways -> {"pred_gt", "accuracy", "gt_pred", "recall", "F1"}
+    (accuracy = precision = fraction of predicted points closer than ``threshold`` to the ground truth)."""
+    d_pg, _ = nearest_neighbors(pred_points, gt_points)
+    d_gp, _ = nearest_neighbors(gt_points, pred_points)
+    return metrics_from_distances(d_pg, d_gp, threshold)
+
+
+def evaluate_meshes(pred, gt, n_samples=100000, threshold=0.025, vertices_only=False, normals=False, generator=None,
+                    device=None, gt_recall=None):
+    """compute_chamfer.py:36-75 / evaluate_bnvf.py:56-72: ``n_samples`` surface samples on each mesh (TriMesh or
+    (vertices, faces) device tensors), then ``evaluate``.
+
+    vertices_only: the ground truth is a ``torch.randperm`` subset of ``n_samples`` of its vertices
+    (compute_chamfer.py:40-41) instead of surface samples.  normals: adds ``normal_consistency`` -- the signed mean of
+    gt_normal . pred_normal[idx], idx from the gt -> pred query (compute_chamfer.py:66-75).  gt_recall: optionally a
+    second ground truth for the recall side (a region every view saw: synthetic.gt_mesh("common")) -- the precision
+    side then uses ``gt`` and the recall side ``gt_recall``."""
+    if normals and vertices_only:
+        raise ValueError("normals need surface samples of the ground truth (compute_chamfer.py:73)")
+    dev = _device(device if device is not None else (pred[0].device if isinstance(pred, tuple) else None))
+    pv, pf = _mesh_tensors(*pred) if isinstance(pred, tuple) else _mesh_tensors(pred, None, dev)
+
+    def gt_side(mesh):
+        gv, gf = _mesh_tensors(*mesh) if isinstance(mesh, tuple) else _mesh_tensors(mesh, None, dev)
+        if vertices_only:
+            perm = torch.randperm(int(gv.shape[0]), generator=generator,
+                                  device="cpu" if generator is None or generator.device.type != "cuda" else dev)
+            return gv[perm[:n_samples].to(dev)], None
+        s = sample_surface(gv, gf, n_samples, generator=generator, return_normals=normals)
+        return s[0], (s[2] if normals else None)
+
+    p = sample_surface(pv, pf, n_samples, generator=generator, return_normals=normals)
+    pred_pts = p[0]
+    gt_pts, gt_nrm = gt_side(gt)
+    d_pg, _ = nearest_neighbors(pred_pts, gt_pts)
+    if gt_recall is not None:
+        gt_pts, gt_nrm = gt_side(gt_recall)
+    d_gp, idx = nearest_neighbors(gt_pts, pred_pts)
+    res = metrics_from_distances(d_pg, d_gp, threshold)
+    if normals:
+        dots = (gt_nrm.double() * p[2].double()[idx]).sum(-1)
+        res["normal_consistency"] = float(dots.mean())
+    return res
+
+
+def summary_line(res):
+    """The reference's one-line summary: pred_gt / accuracy / gt_pred / recall / F1."""
+    return "{:.3f}/{:.4f}/{:.3f}/{:.4f}/{:.4f}".format(*[res[k] for k in KEYS])

@@ -188,3 +188,122 @@ def post_process_mesh(mesh, vertex_threshold=0.005):
     deg = np.asarray(adj.sum(1)).reshape(-1)
     vs = (vm + adj @ vm) / (1.0 + deg)[:, None]
     return TriMesh(vs.astype(np.float32), f)
+
+
+_PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
+                "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
+                "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+_PLY_COUNT_TYPES = ("uchar", "uint8")
+_PLY_INDEX_TYPES = ("int", "uint", "int32", "uint32")
+
+
+def _fan(polys):
+    """Polygons (lists of vertex indices) -> triangles, each polygon as a fan around its first vertex."""
+    tris = []
+    for p in polys:
+        if len(p) < 3:
+            raise ValueError(f"PLY face with {len(p)} vertices")
+        for k in range(1, len(p) - 1):
+            tris.append((p[0], p[k], p[k + 1]))
+    return tris
+
+
+def load_ply(path):
+    """PLY -> TriMesh: ASCII or binary little-endian, as ``TriMesh.export`` and most ground-truth meshes are written.
+    Vertices: ``float`` / ``double`` x, y, z, possibly with further scalar properties (normals, ``uchar`` colours ...),
+    which are read past.  Faces: ``property list uchar|uint8 int|uint|int32|uint32 vertex_indices`` (or
+    ``vertex_index``); quads and larger polygons are triangulated as fans.  Anything else -- big-endian data, list
+    properties on vertices, extra face properties, other elements with data -- fails with a ValueError naming it."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    nl = data.find(b"\n", end)
+    body = data[nl + 1:]
+    fmt = None
+    elements = []                      # [name, count, [(prop name, dtype) | (name, ("list", count dtype, item dtype))]]
+    for raw in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        tok = raw.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: property before any element")
+            if tok[1] == "list":
+                elements[-1][2].append((tok[4], ("list", tok[2], tok[3])))
+            else:
+                if tok[1] not in _PLY_SCALARS:
+                    raise ValueError(f"{path}: unknown PLY property type {tok[1]!r}")
+                elements[-1][2].append((tok[2], tok[1]))
+        else:
+            raise ValueError(f"{path}: unexpected PLY header line {raw!r}")
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: PLY format {fmt!r} is not supported (ascii and binary_little_endian are)")
+    verts, faces = None, np.zeros((0, 3), dtype=np.int64)
+    pos = 0                                           # binary: byte offset into body
+    lines = body.decode("ascii").split("\n") if fmt == "ascii" else None
+    li = 0                                            # ascii: next line
+    for name, count, props in elements:
+        if name == "vertex":
+            if any(isinstance(t, tuple) for _, t in props):
+                raise ValueError(f"{path}: list property on vertices")
+            names = [n for n, _ in props]
+            if names[:3] != ["x", "y", "z"] or any(t not in ("float", "float32", "double", "float64") for _, t in props[:3]):
+                raise ValueError(f"{path}: vertices must start with float or double x, y, z (got {props[:3]})")
+            if fmt == "ascii":
+                rows = [ln.split() for ln in lines[li:li + count]]
+                li += count
+                verts = np.array([[float(r[0]), float(r[1]), float(r[2])] for r in rows], dtype=np.float64).reshape(-1, 3)
+            else:
+                dt = np.dtype([(n, "<" + _PLY_SCALARS[t]) for n, t in props])
+                rec = np.frombuffer(body, dtype=dt, count=count, offset=pos)
+                pos += dt.itemsize * count
+                verts = np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float64)
+        elif name == "face":
+            if len(props) != 1 or not isinstance(props[0][1], tuple) or props[0][0] not in ("vertex_indices",
+                                                                                             "vertex_index"):
+                raise ValueError(f"{path}: faces must carry exactly one list property vertex_indices (got {props})")
+            _, ct, it = props[0][1]
+            if ct not in _PLY_COUNT_TYPES or it not in _PLY_INDEX_TYPES:
+                raise ValueError(f"{path}: face list 'list {ct} {it}' is not supported (list uchar|uint8 "
+                                 "int|uint|int32|uint32)")
+            if fmt == "ascii":
+                polys = []
+                for ln in lines[li:li + count]:
+                    r = [int(x) for x in ln.split()]
+                    if len(r) < 1 or len(r) != r[0] + 1:
+                        raise ValueError(f"{path}: malformed face line {ln!r}")
+                    polys.append(r[1:])
+                li += count
+            else:
+                idt = np.dtype("<" + _PLY_SCALARS[it])
+                buf = memoryview(body)
+                tri = np.dtype([("n", "u1"), ("i", idt, 3)])
+                # fast path: every face a triangle
+                if count and pos + tri.itemsize * count <= len(body):
+                    rec = np.frombuffer(body, dtype=tri, count=count, offset=pos)
+                    if np.all(rec["n"] == 3):
+                        faces = rec["i"].astype(np.int64)
+                        pos += tri.itemsize * count
+                        continue
+                polys = []
+                for _ in range(count):
+                    k = buf[pos]
+                    pos += 1
+                    polys.append(np.frombuffer(body, dtype=idt, count=k, offset=pos).astype(np.int64).tolist())
+                    pos += k * idt.itemsize
+            faces = np.array(_fan(polys), dtype=np.int64).reshape(-1, 3)
+        else:
+            if count == 0:
+                continue
+            raise ValueError(f"{path}: PLY element {name!r} with data is not supported")
+    if verts is None:
+        raise ValueError(f"{path}: no vertex element")
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(verts)):
+        raise ValueError(f"{path}: a face indexes a vertex that does not exist")
+    return TriMesh(verts.astype(np.float32), faces)

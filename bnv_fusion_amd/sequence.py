@@ -204,3 +204,29 @@ def bench_pass(model, dev, n_frames, check=None, grid=512, check_every=200, keep
             "peak_device_memory_mb": torch.cuda.max_memory_allocated(dev) / 1e6,
             "parity_checks": [{"frame": k, "sdf_max_abs_err": e, "mask_decisions_equal": m, "live_fraction": l}
                               for k, e, m, l in checks]}
+
+
+def _box_faces(lo, hi):
+    """The 6 faces of an axis-aligned box as 12 triangles: (vertices [8, 3], faces [12, 3])."""
+    v = np.array([[(lo, hi)[i >> 2 & 1][0], (lo, hi)[i >> 1 & 1][1], (lo, hi)[i & 1][2]] for i in range(8)],
+                 dtype=np.float64)
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    f = [(q[0], q[1], q[2]) for q in quads] + [(q[0], q[2], q[3]) for q in quads]
+    return v, np.array(f, dtype=np.int64)
+
+
+def gt_mesh(scale=1.0):
+    """Ground-truth mesh of the room (``render_depth``'s scene at ``scale``): the room's six inner faces and the six
+    faces of every furniture box, float64 then cast to float32 -> mesh.TriMesh.  Many of these faces are never seen
+    by the sweep's camera (box bottoms, faces against a wall, the room outside the volume): a ground truth for
+    precision, not for recall."""
+    from .mesh import TriMesh
+    boxes = [([-scale * h for h in ROOM_HALF], [scale * h for h in ROOM_HALF])]
+    for c, h in FURNITURE:
+        boxes.append(([scale * (c[a] - h[a]) for a in range(3)], [scale * (c[a] + h[a]) for a in range(3)]))
+    vs, fs = [], []
+    for lo, hi in boxes:
+        v, f = _box_faces(lo, hi)
+        fs.append(f + 8 * len(vs))
+        vs.append(v)
+    return TriMesh(np.concatenate(vs).astype(np.float32), np.concatenate(fs))

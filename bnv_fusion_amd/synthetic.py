@@ -130,3 +130,54 @@ def frame(t, H=480, W=640, seed=0):
         intr[1] *= H / 480.0
     pts = depth_to_input_pts(depth_image(t, H, W, seed), intr, pose(t))
     return pts.astype(np.float32)[None]
+
+
+def _visible_in(R, u0, v0, W=640, H=480):
+    """Which camera-0 pixel coordinates (u0, v0) the camera of rotation R (the same optical centre) sees inside its
+    W x H image (pixel centres 0 .. W-1, 0 .. H-1)."""
+    fx, fy, cx, cy = INTRINSICS[0, 0], INTRINSICS[1, 1], INTRINSICS[0, 2], INTRINSICS[1, 2]
+    d = np.stack([(u0 - cx) / fx, (v0 - cy) / fy, np.ones_like(u0)], axis=0).reshape(3, -1)
+    dt = (R.T @ d).reshape((3,) + u0.shape)           # the world direction in camera t's frame (pose(0) has R = I)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ut = fx * dt[0] / dt[2] + cx
+        vt = fy * dt[1] / dt[2] + cy
+    return (dt[2] > 0) & (ut >= 0) & (ut <= W - 1) & (vt >= 0) & (vt <= H - 1)
+
+
+def gt_mesh(region="union", step_px=1.0):
+    """Ground-truth mesh of the static scene: ``scene_depth0`` triangulated over camera-0 pixel coordinates (a grid of
+    ``step_px``) and lifted to world coordinates with ``pose(0)``, float64 then cast to float32 -> mesh.TriMesh.
+
+    region "union": the part of the surface that ANY yaw of the pan (``yaw_deg`` over a period) sees -- the
+    ground truth for precision; "common": the part EVERY yaw sees -- for recall, so that borders only a few frames saw
+    do not count as missing.  A triangle is kept when its three vertices are in the region."""
+    from .mesh import TriMesh
+    if region not in ("union", "common"):
+        raise ValueError(f"region {region!r}: 'union' or 'common'")
+    step = float(step_px)
+    if not step > 0:
+        raise ValueError("step_px must be positive")
+    yaws = sorted({yaw_deg(t) for t in range(int(round(4 * YAW_AMPLITUDE_DEG / YAW_STEP_DEG)))})
+    # camera-0 pixel coordinates wide enough for the extreme yaws (+-4 degrees: ~37 px in u, a few in v)
+    u = np.arange(-80.0, 640.0 + 80.0 + step / 2, step)
+    v = np.arange(-40.0, 480.0 + 40.0 + step / 2, step)
+    v0, u0 = np.meshgrid(v, u, indexing="ij")
+    seen = None
+    for y in yaws:
+        a = math.radians(y)
+        R = np.array([[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
+        m = _visible_in(R, u0, v0)
+        seen = m if seen is None else (seen | m if region == "union" else seen & m)
+    fx, fy, cx, cy = INTRINSICS[0, 0], INTRINSICS[1, 1], INTRINSICS[0, 2], INTRINSICS[1, 2]
+    d = scene_depth0(u0, v0)
+    pc = np.stack([(u0 - cx) / fx * d, (v0 - cy) / fy * d, d], axis=-1).reshape(-1, 3)
+    T = pose(0)
+    pw = pc @ T[:3, :3].T + T[:3, 3]
+    rows, cols = u0.shape
+    idx = np.arange(rows * cols).reshape(rows, cols)
+    a, b, c, e = idx[:-1, :-1], idx[:-1, 1:], idx[1:, :-1], idx[1:, 1:]
+    tris = np.concatenate([np.stack([a, c, b], -1).reshape(-1, 3), np.stack([b, c, e], -1).reshape(-1, 3)])
+    s = seen.reshape(-1)
+    tris = tris[s[tris].all(axis=1)]
+    used, inv = np.unique(tris, return_inverse=True)
+    return TriMesh(pw[used].astype(np.float32), inv.reshape(-1, 3))

@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--pipelined", action="store_true",
                     help="with --decode-frames: two frames in flight (fuse_and_decode_async) instead of one "
                          "synchronous call per frame")
+    ap.add_argument("--eval-gt", help="score the final mesh against this ground-truth mesh (PLY) and print the "
+                                      "reference's summary line pred_gt/accuracy/gt_pred/recall/F1 at 2.5 cm")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     dev = "cuda:0"
@@ -117,6 +119,12 @@ def main():
         mesh = post_process_mesh(mesh, vertex_threshold=nm.voxel_size / 4)
         mesh.export(os.path.join(args.out, "final.ply"))
     nm.save(args.out, scan_id=args.scan_id.split("/")[-1])
+    if args.eval_gt and mesh is not None:
+        from bnv_fusion_amd import evaluate
+        from bnv_fusion_amd.mesh import load_ply
+        res = evaluate.evaluate_meshes(mesh, load_ply(args.eval_gt), generator=torch.Generator(device=dev).manual_seed(0),
+                                       device=dev)
+        print(evaluate.summary_line(res))
     print(f"{len(nm.frames)} frames, {nm.volume.num_rows()} voxels, "
           f"{0 if mesh is None else len(mesh.faces)} triangles -> {args.out}")
 

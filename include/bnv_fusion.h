@@ -787,6 +787,33 @@ int bnv_frame_ready(bnv_frame_pipe_t* pipe, int slot);
 int bnv_frame_pipe_timeline_enable(bnv_frame_pipe_t* pipe, int on);
 int bnv_frame_timeline(bnv_frame_pipe_t* pipe, int slot, float* ms_host /* [BNV_PIPE_TIMELINE_POINTS] */);
 
+/* ---- Mesh evaluation (bnv_fusion_amd/csrc/eval.hip; the reference's metric: src/scripts/evaluate_bnvf.py:9-31 and
+ * src/scripts/compute_chamfer.py:36-75 -- surface samples, nearest neighbours both ways, distances -> figures).
+ * Every result is bitwise reproducible from run to run. */
+
+/* Workspace bytes of bnv_mesh_sample_surface for a mesh of n_faces faces -> *bytes (host). */
+int bnv_mesh_sample_surface_workspace(int64_t n_faces, int64_t* bytes);
+/* trimesh.sample.sample_surface with caller-supplied uniforms: face areas 0.5 |e1 x e2| (fp32; a face whose area is
+ * not finite counts as zero), their inclusive prefix in float64, face = the first whose prefix is STRICTLY greater
+ * than u0 * total (a zero-area face is never chosen); (a, b) = (u1, u2), folded to (1 - a, 1 - b) when a + b > 1;
+ * point = (v0 + e1 a) + e2 b in fp32 with e1 = v1 - v0, e2 = v2 - v0.  vertices fp32 [n_vertices, 3], faces int32
+ * [n_faces, 3], uniforms fp32 [n, 3] in [0, 1) -> points_out fp32 [n, 3], face_ids_out int32 [n], normals_out (NULL:
+ * not written) fp32 [n, 3] = (e1 x e2) / |e1 x e2|.  BNV_ERR_INVALID_ARGUMENT also when the mesh has no area or a
+ * face indexes outside [0, n_vertices): the one check that reads device data, after the area scan -- so this entry
+ * waits for `stream` once and is not capturable into a graph. */
+int bnv_mesh_sample_surface(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                            const float* uniforms, int64_t n, void* workspace, int64_t ws_bytes, float* points_out,
+                            int32_t* face_ids_out, float* normals_out, bnv_stream_t stream);
+/* Workspace bytes of bnv_nn_query: a function of the two counts alone -> *bytes (host). */
+int bnv_nn_workspace_bytes(int64_t n_ref, int64_t n_query, int64_t* bytes);
+/* Exact nearest neighbour of every query point among the reference points (fp32 [n, 3] each), on a uniform grid
+ * built on the device: d2_out[i] is bitwise the minimum over the reference set of the fp32 expression
+ * (dx*dx + dy*dy) + dz*dz with dx = q.x - r.x, and idx_out[i] the LOWEST reference index attaining it.  A reference
+ * point with a NaN or Inf coordinate is never returned; a query with one (or a reference set without a finite point)
+ * gets d2 = +inf and index -1.  No allocation, synchronisation or host read: capturable into a graph. */
+int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_query, void* workspace,
+                 int64_t ws_bytes, float* d2_out, int32_t* idx_out, bnv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
