@@ -89,8 +89,10 @@ def load_weights(npz_path):
 
 def pointnet_encoder(sd, x):
     """PointNetEncoder.forward(x, global_feat=False), pointnet_utils.py:246-266.
-    x [B, 6, P] -> [B, 8, P].  BatchNorm1d in eval mode (run_e2e.py:234)."""
+    x [B, 6, P] -> [B, 8, P].  BatchNorm1d in eval mode (run_e2e.py:234).  Runs in the dtype of the weights (a float64
+    state dict gives the float64 reference of oracle/precision.py; fp32 inputs are cast, exactly)."""
     p = "pointnet_backbone."
+    x = x.to(sd[f"{p}conv1.weight"].dtype)
     for i in (1, 2, 3, 4):
         x = F.conv1d(x, sd[f"{p}conv{i}.weight"], sd[f"{p}conv{i}.bias"])
         x = F.batch_norm(x, sd[f"{p}bn{i}.running_mean"], sd[f"{p}bn{i}.running_var"],
@@ -112,7 +114,9 @@ def xyz_encoding(t):
 
 
 def geo_forward(sd, x, num_layers=4):
-    """ReplicateNeRFModel.geo_forward, modules.py:657-662.  [..., 17] -> [..., 1]."""
+    """ReplicateNeRFModel.geo_forward, modules.py:657-662.  [..., 17] -> [..., 1].  Runs in the dtype of the weights
+    (inputs are cast: a float64 state dict decodes fp32 positions and features in float64)."""
+    x = x.to(sd["nerf.geo_layer0.weight"].dtype)
     for i in range(num_layers):
         x = F.relu(F.linear(x, sd[f"nerf.geo_layer{i}.weight"], sd[f"nerf.geo_layer{i}.bias"]))
     return F.linear(x, sd["nerf.fc_alpha.weight"], sd["nerf.fc_alpha.bias"])
@@ -206,7 +210,9 @@ class OracleSparseVolume:
     """Semantics of sparse_volume.py:484-695 with the Open3D hash map replaced by a
     Python dict (key tuple -> buffer row, insertion order = buffer order)."""
 
-    def __init__(self, n_feats, voxel_size, dimensions, min_pts_in_grid):
+    def __init__(self, n_feats, voxel_size, dimensions, min_pts_in_grid, dtype=torch.float32):
+        """``dtype``: of the stored features / weights (float64: the precision reference; the voxel geometry --
+        min_coords, local coordinates, trilinear weights -- stays float32 as in the kernels)."""
         min_coords, max_coords, n_xyz = get_world_range(dimensions, voxel_size)
         self.dimensions = dimensions
         self.voxel_size = voxel_size
@@ -215,6 +221,7 @@ class OracleSparseVolume:
         self.n_xyz = torch.from_numpy(np.asarray(n_xyz)).long()  # sparse_volume.py:497
         self.n_feats = n_feats
         self.min_pts_in_grid = min_pts_in_grid
+        self.dtype = dtype
         self._map = {}
         self._keys, self._feats, self._w, self._hits = [], [], [], []
         self.features = self.weights = self.num_hits = self.active_coordinates = None
@@ -236,9 +243,9 @@ class OracleSparseVolume:
         if n == 0:
             return None, None, None
         rows = self._rows(keys, self._map)
-        f = torch.zeros((n, self.n_feats))
-        w = torch.zeros((n, 1))
-        h = torch.zeros((n, 1))
+        f = torch.zeros((n, self.n_feats), dtype=self.dtype)
+        w = torch.zeros((n, 1), dtype=self.dtype)
+        h = torch.zeros((n, 1), dtype=self.dtype)
         for i, r in enumerate(rows):
             if r >= 0:
                 f[i], w[i], h[i] = self._feats[r], self._w[r], self._hits[r]
@@ -267,9 +274,9 @@ class OracleSparseVolume:
     def to_tensor(self):
         """sparse_volume.py:525-559: snapshot of the active entries + key -> row index."""
         self.active_coordinates = torch.tensor(self._keys, dtype=torch.int64).reshape(-1, 3)
-        self.features = torch.stack(self._feats) if self._feats else torch.zeros((0, self.n_feats))
-        self.weights = torch.stack(self._w).reshape(-1, 1) if self._w else torch.zeros((0, 1))
-        self.num_hits = torch.stack(self._hits).reshape(-1, 1) if self._hits else torch.zeros((0, 1))
+        self.features = torch.stack(self._feats) if self._feats else torch.zeros((0, self.n_feats), dtype=self.dtype)
+        self.weights = torch.stack(self._w).reshape(-1, 1) if self._w else torch.zeros((0, 1), dtype=self.dtype)
+        self.num_hits = torch.stack(self._hits).reshape(-1, 1) if self._hits else torch.zeros((0, 1), dtype=self.dtype)
         self._tensor_map = {k: i for i, k in enumerate(self._keys)}
         return self.active_coordinates, self.features, self.weights, self.num_hits
 
@@ -279,9 +286,9 @@ class OracleSparseVolume:
         n = int(np.prod(shapes[:-1]))
         rows = torch.tensor(self._rows(keys, self._tensor_map), dtype=torch.int64)
         found = rows >= 0
-        f = torch.zeros((n, self.n_feats))
-        w = torch.zeros((n, 1))
-        h = torch.zeros((n, 1))
+        f = torch.zeros((n, self.n_feats), dtype=self.features.dtype)
+        w = torch.zeros((n, 1), dtype=self.weights.dtype)
+        h = torch.zeros((n, 1), dtype=self.num_hits.dtype)
         f[found] = self.features[rows[found]]
         w[found] = self.weights[rows[found]]
         h[found] = self.num_hits[rows[found]]
@@ -365,15 +372,17 @@ def decode_feature_grid_w_pts(sd, voxel_coords, feat_grid, pts_weight, voxel_siz
     """LitFusionPointNet.decode_feature_grid_w_pts, local_point_fusion.py:265-367 (+ decode_implicit :372-379,
     LocalNeRFModel.forward(test=True) modules.py:941-960).  voxel_coords [1, Q, 3] -> sdf [1, Q], neighbor_feats.
     Defaults = the yaml configuration (global_coords=False, interpolate_decode=True, :281-329); the other two
-    branches: nearest voxel (:288-292, 331-343) and global coordinates (:345-367, the signature default)."""
+    branches: nearest voxel (:288-292, 331-343) and global coordinates (:345-367, the signature default).
+    Grids of another dtype than the float32 coordinates (float64 features: the precision reference) are sampled
+    with the sampling grid cast to theirs."""
     h, w, d = feat_grid.shape[-3:]
     res = torch.tensor([h, w, d])
     if global_coords:
         g = voxel_coords / (res - 1)
         g = (g * 2 - 1)[..., [2, 1, 0]].unsqueeze(0).unsqueeze(0)           # [1, 1, 1, Q, 3]
-        nf = F.grid_sample(feat_grid, g, mode="bilinear", padding_mode="zeros", align_corners=True)
+        nf = F.grid_sample(feat_grid, g.to(feat_grid.dtype), mode="bilinear", padding_mode="zeros", align_corners=True)
         nf = nf.squeeze(2).squeeze(2).permute(0, 2, 1)                     # [1, Q, F]
-        pw = F.grid_sample(pts_weight, g, mode="nearest", padding_mode="zeros", align_corners=True)
+        pw = F.grid_sample(pts_weight, g.to(pts_weight.dtype), mode="nearest", padding_mode="zeros", align_corners=True)
         pw = pw.squeeze(2).squeeze(2).permute(0, 2, 1)[..., 0]             # [1, Q]
         pts = voxel_coords / (res - 1)                                     # decode_implicit(normalize=False)
         sdf = geo_forward(sd, torch.cat([xyz_encoding(pts[..., :3]), nf], dim=-1))[..., 0]
@@ -383,8 +392,8 @@ def decode_feature_grid_w_pts(sd, voxel_coords, feat_grid, pts_weight, voxel_siz
         nc = torch.round(voxel_coords)
         g = nc / (res - 1)
         g = (g * 2 - 1)[..., [2, 1, 0]].unsqueeze(0).unsqueeze(0)
-        nf = F.grid_sample(feat_grid, g, mode="nearest", padding_mode="zeros", align_corners=True)
-        pw = F.grid_sample(pts_weight, g, mode="nearest", padding_mode="zeros", align_corners=True)
+        nf = F.grid_sample(feat_grid, g.to(feat_grid.dtype), mode="nearest", padding_mode="zeros", align_corners=True)
+        pw = F.grid_sample(pts_weight, g.to(pts_weight.dtype), mode="nearest", padding_mode="zeros", align_corners=True)
         pw = pw * (pw >= min_pts_in_grid)
         nf = nf.squeeze(2).squeeze(2).permute(0, 2, 1)                     # [1, Q, F]
         pw = pw.squeeze(2).squeeze(2).permute(0, 2, 1)[..., 0]             # [1, Q]
@@ -397,8 +406,8 @@ def decode_feature_grid_w_pts(sd, voxel_coords, feat_grid, pts_weight, voxel_siz
     neighbor_coords = get_neighbors(voxel_coords.unsqueeze(1), as_int=True).squeeze(2)  # [1, 8, Q, 3] i32
     g = neighbor_coords / (res - 1)
     g = (g * 2 - 1)[..., [2, 1, 0]].unsqueeze(0)
-    nf = F.grid_sample(feat_grid, g, mode="nearest", padding_mode="zeros", align_corners=True)
-    pw = F.grid_sample(pts_weight, g, mode="nearest", padding_mode="zeros", align_corners=True)
+    nf = F.grid_sample(feat_grid, g.to(feat_grid.dtype), mode="nearest", padding_mode="zeros", align_corners=True)
+    pw = F.grid_sample(pts_weight, g.to(pts_weight.dtype), mode="nearest", padding_mode="zeros", align_corners=True)
     pw = pw * (pw >= min_pts_in_grid)
     nf = nf.squeeze(2).permute(0, 2, 3, 1)          # [1, 8, Q, F]
     pw = pw.squeeze(2).permute(0, 2, 3, 1)[..., 0]  # [1, 8, Q]
