@@ -2,9 +2,10 @@
 //
 // Reference: src/utils/render_utils.py -- get_camera_params / lift (:411-458), stratified_sampling (:77-94),
 // hierarchical_sampling (:191-233), render_with_rays (:461-505), compute_sdf_loss (:508-549).  The torch
-// restatement of the same functions (bnv_fusion_amd/optimize.py, pinned to the reference's golden vectors)
-// costs ~180 tiny launches per 1000-ray split and leaves the optimiser step bound by the HOST's launch rate
-// (7.7 ms per step against 2 ms of kernels).  Here one split is
+// formulation of the same functions (oracle/bnv_oracle.py, pinned to the reference's golden vectors) costs
+// ~180 tiny launches per 1000-ray split and leaves the optimiser step bound by the HOST's launch rate (7.7 ms
+// per step against 2 ms of kernels); bnv_fusion_amd/optimize.py runs every ray path on these kernels.  Here
+// one split is
 //   k_ray_samples   one thread per drawn sample: ray through the pixel, fine + coarse stratified samples, merged
 //                   by distance (rank counting), world points; per sample the L1 target (signed distance to the nearest valid
 //                   neighbouring surface point, truncated) and its weight (valid x ray mask);

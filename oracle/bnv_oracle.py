@@ -613,7 +613,7 @@ def stratified_samples(n_samples, lengths, rand):
     """stratified_sampling (render_utils.py:77-94): one uniform draw inside each of n_samples strata of
     [0, length]; ``lengths`` [b, n, 1]; ``rand(b, n, s)`` supplies the uniforms -> [b, n, s, 1]."""
     b, n = lengths.shape[:2]
-    edges = torch.linspace(0, 1, steps=n_samples).unsqueeze(0).repeat(b, n, 1) * lengths
+    edges = torch.linspace(0, 1, steps=n_samples, device=lengths.device).unsqueeze(0).repeat(b, n, 1) * lengths
     mids = 0.5 * (edges[..., 1:] + edges[..., :-1])
     upper = torch.cat([mids, edges[..., -1:]], dim=-1)
     lower = torch.cat([edges[..., :1], mids], dim=-1)

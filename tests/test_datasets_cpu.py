@@ -71,3 +71,31 @@ def test_random_subset_is_a_sample_without_replacement_in_random_order():
     z = random_subset(40, 8, "cpu", g)                    # k > n / 8: the permutation itself
     assert z.unique().numel() == 8 and int(z.max()) < 40
 
+
+@pytest.mark.parametrize("sampling_size", [100, 4000])
+@pytest.mark.parametrize("seed", [None, 5])
+def test_sample_key_frame_from_depth_equals_from_key_frame_points(seed, sampling_size):
+    """optimize.sample_key_frame on a depth map is sample_key_frame on the frame's key_frame_points (what
+    NeuralMap.optimize keeps per key frame): the same rays, bit for bit, with a CPU generator (the reference's randperm)
+    and without one (random_subset)."""
+    import torch
+    from bnv_fusion_amd import optimize, synthetic
+    H, W = 60, 80
+    depth = torch.from_numpy(synthetic.depth_u16(3, H, W)).float() / 1000.0
+    depth[:3] = 0.0                                       # invalid pixels: no depth, and beyond ray_max_dist
+    depth[-2:] = 5.0
+    K, T = synthetic.intrinsics(H, W), synthetic.pose(3)
+    outs = []
+    for points in (None, optimize.key_frame_points(depth, K, T, 3)):
+        torch.manual_seed(11)
+        gen = None if seed is None else torch.Generator().manual_seed(seed)
+        args = (depth, K, T) if points is None else (None, None, None)
+        outs.append(optimize.sample_key_frame(*args, sampling_size, 3, gen, points=points))
+    a, b = outs
+    assert a.keys() == b.keys() and a["uv"].shape == (1, sampling_size, 2)
+    for k in a:
+        if isinstance(a[k], torch.Tensor):
+            assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), k
+        else:
+            assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+

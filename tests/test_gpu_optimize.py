@@ -239,9 +239,11 @@ def test_neural_map_optimize_runs_with_tcnn_checkpoint():
 
 
 def test_fused_ray_split_equals_the_torch_formulation(bnv, model):
-    """csrc/rays.hip (sampling + loss, fused) + decode forward/backward against optimize.calculate_loss + autograd
-    (itself pinned to the reference's golden vectors): same points, same loss, same gradient, same count_optim."""
+    """csrc/rays.hip (sampling + loss, fused) + decode forward/backward against the oracle's calculate_loss + autograd
+    (itself pinned to the reference's golden vectors): same points, same loss, same gradient, same count_optim; and
+    optimize.calculate_loss (the same kernels behind autograd) against both."""
     from bnv_fusion_amd import optimize
+    from oracle import bnv_oracle as orc
     dec = np.load(os.path.join(GOLDEN, "decode_64.npz"))
     op = np.load(os.path.join(GOLDEN, "optimize_64.npz"))
     rays = {k[5:]: torch.from_numpy(op[k]).to(DEV) for k in op.files if k.startswith("rays_")}
@@ -257,15 +259,26 @@ def test_fused_ray_split_equals_the_torch_formulation(bnv, model):
     assert abs(float(loss) - float(op["depth_bce_loss"])) <= 1e-4 * float(op["depth_bce_loss"])
     ref = op["grad_features"]
     assert np.abs(grad.cpu().numpy() - ref).max() <= 1e-3 * np.abs(ref).max()
-    # and against the torch path of this package on a fresh volume, same generator state
+    # against the oracle's torch formulation on a fresh volume, same generator state
     vol2 = _insertion_order_volume(bnv)
     vol2.features = torch.nn.Parameter(vol2.features)
-    l2 = optimize.calculate_loss(vol2, rays, model.nerf, *args, sdf_delta=delta,
-                                 generator=torch.Generator().manual_seed(int(op["seed"])))["depth_bce_loss"]
+    g = torch.Generator().manual_seed(int(op["seed"]))
+    l2 = orc.calculate_loss(vol2, rays, model.nerf, *args, sdf_delta=delta,
+                            rand=lambda *s: torch.rand(*s, generator=g).to(DEV))[0]["depth_bce_loss"]
     l2.backward()
     assert abs(float(loss) - float(l2.detach())) <= 1e-5 * float(l2.detach())
     assert (grad - vol2.features.grad).abs().max() <= 1e-4 * vol2.features.grad.abs().max()
     assert torch.equal(vol.weights, vol2.weights)
+    # optimize.calculate_loss at the same bars
+    vol3 = _insertion_order_volume(bnv)
+    vol3.features = torch.nn.Parameter(vol3.features)
+    l3 = optimize.calculate_loss(vol3, rays, model.nerf, *args, sdf_delta=delta,
+                                 generator=torch.Generator().manual_seed(int(op["seed"])))["depth_bce_loss"]
+    assert l3.dim() == 0
+    l3.backward()
+    assert abs(float(loss) - float(l3.detach())) <= 1e-5 * float(l3.detach())
+    assert (grad - vol3.features.grad).abs().max() <= 1e-4 * vol3.features.grad.abs().max()
+    assert torch.equal(vol.weights, vol3.weights)
 
 
 def _split_rays(rays, lo, hi):
