@@ -32,6 +32,7 @@ SYMBOLS = [
     "bnv_frame_upsert", "bnv_frame_bound", "bnv_frame_finish", "bnv_frame_result", "bnv_frame_ready", "bnv_frame_pipe_timeline_enable", "bnv_frame_timeline",
     "bnv_frame_side_depth", "bnv_frame_cancel", "bnv_frame_pipe_forget_workspaces", "bnv_shard_state_configure",
     "bnv_mesh_sample_surface_workspace", "bnv_mesh_sample_surface", "bnv_nn_workspace_bytes", "bnv_nn_query",
+    "bnv_tsdf_mesh_workspace_bytes", "bnv_tsdf_mesh_count", "bnv_tsdf_mesh_emit",
     
 ]
 
@@ -259,6 +260,10 @@ def load():
         "bnv_mesh_sample_surface": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
         "bnv_nn_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
         "bnv_nn_query": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+        "bnv_tsdf_mesh_workspace_bytes": (C.c_int, [C.POINTER(i32), C.POINTER(i64)]),
+        "bnv_tsdf_mesh_count": (C.c_int, [vp, vp, C.POINTER(i32), C.c_float, C.c_int, vp, vp, i64, vp, vp]),
+        "bnv_tsdf_mesh_emit": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float,
+                                         C.c_int, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

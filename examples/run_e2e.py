@@ -3,6 +3,7 @@ sequence directory, periodic global optimisation, mesh extraction, final artefac
 
     python examples/run_e2e.py --data-dir DATA --scan-id scene3d/lounge --out OUT          # the reference's layout
     python examples/run_e2e.py --synthetic 24 --out /tmp/bnv_demo                          # writes a synthetic scene first
+    python examples/run_e2e.py ... --tsdf-mesh --eval-gt GT.ply                            # + the TSDF baseline, both scored
     python examples/run_e2e.py --sweep 600 --grid 512 --decode-frames --pipelined --no-optimize --out /tmp/sweep
                                                     # a moving-camera room sweep (bnv_fusion_amd/sequence.py), per-frame
                                                     # SDF decode of the touched voxels, two frames in flight
@@ -23,7 +24,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import bnv_fusion_amd as bnv                                   # noqa: E402
 bnv.configure_runtime()                                       # optional: the package's hardware queue count
 from bnv_fusion_amd import datasets, synthetic                # noqa: E402
-from bnv_fusion_amd.mesh import post_process_mesh             # noqa: E402
+from bnv_fusion_amd.mesh import post_process_mesh, to_host    # noqa: E402
 
 
 def main():
@@ -50,6 +51,9 @@ def main():
                          "synchronous call per frame")
     ap.add_argument("--eval-gt", help="score the final mesh against this ground-truth mesh (PLY) and print the "
                                       "reference's summary line pred_gt/accuracy/gt_pred/recall/F1 at 2.5 cm")
+    ap.add_argument("--tsdf-mesh", action="store_true",
+                    help="also mesh the 2.5 cm TSDF side volume (observed cells only) into tsdf.ply; with --eval-gt "
+                         "its summary line follows the neural mesh's: the TSDF baseline of the same run")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     dev = "cuda:0"
@@ -119,12 +123,22 @@ def main():
         mesh = post_process_mesh(mesh, vertex_threshold=nm.voxel_size / 4)
         mesh.export(os.path.join(args.out, "final.ply"))
     nm.save(args.out, scan_id=args.scan_id.split("/")[-1])
-    if args.eval_gt and mesh is not None:
+    tsdf_mesh = None
+    if args.tsdf_mesh:                                                   # fusion.py:323-341 + meshwrite (:366-399)
+        from bnv_fusion_amd.tsdf import meshwrite
+        tsdf_mesh = nm.tsdf_vol.mesh_tensors(observed_only=True)
+        meshwrite(os.path.join(args.out, "tsdf.ply"), *to_host(*tsdf_mesh))
+    if args.eval_gt and (mesh is not None or tsdf_mesh is not None):
         from bnv_fusion_amd import evaluate
         from bnv_fusion_amd.mesh import load_ply
-        res = evaluate.evaluate_meshes(mesh, load_ply(args.eval_gt), generator=torch.Generator(device=dev).manual_seed(0),
-                                       device=dev)
-        print(evaluate.summary_line(res))
+        gt = load_ply(args.eval_gt)
+        if mesh is not None:
+            res = evaluate.evaluate_meshes(mesh, gt, generator=torch.Generator(device=dev).manual_seed(0), device=dev)
+            print(evaluate.summary_line(res))
+        if tsdf_mesh is not None and len(tsdf_mesh[1]):
+            res = evaluate.evaluate_meshes(tsdf_mesh[:2], gt, generator=torch.Generator(device=dev).manual_seed(0),
+                                           device=dev)
+            print(evaluate.summary_line(res), "(TSDF baseline)")
     print(f"{len(nm.frames)} frames, {nm.volume.num_rows()} voxels, "
           f"{0 if mesh is None else len(mesh.faces)} triangles -> {args.out}")
 

@@ -565,6 +565,35 @@ int bnv_mc_emit_indexed(const float* sdf, const int64_t* origins, int64_t n, con
                         const int64_t* vert_offsets, const int64_t* tri_offsets, float* vertices, int64_t* faces,
                         bnv_stream_t stream);
 
+/* ---- dense marching cubes over the TSDF side volume (TSDFVolume.get_mesh / get_point_cloud, third_parties/fusion.py:
+ * 302-341; the reference runs skimage's marching_cubes_lewiner on a host copy).  tsdf, weight, color: the [X, Y, Z] f32
+ * volumes of bnv_tsdf_integrate, read in place; dim = {X, Y, Z}.  The output is a WELDED mesh: one vertex per grid
+ * edge whose end values straddle `level` (case bit c of the cell based at (i, j, k) is set when tsdf < level at corner
+ * c = 4 dx + 2 dy + dz; tri_table and winding as bnv_mc_*: face normals point toward increasing TSDF, and inside
+ * ambiguous cells the triangulation is that table's, not Lewiner's -- the vertex set is the same for both).  Vertex on
+ * the edge a -> a + e_axis: t = (level - va) / (vb - va), world = fl32(fl32((a + t e_axis) * voxel_size) + origin);
+ * normal = the np.gradient of the volume at both ends interpolated with t and normalised (0 for a zero gradient);
+ * colour = color[rint(a + t e_axis)] unfolded to r, g, b uint8 as fusion.py:331-337.  Vertices are ordered by the
+ * linear index of the owning (lower) grid point, then axis x, y, z; faces by the linear index of the cell's base, then
+ * table order.  observed_only != 0: a cell emits only when its 8 corners have weight > 0 and a vertex exists only when
+ * an emitting cell uses it (weight must then be non-NULL).  A volume with a dimension below 2 has no cell: V = T = 0.
+ * Workspace: bnv_tsdf_mesh_workspace_bytes (< 1 B per grid point).  bnv_tsdf_mesh_count fills it and writes the
+ * totals {V, T} to the device int64[2] `totals`; the caller reads them back to size the outputs and calls
+ * bnv_tsdf_mesh_emit with the same volume, dim, level, observed_only and workspace: vertices [V, 3] f32 (required),
+ * faces [T, 3] i64, normals [V, 3] f32, colors [V, 3] u8 -- each of the last three may be NULL (a point cloud skips
+ * the faces and normals); color may be NULL (colours are then 0).  n_vertices / n_faces: the capacities of the
+ * outputs (rows); nothing is written beyond them.  Neither entry allocates or synchronises; bad arguments return
+ * BNV_ERR_INVALID_ARGUMENT before any HIP call. */
+int bnv_tsdf_mesh_workspace_bytes(const int32_t dim[3], int64_t* bytes);
+int bnv_tsdf_mesh_count(const float* tsdf, const float* weight, const int32_t dim[3], float level, int observed_only,
+                        const int8_t* tri_table, void* workspace, int64_t ws_bytes, int64_t* totals,
+                        bnv_stream_t stream);
+int bnv_tsdf_mesh_emit(const float* tsdf, const float* weight, const float* color, const int32_t dim[3],
+                       const float origin[3], float voxel_size, float level, int observed_only,
+                       const int8_t* tri_table, const void* workspace, int64_t ws_bytes, int64_t n_vertices,
+                       int64_t n_faces, float* vertices, int64_t* faces, float* normals, uint8_t* colors,
+                       bnv_stream_t stream);
+
 size_t bnv_decode_lattice_workspace_bytes(int64_t n_voxels, int64_t row_capacity);
 /* Byte offset, inside that workspace, of two int32 device counters: [0] rows listed by
  * bnv_lattice_neighbors(build_list), [1] table entries (= MLP evaluations) listed by bnv_lattice_mark /
