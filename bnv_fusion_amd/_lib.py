@@ -33,6 +33,7 @@ SYMBOLS = [
     "bnv_frame_side_depth", "bnv_frame_cancel", "bnv_frame_pipe_forget_workspaces", "bnv_shard_state_configure",
     "bnv_mesh_sample_surface_workspace", "bnv_mesh_sample_surface", "bnv_nn_workspace_bytes", "bnv_nn_query",
     "bnv_tsdf_mesh_workspace_bytes", "bnv_tsdf_mesh_count", "bnv_tsdf_mesh_emit",
+    "bnv_render_workspace_bytes", "bnv_render_depth", "bnv_tsdf_render_depth",
     
 ]
 
@@ -264,6 +265,13 @@ def load():
         "bnv_tsdf_mesh_count": (C.c_int, [vp, vp, C.POINTER(i32), C.c_float, C.c_int, vp, vp, i64, vp, vp]),
         "bnv_tsdf_mesh_emit": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float,
                                          C.c_int, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
+        "bnv_render_workspace_bytes": (sz, [i64, i32]),
+        "bnv_render_depth": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, C.POINTER(SdfDelta),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, C.c_float, C.c_float,
+                                       C.c_float, i32, vp, sz, vp, vp, C.POINTER(i64), vp]),
+        "bnv_tsdf_render_depth": (C.c_int, [vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float,
+                                            C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, C.c_float, C.c_float,
+                                            C.c_float, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

@@ -189,3 +189,22 @@ def evaluate_meshes(pred, gt, n_samples=100000, threshold=0.025, vertices_only=F
 def summary_line(res):
     """The reference's one-line summary: pred_gt / accuracy / gt_pred / recall / F1."""
     return "{:.3f}/{:.4f}/{:.3f}/{:.4f}/{:.4f}".format(*[res[k] for k in KEYS])
+
+
+def depth_errors(pred, gt, threshold=0.025):
+    """Rendered depth ``pred`` against observed depth ``gt`` (same shape, metres, 0 = none; any device) -> {"coverage":
+    hits among pixels with gt > 0, "median" / "mean" absolute error and "rmse" over pixels where both are > 0,
+    "within": the fraction of those with |error| <= threshold}.  The error figures are nan when no pixel has both."""
+    p = torch.as_tensor(pred).double()
+    g = torch.as_tensor(gt).to(p.device).double()
+    if p.shape != g.shape:
+        raise ValueError(f"depth_errors: shapes differ ({tuple(p.shape)} vs {tuple(g.shape)})")
+    obs = g > 0
+    both = obs & (p > 0)
+    e = (p - g)[both].abs()
+    n_obs = int(obs.sum())
+    res = {"coverage": (int(both.sum()) / n_obs) if n_obs else float("nan")}
+    if e.numel() == 0:
+        return dict(res, median=float("nan"), mean=float("nan"), rmse=float("nan"), within=float("nan"))
+    return dict(res, median=float(e.median()), mean=float(e.mean()), rmse=float(torch.sqrt((e * e).mean())),
+                within=float((e <= threshold).double().mean()))

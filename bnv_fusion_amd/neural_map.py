@@ -341,6 +341,23 @@ class NeuralMap:
         out = self.volume.meshlize(self.pointnet.nerf, delta, path)
         return None if out is None else out[1]
 
+    def render(self, T_wc, intr_mat, H, W, normals=True):
+        """Depth (and normal) image of the map from pose ``T_wc`` (camera-to-world) with pinhole ``intr_mat``: the
+        field extract_mesh meshes (same rows, TSDF prior / sdf_delta), up to ``self.max_depth``.  Waits for the frames
+        still in the pipeline.  -> (depth [H, W] f32 metres, 0 = no hit; normals [H, W, 3] or None)."""
+        self._drain_pipe()
+        delta = self.prepare_tsdf_volume() if self.tsdf_vol is not None else self.sdf_delta
+        return self.volume.render_depth(T_wc, intr_mat, H, W, self.pointnet.nerf, delta, max_depth=self.max_depth,
+                                        normals=normals)
+
+    def render_tsdf(self, T_wc, intr_mat, H, W, normals=True):
+        """NeuralMap.render of the TSDF side volume (TSDFVolume.render_depth, up to ``self.max_depth``), after the
+        frames still in the pipeline -- whose side streams update that volume -- have been collected."""
+        if self.tsdf_vol is None:
+            raise _lib_error("render_tsdf: this map has no TSDF side volume (NeuralMap(..., tsdf=True))")
+        self._drain_pipe()
+        return self.tsdf_vol.render_depth(T_wc, intr_mat, H, W, max_depth=self.max_depth, normals=normals)
+
     def save(self, working_dir, scan_id="scan"):
         """run_e2e.py:188-194: the TSDF volume as <scan_id>.npy (metres) and the feature volume as
         final_sparse_volume.pth (sparse_volume.py:835-860)."""

@@ -658,6 +658,40 @@ class SparseVolume:
         sdf = self.decode_lattice(self.active_coordinates, nerf, sdf_delta, query_tensor=True)
         return active_pts, sdf.reshape(-1, 3, 3, 3)
 
+    def render_depth(self, T_wc, K, H, W, nerf, sdf_delta=None, near=0.1, max_depth=3.0, step=0.5, normals=True,
+                     query_tensor=False, k=8):
+        """Depth (and normal) image of the volume from camera pose ``T_wc`` (camera-to-world 4x4, +z forward, y down)
+        with pinhole ``K`` -> (depth [H, W] f32 z-depth in metres, 0 = no hit; normals [H, W, 3] world-frame unit
+        vectors or None).  The field is exactly ``decode_pts`` (same rows, MLP mode and ``sdf_delta``); samples lie
+        every ``step`` voxels along the ray (include/bnv_fusion.h, "Rendering").  ``query_tensor``: read the
+        ``to_tensor()`` snapshot like ``decode_pts`` does by default, else the live rows.  ``k``: samples a ray
+        appends per round.  Statistics of the call: ``last_render_stats``."""
+        from .render import camera_args
+        if self.shard[1] > 1:
+            raise NotImplementedError("rendering a sharded volume (shard_world > 1) is not supported")
+        t, km = camera_args(T_wc, K, H, W, near, max_depth, step)
+        H, W = int(H), int(W)
+        n = H * W
+        need = int(self._lib.bnv_render_workspace_bytes(n, int(k)))
+        if need == 0:
+            raise _lib.BnvError(f"render: {H} x {W} rays with k = {k} is out of range")
+        ws = getattr(self, "_render_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._render_ws = torch.empty(need, dtype=torch.uint8, device=self._dev)
+        grid = self._grid_for(nerf)
+        f, w, lim = self._values(query_tensor)
+        d, keep = self._delta(sdf_delta)
+        depth = torch.empty((H, W), dtype=torch.float32, device=self._dev)
+        nrm = torch.empty((H, W, 3), dtype=torch.float32, device=self._dev) if normals else None
+        stats = (C.c_int64 * 4)()
+        _lib.check(self._lib.bnv_render_depth(
+            C.byref(self._struct()), C.byref(grid), _lib.ptr(f), _lib.ptr(w), int(lim), _lib.ptr(nerf.sdf_pack),
+            C.byref(d), t, km, H, W, float(near), float(max_depth), float(step), int(k), _lib.ptr(ws), ws.numel(),
+            _lib.ptr(depth), _lib.ptr(nrm), stats, _lib.stream_ptr()), "bnv_render_depth")
+        self.last_render_stats = {"rounds": int(stats[0]), "samples": int(stats[1]), "live_samples": int(stats[2]),
+                                  "hits": int(stats[3])}
+        return depth, nrm
+
     def save(self, path):
         self.print_statistic()
         n = self._snapshot_rows

@@ -96,6 +96,25 @@ class TSDFVolume:
                 (C.c_float * (9 * k))(*intr.tolist()), (C.c_float * (16 * k))(*pose.tolist()), float(obs_weight),
                 float(max_depth or 0.0), _lib.stream_ptr()), "bnv_tsdf_integrate_batch_u16")
 
+    def render_depth(self, T_wc, K, H, W, near=0.1, max_depth=3.0, step=0.5, normals=True):
+        """Depth (and normal) image of the TSDF volume from camera pose ``T_wc`` with pinhole ``K``: the same rays,
+        schedule (``step`` in TSDF voxels) and hit rule as SparseVolume.render_depth, on the trilinear TSDF of the
+        observed voxels (weight > 0) -> (depth [H, W] f32, normals [H, W, 3] f32 or None).  Runs on the current
+        stream: frames a NeuralMap still has in its pipeline update this volume on side streams, so render a map's
+        TSDF volume through NeuralMap.render_tsdf, which waits for them."""
+        from .render import camera_args
+        t, km = camera_args(T_wc, K, H, W, near, max_depth, step)
+        H, W = int(H), int(W)
+        depth = torch.empty((H, W), dtype=torch.float32, device=self._dev)
+        nrm = torch.empty((H, W, 3), dtype=torch.float32, device=self._dev) if normals else None
+        dim = (C.c_int32 * 3)(*[int(v) for v in self._vol_dim])
+        org = (C.c_float * 3)(*self._vol_origin.tolist())
+        _lib.check(self._lib.bnv_tsdf_render_depth(
+            _lib.ptr(self.tsdf), _lib.ptr(self.weight), dim, org, np.float32(self._voxel_size), t, km, H, W,
+            float(near), float(max_depth), float(step), _lib.ptr(depth), _lib.ptr(nrm), _lib.stream_ptr()),
+            "bnv_tsdf_render_depth")
+        return depth, nrm
+
     def get_volume(self):
         return self.tsdf.cpu().numpy(), self.color.cpu().numpy()
 

@@ -54,6 +54,9 @@ def main():
     ap.add_argument("--tsdf-mesh", action="store_true",
                     help="also mesh the 2.5 cm TSDF side volume (observed cells only) into tsdf.ply; with --eval-gt "
                          "its summary line follows the neural mesh's: the TSDF baseline of the same run")
+    ap.add_argument("--render", metavar="DIR",
+                    help="after the run, render the map at every key frame's pose into DIR (16-bit PNGs, millimetres) "
+                         "and print the mean depth errors against the observed frames")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     dev = "cuda:0"
@@ -139,8 +142,36 @@ def main():
             res = evaluate.evaluate_meshes(tsdf_mesh[:2], gt, generator=torch.Generator(device=dev).manual_seed(0),
                                            device=dev)
             print(evaluate.summary_line(res), "(TSDF baseline)")
+    if args.render:
+        render_key_frames(nm, args.render, max_depth)
     print(f"{len(nm.frames)} frames, {nm.volume.num_rows()} voxels, "
           f"{0 if mesh is None else len(mesh.faces)} triangles -> {args.out}")
+
+
+def render_key_frames(nm, out_dir, max_depth):
+    """Renders the map at every key frame's pose, writes <frame_id>.png (uint16 mm) and prints the mean depth_errors
+    against the observed depth (cut at max_depth like the fused frames)."""
+    from bnv_fusion_amd import evaluate
+    os.makedirs(out_dir, exist_ok=True)
+    sums, counts = {}, {}
+    for k, fr in enumerate(nm.frames):
+        obs = fr["depth"]
+        obs = obs.to(torch.float32) / 1000.0 if obs.dtype in (torch.uint16, torch.int16) else obs.to(torch.float32)
+        obs = torch.where(obs < max_depth, obs, torch.zeros_like(obs))
+        H, W = int(obs.shape[-2]), int(obs.shape[-1])
+        depth, _ = nm.render(fr["T_wc"], fr["intr_mat"], H, W, normals=False)
+        mm = torch.round(depth.double() * 1000.0).clamp(0, 65535).to(torch.int32).cpu().numpy().astype(np.uint16)
+        datasets.write_png16(os.path.join(out_dir, f"{fr.get('frame_id', k)}.png"), mm)
+        e = evaluate.depth_errors(depth, obs)
+        for key, v in e.items():
+            if not np.isnan(v):
+                sums[key] = sums.get(key, 0.0) + v
+                counts[key] = counts.get(key, 0) + 1
+    if counts:
+        print(f"rendered depth vs observed (mean over {counts.get('coverage', 0)} key frames): "
+              + ", ".join(f"{key} {sums[key] / counts[key]:.4f}" for key in sums))
+    else:
+        print("rendered depth: no key frame with observed depth")
 
 
 if __name__ == "__main__":

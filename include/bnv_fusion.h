@@ -843,6 +843,67 @@ int bnv_nn_workspace_bytes(int64_t n_ref, int64_t n_query, int64_t* bytes);
 int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_query, void* workspace,
                  int64_t ws_bytes, float* d2_out, int32_t* idx_out, bnv_stream_t stream);
 
+/* ---- Rendering (bnv_fusion_amd/csrc/render.hip): depth and normal images of the map from a camera pose.  The
+ * reference has no such entry; these are the semantics SparseVolume.render_depth / TSDFVolume.render_depth expose and
+ * the tests replay in float32 (every operation below is one IEEE fp32 rounding, in the order written, sqrt and division
+ * correctly rounded; no contraction).
+ *
+ * Camera.  T_wc_host: float32 [4][4] row-major camera-to-world (camera looks along +z, y points down); K_host:
+ * float32 [3][3] row-major pinhole matrix.  Pixel p = v W + u (u the column) has its centre at integer (u, v):
+ *   x = (u - cx) / fx,  y = (v - cy) / fy,  w_a = (R[a][0] x + R[a][1] y) + R[a][2],  nrm = sqrt((w0 w0 + w1 w1) + w2 w2),
+ *   d_a = w_a / nrm (unit direction), o = T_wc[:3, 3].  A point at Euclidean distance t has z-depth t / nrm.
+ * Sample box.  lo = the grid's origin, hi_a = lo_a + (float)(n_a - 1) * voxel (the neural volume: lo = bound_min,
+ * n = n_xyz; the TSDF volume: lo = origin, n = dim) -- the points whose interpolation corners can all lie in the grid.
+ * Per axis with d_a != 0: t1 = (lo_a - o_a) / d_a, t2 = (hi_a - o_a) / d_a, tin = max(tin, min(t1, t2)),
+ * tout = min(tout, max(t1, t2)) from tin = 0, tout = +inf; an axis with d_a == 0 and o_a outside [lo_a, hi_a] has no
+ * sample.  t0 = max(tin, near * nrm), t1 = min(tout, max_depth * nrm).
+ * Schedule.  s = step * voxel (voxel: the volume's own; step >= BNV_RENDER_MIN_STEP); sample k >= 0 lies at t_k = t0 + (float)k * s, point
+ * p_k = o + t_k d (per axis o_a + t_k d_a), for every k with t_k <= t1.  Acceleration (brick, hash, the walk) only
+ * decides which samples are evaluated, never where they lie.
+ * Field and domain, neural volume: f(p) = bnv_decode_pts at world point p with the same rows, weights, row_limit,
+ * network, mode and delta.  p is in the domain iff the 8 corners decode_pts gathers (floor / ceil per axis of
+ * c = (p - bound_min) / voxel) are all rows r of the volume with r < row_limit.  The out-of-domain sample right before a
+ * run of in-domain samples is the run's lead-in: decode_pts gives it its masked constant (voxel_size, plus the delta
+ * when one is set -- a corner without a row is free space, as the mesh of the same state treats it), without the
+ * MLP.  No other out-of-domain sample is decoded.
+ * Field and domain, TSDF volume: c = (p - origin) / voxel, i = floor(c), f = c - i; in the domain iff the 8 grid
+ * points i + {0,1}^3 lie in the grid and have weight > 0 (unobserved voxels hold -trunc_margin); f(p) = trilinear with
+ * lerp(a, b, f) = a + f (b - a), along x (corner pairs differing in x), then y, then z.
+ * Hit.  The first k >= 1 with sample k in the domain, sample k - 1 in the domain or k's lead-in (neural volume only;
+ * the TSDF volume needs both in the domain) and f(k-1) > 0 >= f(k): a run whose lead-in (or, on the TSDF volume, whose
+ * first sample) is at or below 0 is not a hit -- the ray started inside the surface or met a back face.  Without the
+ * lead-in, a run of rows that begins inside the surface -- the positive side of a surface often lies in cells with a
+ * corner missing -- would hide it.  t_hit = t_{k-1} + (f(k-1) / (f(k-1) - f(k))) s, depth = t_hit / nrm
+ * (z-depth in metres; 0 = no hit, like the input depth images).
+ * Normals (optional, world frame, unit length, 0 where there is no hit or the gradient is 0), at p_hit = o + t_hit d:
+ * neural: g_a = f(p_hit + e e_a) - f(p_hit - e e_a) with e = BNV_RENDER_NORMAL_EPS * voxel (p_hit_a + e, p_hit_a - e);
+ * TSDF: the gradient of the trilinear interpolant at p_hit (cell clamped into the grid); then g / sqrt((gx gx + gy gy)
+ * + gz gz).  Outputs: depth_out f32 [H, W], normals_out f32 [H, W, 3] or NULL. */
+#define BNV_RENDER_NORMAL_EPS 0.5f   /* central-difference offset of neural normals, in voxels */
+#define BNV_RENDER_DEFAULT_K 8       /* in-domain samples a ray appends per round (plus a lead-in) */
+#define BNV_RENDER_MIN_STEP 0.05f    /* smallest sample spacing, in voxels: smaller steps are BNV_ERR_INVALID_ARGUMENT */
+
+/* Workspace bytes of bnv_render_depth for n_rays = H * W rays appending up to k (1..32) samples per round; 0 when the
+ * arguments are out of range.  One workspace serves any number of renders of that size. */
+size_t bnv_render_workspace_bytes(int64_t n_rays, int32_t k);
+/* Renders the sparse neural volume (semantics above).  Rounds until no ray is active: every active ray appends its
+ * next <= k in-domain samples to a compacted buffer, bnv_decode_pts evaluates them, a resolve pass records hits and
+ * retires rays.  Each round reads two counters back to the host (the stream is synchronised once per round and once
+ * for the normals), so this entry is not capturable into a graph.  stats_host (NULL: skipped): int64 [4] = {rounds,
+ * samples decoded, of those the live ones (all corner weights >= min_pts_in_grid), hits}.  A sharded grid
+ * (shard_world > 1) is BNV_ERR_INVALID_ARGUMENT.  The volume is only read. */
+int bnv_render_depth(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host, const float* features,
+                     const float* weights, int64_t row_limit, const float* sdfmlp_pack,
+                     const bnv_sdf_delta_t* delta_host, const float T_wc_host[16], const float K_host[9], int32_t H,
+                     int32_t W, float near_z, float max_depth, float step, int32_t k, void* ws, size_t ws_bytes,
+                     float* depth_out, float* normals_out, int64_t* stats_host, bnv_stream_t stream);
+/* Renders the TSDF side volume (tsdf, weight: the [X, Y, Z] f32 volumes of bnv_tsdf_integrate, dim = {X, Y, Z},
+ * origin / voxel_size their grid) with the same camera, schedule and hit rule; one launch, no host read. */
+int bnv_tsdf_render_depth(const float* tsdf, const float* weight, const int32_t dim[3], const float origin_host[3],
+                          float voxel_size, const float T_wc_host[16], const float K_host[9], int32_t H, int32_t W,
+                          float near_z, float max_depth, float step, float* depth_out, float* normals_out,
+                          bnv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
