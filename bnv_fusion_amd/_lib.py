@@ -34,6 +34,7 @@ SYMBOLS = [
     "bnv_mesh_sample_surface_workspace", "bnv_mesh_sample_surface", "bnv_nn_workspace_bytes", "bnv_nn_query",
     "bnv_tsdf_mesh_workspace_bytes", "bnv_tsdf_mesh_count", "bnv_tsdf_mesh_emit",
     "bnv_render_workspace_bytes", "bnv_render_depth", "bnv_tsdf_render_depth",
+    "bnv_mesh_post_workspace_bytes", "bnv_mesh_post_process",
     
 ]
 
@@ -272,6 +273,8 @@ def load():
         "bnv_tsdf_render_depth": (C.c_int, [vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float,
                                             C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, C.c_float, C.c_float,
                                             C.c_float, vp, vp, vp]),
+        "bnv_mesh_post_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+        "bnv_mesh_post_process": (C.c_int, [vp, i64, vp, i64, C.c_double, vp, i64, vp, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

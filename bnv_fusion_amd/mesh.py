@@ -190,6 +190,73 @@ def post_process_mesh(mesh, vertex_threshold=0.005):
     return TriMesh(vs.astype(np.float32), f)
 
 
+_POST_EXTENT_LIMIT = 2.0 ** 29   # |x| / eps below it: the device neighbour grid is exact (bnv_fusion.h: 2^30 on u)
+
+
+def post_process_mesh_tensors(vertices, faces, vertex_threshold=0.005):
+    """``post_process_mesh`` on the device (csrc/meshpost.hip; include/bnv_fusion.h, "Mesh post-processing"):
+    vertices [V, 3] float32 and faces [T, 3] int64 on the GPU -> (vertices [V', 3] float32, faces [T', 3] int64) on the
+    same device, bit for bit what the host function returns.  The only host reads: one for the input checks, one for
+    the two output counts.  Raises ValueError on CPU tensors, wrong shapes or dtypes, face indices outside [0, V),
+    non-finite vertices, a negative or non-finite threshold, or coordinates beyond 2^29 thresholds."""
+    for name, t, dt in (("vertices", vertices, torch.float32), ("faces", faces, torch.int64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"post_process_mesh_tensors: {name} must be a GPU tensor (there is no CPU path; the host "
+                             "function is mesh.post_process_mesh)")
+        if t.dim() != 2 or t.shape[1] != 3 or t.dtype != dt:
+            raise ValueError(f"post_process_mesh_tensors: {name} must be [N, 3] {dt} (got {list(t.shape)} {t.dtype})")
+    if vertices.device != faces.device:
+        raise ValueError("post_process_mesh_tensors: vertices and faces are on different devices")
+    eps = float(vertex_threshold)
+    if not (np.isfinite(eps) and eps >= 0.0):
+        raise ValueError(f"post_process_mesh_tensors: vertex_threshold must be finite and >= 0 (got {eps})")
+    V, T = int(vertices.shape[0]), int(faces.shape[0])
+    if V >= 2 ** 31 - 1 or T >= 2 ** 31 - 1:
+        raise ValueError(f"post_process_mesh_tensors: {V} vertices / {T} faces: indices are int32 on the device")
+    dev = vertices.device
+    vertices, faces = vertices.detach().contiguous(), faces.detach().contiguous()
+    if V == 0 and T == 0:
+        return vertices.clone(), faces.clone()
+    # one host read for every check: finite, face index range, extent against the neighbour grid
+    checks = [torch.isfinite(vertices).all().to(torch.float64)]
+    if V:
+        checks.append(vertices.abs().max().to(torch.float64))
+    if T:
+        checks += [faces.min().to(torch.float64), faces.max().to(torch.float64)]
+    got = torch.stack(checks).tolist()
+    if not got[0]:
+        raise ValueError("post_process_mesh_tensors: vertices must be finite")
+    if T and (V == 0 or got[-2] < 0 or got[-1] >= V):
+        raise ValueError(f"post_process_mesh_tensors: a face indexes a vertex outside [0, {V})")
+    if V and eps > 0.0 and got[1] >= _POST_EXTENT_LIMIT * eps:
+        raise ValueError(f"post_process_mesh_tensors: coordinates up to {got[1]:g} are beyond 2^29 vertex thresholds "
+                         f"({eps:g}): the device neighbour grid would not be exact")
+    lib = _lib.load()
+    need = C.c_int64()
+    _lib.check(lib.bnv_mesh_post_workspace_bytes(V, T, C.byref(need)), "bnv_mesh_post_workspace_bytes")
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
+        v_out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        f_out = torch.empty((T, 3), dtype=torch.int64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(lib.bnv_mesh_post_process(_lib.ptr(vertices), V, _lib.ptr(faces), T, C.c_double(eps), _lib.ptr(ws),
+                                             int(need.value), _lib.ptr(v_out), _lib.ptr(f_out), _lib.ptr(counts),
+                                             _lib.stream_ptr()), "bnv_mesh_post_process")
+        nv, nf = counts.tolist()                   # the one host read of the result: the mesh's size
+    if nv < 0:
+        raise _lib.BnvError("bnv_mesh_post_process rejected input that passed the host-side checks")
+    return v_out[:nv], f_out[:nf]
+
+
+def post_process_mesh_gpu(mesh, vertex_threshold=0.005, device="cuda:0"):
+    """``post_process_mesh`` of a TriMesh on the GPU: the same TriMesh, bit for bit, through one upload and
+    ``to_host``.  Same errors as post_process_mesh_tensors."""
+    v = torch.from_numpy(np.ascontiguousarray(mesh.vertices, dtype=np.float32)).to(device)
+    f = torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int64)).to(device)
+    vs, fs = post_process_mesh_tensors(v, f, vertex_threshold)
+    return TriMesh(*to_host(vs, fs))
+
+
 _PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
                 "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
                 "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}

@@ -333,12 +333,14 @@ class NeuralMap:
         delta = self.prepare_tsdf_volume() if self.tsdf_vol is not None else self.sdf_delta
         return self.volume.meshlize_sdf(self.pointnet.nerf, delta)
 
-    def extract_mesh(self, path=None):
-        """run_e2e.py:164-167: mesh of the whole volume (TSDF prior included when enabled) -> TriMesh or None."""
+    def extract_mesh(self, path=None, post_process=None):
+        """run_e2e.py:164-167: mesh of the whole volume (TSDF prior included when enabled) -> TriMesh or None.
+        ``post_process``: None, or a vertex threshold (run_e2e.py:293 uses voxel_size / 4) -- the mesh is then
+        post-processed on the device, the same as mesh.post_process_mesh(extract_mesh(), post_process)."""
         self._drain_pipe()
         delta = self.prepare_tsdf_volume() if self.tsdf_vol is not None else self.sdf_delta
         self.volume.to_tensor()
-        out = self.volume.meshlize(self.pointnet.nerf, delta, path)
+        out = self.volume.meshlize(self.pointnet.nerf, delta, path, post_process=post_process)
         return None if out is None else out[1]
 
     def render(self, T_wc, intr_mat, H, W, normals=True):

@@ -631,12 +631,14 @@ class SparseVolume:
         off = int(self._lib.bnv_decode_lattice_count_offset(self._row_capacity))
         return self._lattice_last[off + 4: off + 8].view(torch.int32)
 
-    def meshlize(self, nerf, sdf_delta=None, path=None):
+    def meshlize(self, nerf, sdf_delta=None, path=None, post_process=None):
         """sparse_volume.py:697-766: decode the 3x3x3 lattice of every active voxel and run per-voxel
         marching cubes -- both on the GPU.  Returns (active_pts, mesh) like the reference (None when no
         voxel straddles the surface); ``mesh`` is a bnv_fusion_amd.mesh.TriMesh (vertices / faces /
-        export), standing in for trimesh.Trimesh(process=False)."""
-        from .mesh import TriMesh, marching_cubes_lattice_indexed, to_host
+        export), standing in for trimesh.Trimesh(process=False).  ``post_process``: None, or a vertex threshold --
+        the mesh is then mesh.post_process_mesh'ed on the device (post_process_mesh_tensors, bit for bit the host
+        result) before it leaves it."""
+        from .mesh import TriMesh, marching_cubes_lattice_indexed, post_process_mesh_tensors, to_host
         assert self.active_coordinates is not None, "call self.to_tensor() first."
         active_pts = self.active_coordinates * self.voxel_size + self.min_coords
         sdf = self.decode_lattice(self.active_coordinates, nerf, sdf_delta, query_tensor=True)
@@ -645,6 +647,8 @@ class SparseVolume:
                                                             self.min_coords)
         if faces.shape[0] == 0:
             return None
+        if post_process is not None:
+            verts, faces = post_process_mesh_tensors(verts, faces, float(post_process))
         v_host, f_host, pts_host = to_host(verts, faces, active_pts)
         mesh = TriMesh(v_host, f_host)
         if path is not None:

@@ -54,6 +54,9 @@ def main():
     ap.add_argument("--tsdf-mesh", action="store_true",
                     help="also mesh the 2.5 cm TSDF side volume (observed cells only) into tsdf.ply; with --eval-gt "
                          "its summary line follows the neural mesh's: the TSDF baseline of the same run")
+    ap.add_argument("--post-process", default="host", choices=["host", "gpu"],
+                    help="where the written meshes are post-processed (merge close vertices, clean, smooth): the host "
+                         "function or its device version (same output bit for bit)")
     ap.add_argument("--render", metavar="DIR",
                     help="after the run, render the map at every key frame's pose into DIR (16-bit PNGs, millimetres) "
                          "and print the mean depth errors against the observed frames")
@@ -109,9 +112,13 @@ def main():
             nm.optimize(n_iters=n_iters, last_frame=last, ray_max_dist=max_depth)
             torch.cuda.synchronize()
             t_global += time.perf_counter() - t0
-            mesh = nm.extract_mesh()
+            if args.post_process == "gpu":
+                mesh = nm.extract_mesh(post_process=0.005)
+            else:
+                mesh = nm.extract_mesh()
+                mesh = None if mesh is None else post_process_mesh(mesh)
             if mesh is not None:                                             # :277-280
-                post_process_mesh(mesh).export(os.path.join(args.out, f"{idx}.ply"))
+                mesh.export(os.path.join(args.out, f"{idx}.ply"))
     mesh = nm.extract_mesh(os.path.join(args.out, "before_optim.ply"))   # :280-282
     steps = int(len(nm.frames) * args.skip_images) * (1 if args.mode == "demo" else 2)   # :283-284
     if not args.no_optimize:
@@ -121,9 +128,12 @@ def main():
         t_global += time.perf_counter() - t0
     print(f"speed on local fusion: {len(nm.frames) / max(t_local, 1e-9):.1f} fps"
           + ("" if args.no_optimize else f"; speed on global fusion: {steps / max(t_global, 1e-9):.1f} fps"))
-    mesh = nm.extract_mesh()                                             # :291-294
+    if args.post_process == "gpu":                                      # :291-294
+        mesh = nm.extract_mesh(post_process=nm.voxel_size / 4)
+    else:
+        mesh = nm.extract_mesh()
+        mesh = None if mesh is None else post_process_mesh(mesh, vertex_threshold=nm.voxel_size / 4)
     if mesh is not None:
-        mesh = post_process_mesh(mesh, vertex_threshold=nm.voxel_size / 4)
         mesh.export(os.path.join(args.out, "final.ply"))
     nm.save(args.out, scan_id=args.scan_id.split("/")[-1])
     tsdf_mesh = None

@@ -904,6 +904,35 @@ int bnv_tsdf_render_depth(const float* tsdf, const float* weight, const int32_t 
                           float near_z, float max_depth, float step, float* depth_out, float* normals_out,
                           bnv_stream_t stream);
 
+/* ---- Mesh post-processing (bnv_fusion_amd/csrc/meshpost.hip): mesh.post_process_mesh on the device, the reference's
+ * o3d_helper.post_process_mesh (src/utils/o3d_helper.py:220-241) as the host function restates it, with the same
+ * output bit for bit.  All arithmetic is float64, one rounding per operation in the order written, no contraction.
+ *
+ * Input: vertices f32 [V, 3], faces i64 [T, 3], eps = vertex_threshold (finite, >= 0).
+ * 1. Exact weld.  u = rint(x * 1e9) / 1e9 per coordinate (np.round(x, 9)); -0 is +0.  The distinct rows u, in
+ *    lexicographic (x, y, z) order, are the unique points 0..n-1.  Float32 values closer than 1e-9 near 0 are one point.
+ * 2. Clusters.  Unique points i and j are joined when (dx*dx + dy*dy) + dz*dz <= eps*eps (ties join); clusters are the
+ *    connected components, numbered in ascending order of their smallest member (scipy's labelling).
+ * 3. Cluster position: the members' u summed one after another in ascending index order, divided by the count.
+ * 4. Faces: every corner -> unique point -> cluster.  Faces with two equal corners are dropped.  A face rotated so its
+ *    smallest label comes first (cyclic order kept) is a duplicate of an earlier face with the same rotation: the first
+ *    occurrence is kept, face order preserved.  A face with the reversed winding is not a duplicate.
+ * 5. Only clusters the surviving faces reference are kept, in label order; the faces are renumbered.
+ * 6. One pass of simple Laplacian smoothing: neighbours = the distinct vertices sharing a triangle edge;
+ *    out = (v + sum of neighbours in ascending index order) / (1 + degree), rounded to float32.
+ * A mesh without faces comes back unchanged (V' = V, T' = 0); every face degenerate gives V' = T' = 0.
+ *
+ * Workspace: bnv_mesh_post_workspace_bytes (~180 B per vertex + ~150 B per face; V, T < 2^31 - 1, else
+ * BNV_ERR_INVALID_ARGUMENT).  bnv_mesh_post_process writes vertices_out f32 [V, 3] and faces_out i64 [T, 3] (capacities
+ * of the input's size: V' <= V, T' <= T) and the device int64[2] counts = {V', T'}; the rows past the counts are
+ * unspecified.  Input the device finds invalid -- a non-finite vertex, a face index outside [0, V), or (eps > 0) a
+ * coordinate with |u| / eps >= 2^30, beyond which the neighbour grid's cells are not exact -- gives counts = {-1, -1}.
+ * No allocation, synchronisation or host read: the caller reads the two counts. */
+int bnv_mesh_post_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t* bytes);
+int bnv_mesh_post_process(const float* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces,
+                          double vertex_threshold, void* workspace, int64_t ws_bytes, float* vertices_out,
+                          int64_t* faces_out, int64_t* counts, bnv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
