@@ -35,6 +35,8 @@ SYMBOLS = [
     "bnv_tsdf_mesh_workspace_bytes", "bnv_tsdf_mesh_count", "bnv_tsdf_mesh_emit",
     "bnv_render_workspace_bytes", "bnv_render_depth", "bnv_tsdf_render_depth",
     "bnv_mesh_post_workspace_bytes", "bnv_mesh_post_process",
+    "bnv_depth_to_points_gated", "bnv_depth_to_points_padded_gated", "bnv_encode_begin_depth_gated",
+    "bnv_frame_begin_depth_gated",
     
 ]
 
@@ -148,6 +150,9 @@ def load():
         "bnv_encode_begin": (C.c_int, [vp, i64, C.POINTER(Grid), vp, sz, i64, vp]),
         "bnv_encode_begin_depth": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                              C.POINTER(C.c_double), C.c_double, C.POINTER(Grid), vp, sz, i64, vp, vp]),
+        "bnv_encode_begin_depth_gated": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_double), C.c_double, vp, C.c_int, C.POINTER(Grid), vp,
+                                                   sz, i64, vp, vp]),
         "bnv_encode_finish": (C.c_int, [vp, i64, C.POINTER(Grid), vp, vp, sz, i64, vp, vp, vp, vp, i64, C.c_int,
                                         vp, vp]),
         "bnv_encode_finish_image": (C.c_int, [vp, i64, C.c_int, C.POINTER(Grid), vp, vp, sz, i64, vp, vp, vp, vp, i64,
@@ -207,6 +212,11 @@ def load():
                                           C.c_double, vp, sz, vp, vp, vp]),
         "bnv_depth_to_points_padded": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.c_double, vp, sz, vp, vp, vp]),
+        "bnv_depth_to_points_gated": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                                C.POINTER(C.c_double), C.c_double, vp, C.c_int, vp, sz, vp, vp, vp]),
+        "bnv_depth_to_points_padded_gated": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                                       C.POINTER(C.c_double), C.c_double, vp, C.c_int, vp, sz, vp, vp,
+                                                       vp]),
         "bnv_tsdf_integrate": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float, vp, vp,
                                          C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float,
                                          vp, vp]),
@@ -245,6 +255,8 @@ def load():
         "bnv_frame_pipe_destroy": (C.c_int, [vp]),
         "bnv_frame_begin_depth": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), vp]),
+        "bnv_frame_begin_depth_gated": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_double), vp, C.c_int, vp]),
         "bnv_frame_begin_points": (C.c_int, [vp, C.c_int, vp, i64]),
         "bnv_frame_upsert": (C.c_int, [vp, C.c_int, C.POINTER(Volume), vp, sz, vp, i32]),
         "bnv_frame_bound": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),

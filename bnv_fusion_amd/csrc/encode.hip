@@ -2159,9 +2159,18 @@ int bnv_encode_begin(const float* input_pts, int64_t n_points, const bnv_grid_t*
 int bnv_encode_begin_depth(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
                            const double* T_wc_host, double max_depth, const bnv_grid_t* grid_host, void* ws_ptr,
                            size_t ws_bytes, int64_t ws_max_points, float* out_pts, bnv_stream_t stream_) {
+  return bnv_encode_begin_depth_gated(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, nullptr, 0, grid_host,
+                                      ws_ptr, ws_bytes, ws_max_points, out_pts, stream_);
+}
+
+int bnv_encode_begin_depth_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
+                                 const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
+                                 const bnv_grid_t* grid_host, void* ws_ptr, size_t ws_bytes, int64_t ws_max_points,
+                                 float* out_pts, bnv_stream_t stream_) {
   if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   if (!depth || !intr_host || !T_wc_host || !grid_host || !ws_ptr || !out_pts || H <= 0 || W <= 0 || depth_dtype < 0 ||
-      depth_dtype > 2 || (int64_t)H * W > (1 << 27) || ws_max_points < (int64_t)H * W)
+      depth_dtype > 2 || (int64_t)H * W > (1 << 27) || ws_max_points < (int64_t)H * W ||
+      !front_conf_args_ok(conf, conf_level))
     return BNV_ERR_INVALID_ARGUMENT;
   const bnv_grid_t g = *grid_host;
   if (!grid_ok(g)) return BNV_ERR_INVALID_ARGUMENT;
@@ -2170,6 +2179,8 @@ int bnv_encode_begin_depth(const void* depth, int depth_dtype, int H, int W, con
   if (encode_ws_layout(ws_max_points, g.n_xyz, (char*)ws_ptr, &ws) > ws_bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
   FrontArgs a;
   front_args_fill(a, depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth);
+  a.conf = conf;
+  a.conf_level = conf_level;
   const int64_t n = (int64_t)H * W;
   hipLaunchKernelGGL(k_front_mark, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a, out_pts, g, ws.bytemap,
                      ws.chunk_flag, ws.valid_blocks,

@@ -23,7 +23,7 @@ __global__ __launch_bounds__(kFrontThreads) void k_front_count(FrontArgs a, uint
 #pragma unroll
   for (int e = 0; e < kFrontItems; ++e) {
     const int64_t i = base + e;
-    if (i < n) s += depth_at(a, (int)(i / a.W), (int)(i % a.W)) > 0.0 ? 1u : 0u;
+    if (i < n) s += pixel_valid(a, (int)(i / a.W), (int)(i % a.W)) ? 1u : 0u;
   }
   uint32_t total;
   block_exclusive_scan<kFrontThreads>(s, wave_tot, &total);
@@ -56,20 +56,20 @@ __global__ __launch_bounds__(kFrontThreads) void k_front_points(FrontArgs a, con
   __shared__ uint32_t wave_tot[kFrontThreads / 64];
   const int64_t n = (int64_t)a.H * a.W;
   const int64_t base = (int64_t)blockIdx.x * kFrontTile + (int64_t)threadIdx.x * kFrontItems;
-  double dd[kFrontItems];
+  bool ok[kFrontItems];
   uint32_t s = 0;
 #pragma unroll
   for (int e = 0; e < kFrontItems; ++e) {
     const int64_t i = base + e;
-    dd[e] = (i < n) ? depth_at(a, (int)(i / a.W), (int)(i % a.W)) : 0.0;
-    s += dd[e] > 0.0 ? 1u : 0u;
+    ok[e] = (i < n) && pixel_valid(a, (int)(i / a.W), (int)(i % a.W));   // (k_front_count's predicate)
+    s += ok[e] ? 1u : 0u;
   }
   uint32_t total;
   uint32_t run = block_exclusive_scan<kFrontThreads>(s, wave_tot, &total) + block_sums[blockIdx.x];
 #pragma unroll
   for (int e = 0; e < kFrontItems; ++e) {
     const int64_t i = base + e;
-    if (!(dd[e] > 0.0)) {
+    if (!ok[e]) {
       if (pad_total && i < n) {
         float* o = out + ((size_t)*pad_total + (size_t)(i - run)) * 6;
 #pragma unroll
@@ -98,14 +98,17 @@ size_t bnv_depth_workspace_bytes(int H, int W) {
 }
 
 static int depth_to_points_impl(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                                const double* T_wc_host, double max_depth, void* ws, size_t ws_bytes, float* out_pts,
-                                int32_t* n_out, bool pad, bnv_stream_t stream_) {
+                                const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
+                                void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out, bool pad,
+                                bnv_stream_t stream_) {
   if (!depth || !intr_host || !T_wc_host || !ws || !out_pts || !n_out || H <= 0 || W <= 0 || depth_dtype < 0 ||
-      depth_dtype > 2 || (int64_t)H * W >= (1LL << 31))
+      depth_dtype > 2 || (int64_t)H * W >= (1LL << 31) || !front_conf_args_ok(conf, conf_level))
     return BNV_ERR_INVALID_ARGUMENT;
   if (ws_bytes < bnv_depth_workspace_bytes(H, W)) return BNV_ERR_WORKSPACE_TOO_SMALL;
   FrontArgs a;
   front_args_fill(a, depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth);
+  a.conf = conf;
+  a.conf_level = conf_level;
   hipStream_t stream = (hipStream_t)stream_;
   const int nb = (int)(((int64_t)H * W + kFrontTile - 1) / kFrontTile);
   uint32_t* sums = (uint32_t*)ws;
@@ -122,15 +125,29 @@ static int depth_to_points_impl(const void* depth, int depth_dtype, int H, int W
 int bnv_depth_to_points(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
                         const double* T_wc_host, double max_depth, void* ws, size_t ws_bytes, float* out_pts,
                         int32_t* n_out, bnv_stream_t stream) {
-  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, ws, ws_bytes, out_pts, n_out,
-                              false, stream);
+  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, nullptr, 0, ws, ws_bytes,
+                              out_pts, n_out, false, stream);
 }
 
 int bnv_depth_to_points_padded(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
                                const double* T_wc_host, double max_depth, void* ws, size_t ws_bytes, float* out_pts,
                                int32_t* n_out, bnv_stream_t stream) {
-  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, ws, ws_bytes, out_pts, n_out,
-                              true, stream);
+  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, nullptr, 0, ws, ws_bytes,
+                              out_pts, n_out, true, stream);
+}
+
+int bnv_depth_to_points_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
+                              const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level, void* ws,
+                              size_t ws_bytes, float* out_pts, int32_t* n_out, bnv_stream_t stream) {
+  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, conf, conf_level, ws,
+                              ws_bytes, out_pts, n_out, false, stream);
+}
+
+int bnv_depth_to_points_padded_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
+                                     const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
+                                     void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out, bnv_stream_t stream) {
+  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, conf, conf_level, ws,
+                              ws_bytes, out_pts, n_out, true, stream);
 }
 
 }  // extern "C"

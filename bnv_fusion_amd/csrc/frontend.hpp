@@ -16,6 +16,8 @@ struct FrontArgs {
   double T[12];  // rows 0..2 of T_wc
   double max_depth;
   float fxf, fyf, cxf, cyf;  // depth2xyz builds its pixel rays in float32 (geometry.py:163-168)
+  const uint8_t* conf;       // [H, W] depth confidence (ARKit: 0 / 1 / 2) or null: no gate
+  int conf_level;            // a pixel is kept when conf >= conf_level (FusionInferenceDatasetARKit.read_mask)
 };
 
 __device__ __forceinline__ double depth_at(const FrontArgs& a, int y, int x) {
@@ -39,11 +41,24 @@ __device__ __forceinline__ void xyz_at(const FrontArgs& a, int y, int x, double 
   p[2] = d;
 }
 
+// The confidence half of "pixel valid" (row-major pixel index i).  Deliberately not part of depth_at / xyz_at: the
+// reference multiplies the confidence into the ROW mask only (fusion_inference_dataset.py:49-51, 75), so the Sobel
+// stencil of a kept pixel still reads the depth of a rejected neighbour.
+__device__ __forceinline__ bool conf_ok(const FrontArgs& a, int64_t i) {
+  return !a.conf || (int)a.conf[i] >= a.conf_level;
+}
+
+// "pixel valid": 0 < depth < max_depth and, with a confidence map, conf >= conf_level.  The one predicate of the count
+// kernel, the emit kernel (compaction and NaN padding) and front_point: they must agree row for row.
+__device__ __forceinline__ bool pixel_valid(const FrontArgs& a, int y, int x) {
+  return depth_at(a, y, x) > 0.0 && conf_ok(a, (int64_t)y * a.W + x);
+}
+
 // World point (out[0..2]) and world normal (out[3..5]) of pixel (y, x), rounded to float32; false if the pixel is
-// invalid (depth 0 or >= max_depth).
+// invalid (depth 0 or >= max_depth, or confidence below the gate).
 __device__ __forceinline__ bool front_point(const FrontArgs& a, int y, int x, float (&out)[6]) {
   const double d = depth_at(a, y, x);
-  if (!(d > 0.0)) return false;
+  if (!(d > 0.0) || !conf_ok(a, (int64_t)y * a.W + x)) return false;
   // ---- normal: Sobel/8 of the xyz map, cross product, L2 normalise (kornia depth_to_normals) ----
   double A[3], B[3], C[3], D[3], E[3], F[3], gx[3], gy[3];
   xyz_at(a, y - 1, x + 1, A); xyz_at(a, y, x + 1, B); xyz_at(a, y + 1, x + 1, C);
@@ -88,6 +103,14 @@ static inline void front_args_fill(FrontArgs& a, const void* depth, int depth_dt
   a.fyf = (float)a.fy;
   a.cxf = (float)a.cx;
   a.cyf = (float)a.cy;
+  a.conf = nullptr;
+  a.conf_level = 0;
+}
+
+// the confidence gate of the *_gated entries: a null map with a positive level is a caller error; a null map with
+// level 0 is the ungated front end
+static inline bool front_conf_args_ok(const uint8_t* conf, int conf_level) {
+  return conf_level >= 0 && (conf || conf_level == 0);
 }
 
 }  // namespace bnv

@@ -32,6 +32,7 @@
 #include <new>
 
 #include "bnv_common.hpp"
+#include "frontend.hpp"   // front_conf_args_ok
 
 using namespace bnv;
 
@@ -308,7 +309,16 @@ static int side_depth(bnv_frame_pipe* p, int slot, const void* depth, int depth_
 
 int bnv_frame_begin_depth(bnv_frame_pipe_t* p, int slot, const void* depth, int depth_dtype, int H, int W,
                           const double* intr_host, const double* T_wc_host, const float* color_im) {
-  if (!slot_ok(p, slot)) return BNV_ERR_INVALID_ARGUMENT;
+  return bnv_frame_begin_depth_gated(p, slot, depth, depth_dtype, H, W, intr_host, T_wc_host, nullptr, 0, color_im);
+}
+
+// The confidence gate applies to the neural encode only: the TSDF side fusion reads the range-masked depth, as the
+// reference's does (run_e2e.py:99-109 fuses frame['rgbd'], which read_mask does not touch), and stays gated by the
+// frame's in-bounds point count, taken after the confidence gate.
+int bnv_frame_begin_depth_gated(bnv_frame_pipe_t* p, int slot, const void* depth, int depth_dtype, int H, int W,
+                                const double* intr_host, const double* T_wc_host, const uint8_t* conf, int conf_level,
+                                const float* color_im) {
+  if (!slot_ok(p, slot) || !front_conf_args_ok(conf, conf_level)) return BNV_ERR_INVALID_ARGUMENT;
   const bnv_frame_pipe_config_t& c = p->cfg;
   const bnv_frame_slot_t& b = c.slots[slot];
   if (!b.input_pts || (int64_t)H * W > c.max_points || !intr_host || !T_wc_host) return BNV_ERR_INVALID_ARGUMENT;
@@ -316,8 +326,8 @@ int bnv_frame_begin_depth(bnv_frame_pipe_t* p, int slot, const void* depth, int 
   int rc = begin_head(p, slot);
   if (rc != BNV_OK) return rc;
   const bnv_grid_t g = slot_grid(p, slot);
-  rc = bnv_encode_begin_depth(depth, depth_dtype, H, W, intr_host, T_wc_host, c.max_depth, &g, slot_encws(p, slot),
-                              c.enc_ws_bytes, c.enc_ws_max_points, b.input_pts, p->F);
+  rc = bnv_encode_begin_depth_gated(depth, depth_dtype, H, W, intr_host, T_wc_host, c.max_depth, conf, conf_level, &g,
+                                    slot_encws(p, slot), c.enc_ws_bytes, c.enc_ws_max_points, b.input_pts, p->F);
   if (rc != BNV_OK) return rc;
   rc = begin_tail(p, slot, b.input_pts, (int64_t)H * W, W);
   if (rc != BNV_OK) return rc;

@@ -7,6 +7,17 @@
     <data_dir>/<scan_id>/pose/dimensions.txt    3 numbers: the metric extent of the volume
     <data_dir>/<scan_id>/image/<i>.jpg          colour (only counted, never decoded on this path)
 
+``ARKitDataset`` reads the other layout the reference offers (``FusionInferenceDatasetARKit``,
+fusion_inference_dataset.py:242-306): an iPhone / iPad LiDAR capture exported by the *3D Scanner* app ("All Data"),
+
+    <data_dir>/<scan_id>/depth_<n>.png    16-bit greyscale, millimetres (256x192 on current devices)
+    <data_dir>/<scan_id>/conf_<n>.png     8-bit greyscale, ARKit depth confidence 0 / 1 / 2
+    <data_dir>/<scan_id>/frame_<n>.json   cameraPoseARFrame (4x4, row-major, ARKit camera axes), intrinsics (3x3,
+                                          row-major, of the 1920x1440 colour image)
+    <data_dir>/<scan_id>/export.obj       the app's rough mesh: its bounds place the volume
+
+and ``write_arkit_capture`` writes it.
+
 ``FusionInferenceDataset`` yields the frame dicts ``NeuralMap.integrate`` / ``fuse_and_decode_async`` take
 (``depth`` as a uint16 tensor on the device: the GPU front end replaces the dataset's numpy unprojection).
 OpenCV is not a dependency: the PNG container is parsed here (chunks + zlib), the scanline filters are reversed by
@@ -14,6 +25,7 @@ OpenCV is not a dependency: the PNG container is parsed here (chunks + zlib), th
 ``examples/run_e2e.py`` for a synthetic scene).
 """
 import ctypes as C
+import json
 import os
 import struct
 import zlib
@@ -99,12 +111,20 @@ def write_png16(path, image, filter_type=0, level=6):
     return _write_png(path, w, h, raw, level)
 
 
-def _write_png(path, w, h, raw, level):
+def write_png8(path, image, level=6):
+    """numpy [H, W] uint8 -> 8-bit greyscale PNG (no scanline filter): an ARKit confidence map."""
+    img = np.ascontiguousarray(np.asarray(image, dtype=np.uint8))
+    h, w = img.shape
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), img], axis=1).tobytes()
+    return _write_png(path, w, h, raw, level, bit_depth=8)
+
+
+def _write_png(path, w, h, raw, level, bit_depth=16):
     def chunk(kind, body):
         return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
 
     with open(path, "wb") as fh:
-        fh.write(_PNG_SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 16, 0, 0, 0, 0))
+        fh.write(_PNG_SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, bit_depth, 0, 0, 0, 0))
                  + chunk(b"IDAT", zlib.compress(raw, level)) + chunk(b"IEND", b""))
     return path
 
@@ -146,11 +166,7 @@ class FusionInferenceDataset:
         intr = _read_matrix(os.path.join(self.root, "pose", f"intr_mat_{i}.txt"))[:3, :3].copy()
         if self.downsample_scale != 1.0:
             # load_depth's dense mode (common.py:96-103): nearest-neighbour resize, intrinsics scaled (:135)
-            h, w = depth.shape
-            rh, rw = int(h * self.downsample_scale), int(w * self.downsample_scale)
-            ys = np.minimum((np.arange(rh) * (h / rh)).astype(np.int64), h - 1)     # cv2.INTER_NEAREST: floor(dst * scale)
-            xs = np.minimum((np.arange(rw) * (w / rw)).astype(np.int64), w - 1)
-            depth = depth[ys][:, xs]
+            depth = _resize_nearest(depth, self.downsample_scale)
             intr[:2, :3] *= self.downsample_scale
         return {
             "frame_id": i, "scene_id": self.scan_id, "max_depth": self.max_depth,
@@ -163,6 +179,131 @@ class FusionInferenceDataset:
     def __iter__(self):
         for k in range(len(self)):
             yield self[k]
+
+
+def _resize_nearest(img, scale):
+    """cv2.resize(img, (int(w * scale), int(h * scale)), interpolation=cv2.INTER_NEAREST): floor(dst * src / dst)."""
+    h, w = img.shape
+    rh, rw = int(h * scale), int(w * scale)
+    ys = np.minimum((np.arange(rh) * (h / rh)).astype(np.int64), h - 1)
+    xs = np.minimum((np.arange(rw) * (w / rw)).astype(np.int64), w - 1)
+    return img[ys][:, xs]
+
+
+# ARKit's camera looks down -z with y up; the reference's frames look down +z with y down (fusion_inference_dataset.py:
+# 290-294).  Its own inverse.
+_ARKIT_FLIP = np.diag([1.0, -1.0, -1.0, 1.0])
+ARKIT_INTR_SCALE = 1 / 7.5      # colour intrinsics (1920x1440) -> depth intrinsics (256x192), hard-coded by the reference
+
+
+def read_obj_vertices(path):
+    """The ``v`` lines of a Wavefront OBJ file -> float64 [N, 3] (all the volume placement needs of the mesh)."""
+    verts = []
+    with open(path, "r") as fh:
+        for line in fh:
+            if line.startswith("v ") or line.startswith("v\t"):
+                verts.append([float(t) for t in line.split()[1:4]])
+    if not verts:
+        raise ValueError(f"{path}: no vertices")
+    return np.asarray(verts, dtype=np.float64)
+
+
+class ARKitDataset:
+    """FusionInferenceDatasetARKit (fusion_inference_dataset.py:242-306): an iPhone / iPad LiDAR capture, frames in the
+    numeric order of their names (depth_10 after depth_9).  ``dimensions`` and ``axis_align_mat`` come from the
+    bounds of ``export.obj`` (the volume is centred on them); poses are ``axis_align_mat @ cameraPoseARFrame @
+    diag(1, -1, -1, 1)`` in float64; the colour intrinsics are scaled by ``intr_scale * downsample_scale``.
+
+    Each frame dict is shaped like FusionInferenceDataset's (``depth`` uint16 on the device, ``intr_mat``, ``T_wc``,
+    ...) and also carries the confidence map (``conf`` uint8 on the device) and ``conf_level``: NeuralMap keeps the
+    pixels with ``0 < depth < max_depth`` and ``conf >= conf_level`` as points and as training rays; the normals and the
+    TSDF side fusion see the range-masked depth, as in the reference.  ``skip_images`` (the reference ignores it for
+    this layout) keeps every k-th frame; the default keeps all."""
+
+    def __init__(self, data_dir, scan_id, confidence_level=2, max_depth=3.0, downsample_scale=1.0,
+                 intr_scale=ARKIT_INTR_SCALE, skip_images=1, device="cuda:0"):
+        self.root = os.path.join(data_dir, scan_id)
+        self.scan_id = scan_id
+        self.device = device
+        self.confidence_level = int(confidence_level)
+        self.max_depth = max_depth
+        self.downsample_scale = float(downsample_scale)
+        self.intr_scale = float(intr_scale)
+        obj = os.path.join(self.root, "export.obj")
+        if not os.path.exists(obj):
+            raise FileNotFoundError(f"{obj}: missing -- the capture's rough mesh, whose bounds place the volume")
+        v = read_obj_vertices(obj)
+        lo, hi = v.min(axis=0), v.max(axis=0)
+        self.dimensions = hi - lo
+        self.axis_align_mat = np.eye(4)
+        self.axis_align_mat[:3, 3] = -(lo + hi) / 2
+        names = [f.split("_")[1].split(".")[0] for f in os.listdir(self.root) if f.startswith("depth_")]
+        self.names = sorted(names, key=int)[:: max(int(skip_images), 1)]
+
+    def __len__(self):
+        return len(self.names)
+
+    def __getitem__(self, k):
+        n = self.names[k]
+        depth_path = os.path.join(self.root, f"depth_{n}.png")
+        conf_path = os.path.join(self.root, f"conf_{n}.png")
+        if not os.path.exists(conf_path):
+            raise FileNotFoundError(f"{conf_path}: missing -- the depth confidence map of frame {n}")
+        depth = read_png16(depth_path)
+        conf = read_png16(conf_path).astype(np.uint8)
+        with open(os.path.join(self.root, f"frame_{n}.json"), "r") as fh:
+            cam = json.load(fh)
+        T_wc = self.axis_align_mat @ np.asarray(cam["cameraPoseARFrame"], dtype=np.float64).reshape(4, 4) @ _ARKIT_FLIP
+        intr = np.asarray(cam["intrinsics"], dtype=np.float64).reshape(3, 3)      # (a fresh array: scaled in place)
+        intr[:2, :3] *= self.intr_scale * self.downsample_scale
+        if self.downsample_scale != 1.0:
+            depth = _resize_nearest(depth, self.downsample_scale)
+            conf = _resize_nearest(conf, self.downsample_scale)
+        return {
+            "frame_id": k, "scene_id": self.scan_id, "max_depth": self.max_depth,
+            "depth": torch.from_numpy(depth).to(self.device),
+            "conf": torch.from_numpy(conf).to(self.device), "conf_level": self.confidence_level,
+            "depth_path": depth_path, "conf_path": conf_path,
+            "intr_mat": intr, "T_wc": T_wc,
+        }
+
+    def __iter__(self):
+        for k in range(len(self)):
+            yield self[k]
+
+
+def write_arkit_capture(data_dir, scan_id, depths_u16, confs_u8, intrinsics, poses, dimensions, center=(0.0, 0.0, 0.0),
+                        intr_scale=ARKIT_INTR_SCALE, names=None, filter_type=0, level=6):
+    """Writes a capture in the layout ARKitDataset reads: the inverse of the loader.  ``poses``: T_wc in the loader's
+    frame (centred volume, +z forward); written as cameraPoseARFrame = translate(center) @ T_wc @ diag(1, -1, -1, 1).
+    ``intrinsics`` (one 3x3, or one per frame) at depth resolution; written at colour resolution (rows 0-1 divided by
+    ``intr_scale``).  ``export.obj`` is the box ``center +- dimensions / 2`` (8 vertices, 12 triangles): the loader
+    recovers ``dimensions`` and ``axis_align_mat = translate(-center)`` from it.  ``names``: the frames' <n> (default
+    0, 1, ...)."""
+    root = os.path.join(data_dir, scan_id)
+    os.makedirs(root, exist_ok=True)
+    center = np.asarray(center, dtype=np.float64).reshape(3)
+    half = np.asarray(dimensions, dtype=np.float64).reshape(3) / 2
+    with open(os.path.join(root, "export.obj"), "w") as fh:
+        for c in range(8):
+            sgn = np.array([1.0 if c & 1 else -1.0, 1.0 if c & 2 else -1.0, 1.0 if c & 4 else -1.0])
+            fh.write("v " + " ".join(repr(float(x)) for x in center + sgn * half) + "\n")
+        quads = [(0, 2, 3, 1), (4, 5, 7, 6), (0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5)]
+        for a, b, c, d in quads:
+            fh.write(f"f {a + 1} {b + 1} {c + 1}\nf {a + 1} {c + 1} {d + 1}\n")
+    unalign = np.eye(4)
+    unalign[:3, 3] = center
+    for i, (d, cf, T) in enumerate(zip(depths_u16, confs_u8, poses)):
+        n = str(names[i]) if names is not None else str(i)
+        write_png16(os.path.join(root, f"depth_{n}.png"), d, filter_type, level)
+        write_png8(os.path.join(root, f"conf_{n}.png"), cf, level)
+        K = np.array(intrinsics[i] if np.ndim(intrinsics) == 3 else intrinsics, dtype=np.float64).reshape(3, 3)
+        K[:2, :3] /= intr_scale
+        pose = unalign @ np.asarray(T, dtype=np.float64).reshape(4, 4) @ _ARKIT_FLIP
+        with open(os.path.join(root, f"frame_{n}.json"), "w") as fh:
+            json.dump({"cameraPoseARFrame": [float(x) for x in pose.reshape(-1)],
+                       "intrinsics": [float(x) for x in K.reshape(-1)]}, fh)
+    return root
 
 
 def write_sequence(data_dir, scan_id, depths_u16, intrinsics, poses, dimensions, filter_type=4, level=6):

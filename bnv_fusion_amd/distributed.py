@@ -841,7 +841,7 @@ class HipFrameBackend:
                 return self.encode_frame(frame)
         if not self.overlap_encode:
             self._enc_src = None
-        from .neural_map import frame_input_pts
+        from .neural_map import frame_conf
         v = self.volume
         self.pointnet.shard = (0, 1, BLOCK_LOG2)
         rows = self.record_rows(frame)
@@ -857,7 +857,8 @@ class HipFrameBackend:
                                                         v.voxel_size, out=outs)[4]
         else:      # straight from the depth image: front end fused into the voxelisation
             cnt = self.pointnet.encode_depth_async(frame["depth"], frame["intr_mat"], frame["T_wc"], self.max_depth,
-                                                   v.n_xyz, v.min_coords, v.max_coords, v.voxel_size, out=outs)[4]
+                                                   v.n_xyz, v.min_coords, v.max_coords, v.voxel_size, out=outs,
+                                                   **frame_conf(frame))[4]     # (an ARKit frame's confidence gate)
         header_counters(hdr).copy_(cnt)
         return EncodedFrame(hdr, grid_ids, pcounts, feats)
 

@@ -300,14 +300,15 @@ class LitFusionPointNet(nn.Module):
         return feats, pcounts, flat_ids, grid_ids, counters, cap
 
     def encode_depth_async(self, depth, intr_mat, T_wc, max_depth, n_xyz, bound_min, bound_max, voxel_size, out=None,
-                           between=None):
+                           between=None, conf=None, conf_level=0):
         """encode_pointcloud_async straight from a depth image [H, W] on the GPU (uint16/int16 millimetres, or
         float32/float64 metres): the front end (FusionInferenceAbstractDataset.__getitem__,
         fusion_inference_dataset.py:40-90) is fused in front of the voxelisation -- one kernel computes every pixel's
         world point + normal in float64, writes its float32 input_pts row (pixel order, NaN rows for invalid pixels)
         and marks its voxels.  Returns the same tuple as encode_pointcloud_async plus the input_pts tensor
-        [1, H*W, 6]."""
-        from .frontend import DEPTH_DTYPES
+        [1, H*W, 6].  ``conf`` / ``conf_level``: the confidence gate of frontend.depth_to_input_pts (a rejected pixel
+        is a NaN row)."""
+        from .frontend import DEPTH_DTYPES, conf_arg
         lib = self._lib_for(self.pointnet_pack)
         if not depth.is_cuda:
             raise _lib.BnvError("encode_depth_async runs on the GPU only")
@@ -320,9 +321,16 @@ class LitFusionPointNet(nn.Module):
         K = (C.c_double * 9)(*np.asarray(intr_mat, dtype=np.float64)[:3, :3].reshape(-1))
         T = (C.c_double * 16)(*np.asarray(T_wc, dtype=np.float64).reshape(-1))
         ws = (_lib.ptr(self._enc_ws), self._enc_ws.numel(), self._enc_ws_points)
-        _lib.check(lib.bnv_encode_begin_depth(_lib.ptr(d), DEPTH_DTYPES[d.dtype], H, W, K, T, float(max_depth),
-                                              C.byref(grid), *ws, _lib.ptr(pts), _lib.stream_ptr()),
-                   "bnv_encode_begin_depth")
+        c, c_ptr, level = conf_arg(conf, conf_level, (H, W), d.device, "encode_depth_async")
+        if c_ptr is None and level == 0:
+            _lib.check(lib.bnv_encode_begin_depth(_lib.ptr(d), DEPTH_DTYPES[d.dtype], H, W, K, T, float(max_depth),
+                                                  C.byref(grid), *ws, _lib.ptr(pts), _lib.stream_ptr()),
+                       "bnv_encode_begin_depth")
+        else:
+            _lib.check(lib.bnv_encode_begin_depth_gated(_lib.ptr(d), DEPTH_DTYPES[d.dtype], H, W, K, T,
+                                                        float(max_depth), c_ptr, level, C.byref(grid), *ws,
+                                                        _lib.ptr(pts), _lib.stream_ptr()),
+                       "bnv_encode_begin_depth_gated")
         if between is not None:
             between()
         _lib.check(lib.bnv_encode_finish_image(_lib.ptr(pts), n, W, C.byref(grid), _lib.ptr(self.pointnet_pack), *ws,

@@ -24,8 +24,17 @@ def frame_input_pts(frame, max_depth=3.0):
     if "input_pts" in frame:
         return frame["input_pts"]
     from .frontend import depth_to_input_pts
-    pts, _ = depth_to_input_pts(frame["depth"], frame["intr_mat"], frame["T_wc"], max_depth=max_depth, compact=False)
+    pts, _ = depth_to_input_pts(frame["depth"], frame["intr_mat"], frame["T_wc"], max_depth=max_depth, compact=False,
+                                **frame_conf(frame))
     return pts
+
+
+def frame_conf(frame):
+    """The confidence gate a depth frame carries (datasets.ARKitDataset: ``conf`` [H, W] uint8 on the device and
+    ``conf_level``) as keyword arguments of the front-end calls; {} for a frame without one."""
+    if frame.get("conf") is None:
+        return {}
+    return {"conf": frame["conf"], "conf_level": int(frame.get("conf_level", 0))}
 
 
 class FrameHandle:
@@ -224,7 +233,8 @@ class NeuralMap:
             return self.pointnet.encode_pointcloud_async(frame["input_pts"], v.n_xyz, v.min_coords, v.max_coords,
                                                          v.voxel_size)
         return self.pointnet.encode_depth_async(frame["depth"], frame["intr_mat"], frame["T_wc"], self.max_depth,
-                                                v.n_xyz, v.min_coords, v.max_coords, v.voxel_size)[:6]
+                                                v.n_xyz, v.min_coords, v.max_coords, v.voxel_size,
+                                                **frame_conf(frame))[:6]
 
     def fuse_and_decode_async(self, frame, decode=True):
         """The same work as fuse_and_decode, enqueued without any host synchronisation: integrate and the
@@ -311,15 +321,20 @@ class NeuralMap:
                 k = int(torch.randint(lo, len(self.frames), (1,), generator=cpu_gen))
                 f = self.frames[k]
                 hit = cache.get(id(f))
-                pts = hit[1] if hit is not None and hit[0] is f and hit[2] == ray_max_dist else None
+                # (the confidence gate is part of the key: gated points never answer an ungated request, or the
+                # reverse -- a frame whose conf map or conf_level changed since is recomputed)
+                gate = frame_conf(f)
+                key = (ray_max_dist, gate.get("conf_level", 0))
+                pts = hit[1] if (hit is not None and hit[0] is f and hit[2] == key
+                                 and hit[3] is gate.get("conf")) else None
                 if pts is None:
                     d = f["depth"]
                     if d.dtype in (torch.uint16, torch.int16):
                         d = d.to(torch.float32) / 1000.0
-                    pts = key_frame_points(d, f["intr_mat"], f["T_wc"], ray_max_dist)
+                    pts = key_frame_points(d, f["intr_mat"], f["T_wc"], ray_max_dist, **gate)
                     if len(cache) >= 256:
                         cache.pop(next(iter(cache)))
-                    cache[id(f)] = (f, pts, ray_max_dist)
+                    cache[id(f)] = (f, pts, key, gate.get("conf"))
                 yield sample_key_frame(None, None, None, sampling_size, ray_max_dist, generator, points=pts)
 
         return optimize_volume(self.volume, self.pointnet.nerf, batches(), self.truncated_units,

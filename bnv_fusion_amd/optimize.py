@@ -116,15 +116,21 @@ def calculate_loss(volume, rays, nerf, truncated_units, truncated_dist, ray_max_
     return {"depth_bce_loss": _RayLoss.apply(pred, target, weight, n_valid)}
 
 
-def key_frame_points(depth, intr_mat, T_wc, ray_max_dist):
+def key_frame_points(depth, intr_mat, T_wc, ray_max_dist, conf=None, conf_level=0):
     """The part of _sample_key_frame that depends on the frame alone: every pixel's world point (float64 arithmetic of
     geometry.py:150-171, rounded to float32 as the sampler's ``.float()`` does after its gather) and validity
-    (common.py:110-113).  -> (pts [H * W, 3] f32, mask [H * W] f32, H, W, host copies of T_wc / intr_mat)."""
+    (common.py:110-113).  -> (pts [H * W, 3] f32, mask [H * W] f32, H, W, host copies of T_wc / intr_mat).
+    ``conf`` [H, W] (an ARKit confidence map): the validity also requires ``conf >= conf_level``
+    (fusion_inference_dataset.py:388-389); the points stay those of the range-masked depth."""
     dev = depth.device
     intr_mat, T_wc = torch.as_tensor(intr_mat), torch.as_tensor(T_wc)
     depth = depth.to(torch.float64)
     mask = (depth > 0) & (depth < ray_max_dist)                       # common.py:110-113
     depth = depth * mask
+    if conf is not None:
+        mask = mask & (torch.as_tensor(conf, device=dev).reshape(depth.shape).to(torch.int32) >= int(conf_level))
+    elif int(conf_level) > 0:
+        raise _lib.BnvError("key_frame_points: conf_level > 0 needs a confidence map")
     H, W = depth.shape
     K = intr_mat.to(dev, torch.float32)
     T = T_wc.to(dev, torch.float32).to(torch.float64)

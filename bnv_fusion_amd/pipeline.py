@@ -220,6 +220,13 @@ class FramePipe:
             converted |= d.data_ptr() != src.data_ptr()
             if d.dtype == torch.float64 and self.tsdf_vol is not None:
                 raise _lib.BnvError("FramePipe with a TSDF side volume takes uint16 (mm) or float32 (m) depth images")
+            # the confidence gate of an ARKit frame (datasets.ARKitDataset): on the neural encode only
+            from .frontend import conf_arg
+            gated = frame.get("conf") is not None
+            conf, conf_ptr, conf_level = conf_arg(frame.get("conf"), frame.get("conf_level", 0) if gated else 0,
+                                                  (int(d.shape[-2]), int(d.shape[-1])), d.device, "FramePipe.begin")
+            if conf is not None:
+                converted |= conf.data_ptr() != frame["conf"].data_ptr()
         if not self.inputs_resident or converted:
             (self.front or self.enc).wait_stream(self.main)     # the stream the frame's first kernel runs on
         mode = _lib.model_mode(self.pointnet)            # the frame keeps it through its decode (per slot, in C)
@@ -239,9 +246,14 @@ class FramePipe:
             H, W = int(d.shape[-2]), int(d.shape[-1])
             K = (C.c_double * 9)(*np.asarray(frame["intr_mat"], dtype=np.float64)[:3, :3].reshape(-1))
             T = (C.c_double * 16)(*np.asarray(frame["T_wc"], dtype=np.float64).reshape(-1))
-            self._keep[s] = (d, col)
-            _lib.check(lib.bnv_frame_begin_depth(self._h, s, _lib.ptr(d), self._dtypes[d.dtype], H, W, K, T,
-                                                 _lib.ptr(col)), "bnv_frame_begin_depth")
+            self._keep[s] = (d, col, conf)
+            if conf_ptr is None and conf_level == 0:
+                _lib.check(lib.bnv_frame_begin_depth(self._h, s, _lib.ptr(d), self._dtypes[d.dtype], H, W, K, T,
+                                                     _lib.ptr(col)), "bnv_frame_begin_depth")
+            else:
+                _lib.check(lib.bnv_frame_begin_depth_gated(self._h, s, _lib.ptr(d), self._dtypes[d.dtype], H, W, K, T,
+                                                           conf_ptr, conf_level, _lib.ptr(col)),
+                           "bnv_frame_begin_depth_gated")
         self._busy[s] = True
         self._slot_mode[s] = mode
         self._next = (s + 1) % self.n_slots

@@ -181,3 +181,56 @@ def gt_mesh(region="union", step_px=1.0):
     tris = tris[s[tris].all(axis=1)]
     used, inv = np.unique(tris, return_inverse=True)
     return TriMesh(pw[used].astype(np.float32), inv.reshape(-1, 3))
+
+
+ARKIT_HW = (192, 256)                      # the LiDAR depth resolution of current iPhones / iPads
+ARKIT_CENTER = np.array([0.05, -0.04, 0.1])   # the scene's world box centre: the capture's export.obj is not at 0
+
+
+def arkit_capture(n_frames, voxel_size=0.01, seed=0):
+    """The synthetic scene as an iPhone LiDAR capture would hold it (datasets.write_arkit_capture's arguments): depth at
+    256x192 from ``pose(t)``, and wrong depth that the sensor marks as confidence 0.
+
+    * flying pixels: the scene has no occluding edge, so bands of 4 pixels every 48 rows and columns stand in for
+      depth edges; each band's depth is pulled 15-25 % towards the camera (one factor per band and frame), as pixels
+      that mix a foreground edge with the surface behind it -- a coherent ghost surface, not scattered noise;
+    * outliers: 1.5 % of the other pixels, 0.2-0.5 m in front of or behind the surface.
+
+    Corrupted pixels get confidence 0, their clean 4-neighbours 1, every other pixel 2.  The ARKit world is the
+    synthetic world; the loader's volume is centred on ``ARKIT_CENTER`` -> dict(depths, confs, intrinsics, poses (in
+    the loader's frame), dimensions, center, outliers: per frame the [K, 2] (row, col) pixels of the outliers)."""
+    H, W = ARKIT_HW
+    rng = np.random.default_rng(seed + 77)
+    dims = {0.01: 2.54, 0.02: 2.52}.get(voxel_size, 2.54)
+    align = np.eye(4)
+    align[:3, 3] = -ARKIT_CENTER
+    depths, confs, poses, outliers = [], [], [], []
+    for t in range(n_frames):
+        d = depth_image(t, H, W, seed)
+        bad = np.zeros((H, W), bool)
+        band = np.zeros((H, W), bool)
+        pull = np.ones((H, W))
+        for k in range(24, H, 48):
+            band[k:k + 4] = True
+            pull[k:k + 4] = rng.uniform(0.75, 0.85)
+        for k in range(24, W, 48):
+            band[:, k:k + 4] = True
+            pull[:, k:k + 4] = rng.uniform(0.75, 0.85)
+        d = np.where(band, d * pull, d)
+        bad |= band
+        sprinkle = (~band) & (rng.random((H, W)) < 0.015)
+        off = rng.uniform(0.2, 0.5, size=(H, W)) * np.where(rng.random((H, W)) < 0.5, -1.0, 1.0)
+        d = np.where(sprinkle, d + off, d)
+        bad |= sprinkle
+        near = np.zeros_like(bad)
+        near[1:] |= bad[:-1]
+        near[:-1] |= bad[1:]
+        near[:, 1:] |= bad[:, :-1]
+        near[:, :-1] |= bad[:, 1:]
+        conf = np.where(bad, 0, np.where(near, 1, 2)).astype(np.uint8)
+        depths.append(np.round(d * 1000.0).astype(np.uint16))
+        confs.append(conf)
+        poses.append(align @ pose(t))
+        outliers.append(np.argwhere(sprinkle))
+    return {"depths": depths, "confs": confs, "intrinsics": intrinsics(H, W), "poses": poses,
+            "dimensions": [dims] * 3, "center": ARKIT_CENTER.copy(), "outliers": outliers}

@@ -4,13 +4,18 @@ sequence directory, periodic global optimisation, mesh extraction, final artefac
     python examples/run_e2e.py --data-dir DATA --scan-id scene3d/lounge --out OUT          # the reference's layout
     python examples/run_e2e.py --synthetic 24 --out /tmp/bnv_demo                          # writes a synthetic scene first
     python examples/run_e2e.py ... --tsdf-mesh --eval-gt GT.ply                            # + the TSDF baseline, both scored
+    python examples/run_e2e.py --arkit --data-dir DATA --scan-id room --tiny-cuda           # an iPhone / iPad LiDAR capture
+    python examples/run_e2e.py --synthetic-arkit 24 --out /tmp/bnv_arkit                    # writes a synthetic one first
     python examples/run_e2e.py --sweep 600 --grid 512 --decode-frames --pipelined --no-optimize --out /tmp/sweep
                                                     # a moving-camera room sweep (bnv_fusion_amd/sequence.py), per-frame
                                                     # SDF decode of the touched voxels, two frames in flight
 
 Frames are read from ``<data-dir>/<scan-id>/{depth/<i>.png, pose/T_wc_<i>.txt, pose/intr_mat_<i>.txt,
 pose/dimensions.txt}`` (bnv_fusion_amd/datasets.py), the volume extent comes from ``dimensions.txt`` exactly as in
-the reference; checkpoints default to the converted weights shipped with the package.
+the reference; checkpoints default to the converted weights shipped with the package.  With ``--arkit`` they are read
+from a *3D Scanner* app export (``depth_<n>.png``, ``conf_<n>.png``, ``frame_<n>.json``, ``export.obj``:
+datasets.ARKitDataset, the reference's ``dataset=fusion_inference_dataset_arkit``); pixels whose depth confidence is
+below ``--confidence-level`` become neither points nor training rays.
 """
 import argparse
 import os
@@ -57,6 +62,13 @@ def main():
     ap.add_argument("--post-process", default="host", choices=["host", "gpu"],
                     help="where the written meshes are post-processed (merge close vertices, clean, smooth): the host "
                          "function or its device version (same output bit for bit)")
+    ap.add_argument("--arkit", action="store_true",
+                    help="read --data-dir/--scan-id as an iPhone / iPad LiDAR capture (3D Scanner app, 'All Data')")
+    ap.add_argument("--confidence-level", type=int, default=2,
+                    help="--arkit: lowest ARKit depth confidence (0 / 1 / 2) a pixel needs to be fused and trained on")
+    ap.add_argument("--synthetic-arkit", type=int, default=0,
+                    help="write this many frames of a synthetic 256x192 LiDAR capture (flying pixels and outliers "
+                         "marked confidence 0) and use them (implies --arkit)")
     ap.add_argument("--render", metavar="DIR",
                     help="after the run, render the map at every key frame's pose into DIR (16-bit PNGs, millimetres) "
                          "and print the mean depth errors against the observed frames")
@@ -81,7 +93,17 @@ def main():
                                 (sequence.depth_u16(t, scale=scale, device=dev).cpu().numpy() for t in range(args.sweep)),
                                 sequence.intrinsics(), (sequence.sweep_pose(t, scale) for t in range(args.sweep)),
                                 [dims_m] * 3, filter_type=0, level=1)
-    data = datasets.FusionInferenceDataset(args.data_dir, args.scan_id, skip_images=args.skip_images, device=dev)
+    if args.synthetic_arkit:
+        args.arkit = True
+        args.data_dir = args.data_dir or os.path.join(args.out, "data")
+        cap = synthetic.arkit_capture(args.synthetic_arkit, voxel_size=args.voxel_size)
+        datasets.write_arkit_capture(args.data_dir, args.scan_id, cap["depths"], cap["confs"], cap["intrinsics"],
+                                     cap["poses"], cap["dimensions"], center=cap["center"])
+    if args.arkit:
+        data = datasets.ARKitDataset(args.data_dir, args.scan_id, confidence_level=args.confidence_level,
+                                     skip_images=args.skip_images, device=dev)
+    else:
+        data = datasets.FusionInferenceDataset(args.data_dir, args.scan_id, skip_images=args.skip_images, device=dev)
     model = bnv.load_pretrained(device=dev, voxel_size=args.voxel_size, tiny_cuda=args.tiny_cuda)
     nm = bnv.NeuralMap(data.dimensions, args.voxel_size, model, capacity=1 << 20, device=dev, tsdf=True,
                        max_depth=data.max_depth)

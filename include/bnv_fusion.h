@@ -230,6 +230,18 @@ int bnv_depth_to_points(const void* depth, int depth_dtype, int H, int W, const 
 int bnv_depth_to_points_padded(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
                                const double* T_wc_host, double max_depth, void* ws, size_t ws_bytes,
                                float* out_pts, int32_t* n_out, bnv_stream_t stream);
+/* Both with a depth-confidence gate (FusionInferenceDatasetARKit, fusion_inference_dataset.py:242-306): conf [H,W]
+ * uint8 on the device (ARKit: 0 / 1 / 2); a pixel is a row when 0 < depth < max_depth AND conf >= conf_level.  The
+ * confidence removes rows only: the normals' Sobel stencil still reads the depth of rejected neighbours.  conf NULL
+ * with conf_level 0 is the ungated entry; conf NULL with conf_level > 0 (or conf_level < 0) is
+ * BNV_ERR_INVALID_ARGUMENT. */
+int bnv_depth_to_points_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
+                              const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
+                              void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out, bnv_stream_t stream);
+int bnv_depth_to_points_padded_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
+                                     const double* T_wc_host, double max_depth, const uint8_t* conf,
+                                     int conf_level, void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out,
+                                     bnv_stream_t stream);
 
 /* ---- TSDF side fusion: TSDFVolume.integrate (third_parties/fusion.py:68-141, called per frame from
  * run_e2e.py:99-109).  tsdf / weight / color [dx,dy,dz] f32 (color may be NULL); depth_im [h,w] f32 metres
@@ -319,6 +331,11 @@ int bnv_encode_begin(const float* input_pts, int64_t n_points, const bnv_grid_t*
 int bnv_encode_begin_depth(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
                            const double* T_wc_host, double max_depth, const bnv_grid_t* grid_host, void* ws,
                            size_t ws_bytes, int64_t ws_max_points, float* out_pts, bnv_stream_t stream);
+/* bnv_encode_begin_depth with the confidence gate of bnv_depth_to_points_gated (a rejected pixel is a NaN row). */
+int bnv_encode_begin_depth_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
+                                 const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
+                                 const bnv_grid_t* grid_host, void* ws, size_t ws_bytes, int64_t ws_max_points,
+                                 float* out_pts, bnv_stream_t stream);
 int bnv_encode_finish(const float* input_pts, int64_t n_points, const bnv_grid_t* grid_host,
                       const float* pointnet_pack, void* ws, size_t ws_bytes, int64_t ws_max_points,
                       float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids, int64_t* out_grid_ids,
@@ -779,6 +796,12 @@ int bnv_frame_pipe_set_mlp_mode(bnv_frame_pipe_t* pipe, int32_t grid_mlp_mode);
  * (the TSDF side fusion): they must stay valid until the frame's result is in. */
 int bnv_frame_begin_depth(bnv_frame_pipe_t* pipe, int slot, const void* depth, int depth_dtype, int H, int W,
                           const double* intr_host, const double* T_wc_host, const float* color_im);
+/* bnv_frame_begin_depth with the confidence gate of bnv_encode_begin_depth_gated (conf: a device buffer under the same
+ * lifetime rule as depth).  The TSDF side fusion ignores the confidence, as the reference's does; it still runs only
+ * when the frame keeps an in-bounds point after the gate. */
+int bnv_frame_begin_depth_gated(bnv_frame_pipe_t* pipe, int slot, const void* depth, int depth_dtype, int H, int W,
+                                const double* intr_host, const double* T_wc_host, const uint8_t* conf,
+                                int conf_level, const float* color_im);
 int bnv_frame_begin_points(bnv_frame_pipe_t* pipe, int slot, const float* input_pts, int64_t n_points);
 /* The TSDF side fusion (run_e2e.py:99-109) of a frame begun with bnv_frame_begin_points that ALSO carries its depth
  * image -- the reference dataset's frames hold input_pts, rgbd, intr_mat and T_wc together (run_e2e.py:78-109) -- gated
