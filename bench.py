@@ -2,7 +2,7 @@
 """Benchmark of the hot path: depth frames/sec fused + decoded, 640x480 @ 256^3 grid
 (BASELINE.json metric; workload definition in SURVEY.md section 8d / DESIGN.md section 5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One step = one synthetic 640x480 frame: uint16 depth image -> points + normals (GPU front end) ->
 encode_pointcloud + _integrate into the persistent volume (+ TSDF side fusion) (fused) + SDF decode of the
@@ -12,9 +12,9 @@ region.
 N > 1: one rank per GPU over RCCL.  Started either by `python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or as plain `python bench.py --gpus N`, which
 starts the N ranks itself as a child `torch.distributed.run` BEFORE this process makes any GPU call and exits with
-the child's code.  Both decompositions are measured in the same run; `value` is the one --parallelism names.
-Default: 'spatial', the decomposition BASELINE.json names -- the active-voxel set sharded by spatial hash, every rank
-works on every frame, one all-gather of boundary-voxel records per frame (strong scaling of one stream; a step = one
+the child's code.  `value` is the decomposition --parallelism names; with --full the other one is measured in the
+same run and reported beside it.  Default: 'spatial', the decomposition BASELINE.json names -- the active-voxel set
+sharded by spatial hash, every rank works on every frame, one all-gather of boundary-voxel records per frame (strong scaling of one stream; a step = one
 frame).  'frame': ranks encode / decode different frames of a batch, replicated volume, one all-gather of encoded
 voxels per batch (weak scaling; a step = one batch of N consecutive frames, `value` counts all of them)
 (bnv_fusion_amd/distributed.py).  Collectives time out (--dist-timeout) and any rank's failure
@@ -23,8 +23,11 @@ ends the job with a non-zero exit code.
 The timed region runs with the cyclic garbage collector disabled and a volume that does not grow inside it
 (timing hygiene); BNV_BENCH_DEBUG=1 prints per-frame enqueue times to stderr.
 Rank 0 prints ONE JSON line: metric / value -- a SUSTAINED rate: the timed steps run right behind --preheat untimed
-frames, so the clock has settled under the package power limit -- plus
-  burst            the same steps from an idle GPU (what earlier rounds reported as `value`);
+frames, so the clock has settled under the package power limit -- with unit, dtype, ms_per_step and the run's config.
+That is all a plain run reports.  On one GPU the same steps run twice from an idle GPU before the pre-heat (once with
+the encode on its own stream, once on the main stream), in a plain run too: they are part of the volume's history that
+the timed steps fuse into.  With --full the line also carries
+  burst            those same steps from an idle GPU (what earlier rounds reported as `value`);
   roofline         dominant kernel of the headline arithmetic mode, timed alone (HIP events on its stream);
   fp32_exact       the same --steps in IEEE-fp32 MFMA arithmetic (the reference's precision to the letter), with its
                    own kernel-alone roofline and parity check;
@@ -39,7 +42,10 @@ frames, so the clock has settled under the package power limit -- plus
                    ms, table-kernel and marching-cubes figures, marching cubes against the oracle's (section 8 f-4);
   parity           GPU outputs of the last timed frame against the oracle (>= 2,000 voxels);
   other_mlp_modes  the f16-operand mode (lower precision, never the headline);
-  cpu_baseline     the oracle on the host cores.
+  cpu_baseline     the oracle on the host cores;
+and, N > 1, the second decomposition and each one's parity.  The --no-* options and --sustained-frames /
+--sequence-frames pick among these entries of a --full run.  Every pass behind them runs after the timed steps, so the
+timed steps, their inputs and `value` are the same with and without --full.
 
 --dump-outputs DIR writes what the last timed step returned to its caller -- the voxel coordinates and their SDF
 lattices (rank 0's share when sharded) -- as DIR/coords.npy (float64) and DIR/sdf.npy (float32), so that two builds
@@ -601,6 +607,12 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step of `value` returned (voxel coordinates, SDF lattices; rank "
                          "0's share when sharded) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="report `burst` and, after the timed steps, measure and check everything else as well: "
+                         "roofline and kernel-alone passes, the other arithmetic modes and networks, sustained / growth "
+                         "/ sequence passes, optimiser and mesh extraction, parity against the oracle, the CPU baseline "
+                         "and (N > 1) the second decomposition.  Without it a run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the headline line")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be >= 1")
@@ -757,7 +769,7 @@ def run_bench(args, rank, world, dev, dist, backend):
             m.copy_results = False            # results are views into the pipeline's slots (collected before reuse)
         return m
 
-    kinds = ["single"] if world == 1 else ([args.parallelism] + ([] if args.no_alt_mode else
+    kinds = ["single"] if world == 1 else ([args.parallelism] + ([] if args.no_alt_mode or not args.full else
                                            [k for k in ("spatial", "frame") if k != args.parallelism]))
 
     # ---- synthetic inputs, resident in HBM before anything is timed -----------------------------
@@ -921,7 +933,7 @@ def run_bench(args, rank, world, dev, dist, backend):
                 run = timed(m, kind, args.mlp_mode, step_idx, warm_idx, preheat=min(args.preheat, 4 * POOL))
                 if args.dump_outputs and rank == 0:
                     run["outputs"] = host_outputs(run)
-                run["parity"] = parity_check(m, run)
+                run["parity"] = parity_check(m, run) if args.full else None
                 if kind == "spatial":
                     extra = {"ownership": m.backend.ownership, "block_log2": m.backend.block_log2,
                              "exchange": "rows after the upsert, one all-gather on the main stream",
@@ -997,7 +1009,7 @@ def run_bench(args, rank, world, dev, dist, backend):
                                               "stream's kernels)"),
             "kernels": {"pointnet_scatter": {"avg_ms": prim["enc_ms"], "tflops": prim["enc_tflops"],
                                              "frac_of_peak": prim["enc_tflops"] / PEAK_TFLOPS[m_]}},
-            "parity": prim["parity"],
+            **({"parity": prim["parity"]} if args.full else {}),
             "distributed": {"backend": "rccl" if backend == "nccl" else backend,
                             "world_size_seen_by_backend": dist.get_world_size(), **contact,
                             "collective_timeout_s": args.dist_timeout,
@@ -1021,9 +1033,10 @@ def run_bench(args, rank, world, dev, dist, backend):
     drv.run(nm, "single", list(range(args.preroll)), decode=False)           # setup: make the decode mask live
     warm_idx, step_idx = idx_of(1)
 
-    def measure(mode):
+    def measure(mode, full=True):
         """-> (sustained run: pre-heated timed region [+ parity], burst run: the same steps from an idle GPU,
-        kernel-alone run, note)."""
+        kernel-alone run, note).  ``full=False``: the burst passes and the timed region only (kernel-alone run and
+        note None): the burst passes stay, as the volume the timed region fuses into is what they leave behind."""
         ph = args.preheat if mode != 0 else min(args.preheat, 300)     # (exact fp32 draws less: burst == sustained)
         burst = timed(nm, "single", mode, step_idx, warm_idx)
         if getattr(nm, "overlap_encode", False):      # the dominant kernel alone at the burst clock, as rounds 1-2 quoted it
@@ -1036,6 +1049,8 @@ def run_bench(args, rank, world, dev, dist, backend):
         run = timed(nm, "single", mode, step_idx, warm_idx, preheat=ph)
         if args.dump_outputs and mode == args.mlp_mode:
             run["outputs"] = host_outputs(run)
+        if not full:
+            return run, burst, None, None
         run["parity"] = parity_check(nm, run)  # right after the timed region: the volume is in that run's final state
         # Kernel-alone pass for the roofline: with the encode on a second stream the two MLP kernels of consecutive
         # frames share the GPU, so their event-to-event durations overlap.  A roofline needs the kernel's own
@@ -1052,8 +1067,25 @@ def run_bench(args, rank, world, dev, dist, backend):
                     "frames/s")
         return run, burst, kern, note
 
-    main_run, burst_run, kern_run, kern_note = measure(args.mlp_mode)
+    main_run, burst_run, kern_run, kern_note = measure(args.mlp_mode, full=args.full)
     dumped = dump_outputs(main_run.pop("outputs"), args.dump_outputs) if args.dump_outputs else None
+    m = args.mlp_mode
+    headline = {
+        "value": main_run["fps"], "ms_per_step": 1e3 * main_run["elapsed"] / args.steps, "scaling": "weak",
+        "value_note": f"the {args.steps} timed steps run right behind {args.preheat} untimed pre-heat frames + "
+                      f"{args.warmup} warm-up steps (clock settled under the package power limit); `burst` is the same "
+                      "steps from an idle GPU" + ("" if args.full else " (reported with --full)")}
+    config = {"workload": workload, "grid": args.grid, "voxel_size": voxel, "preroll_frames": args.preroll,
+              "preheat_frames": args.preheat, "frames_per_step": 1, "mlp_mode": MODE_NAME[m],
+              "voxels_per_frame": main_run["n_vox"], "sdf_values_per_frame": 27.0 * main_run["n_vox"],
+              "decode_live_fraction": main_run["live"], "parallelism": "1 GPU",
+              "mlp_evals_last_timed_frame": main_run["rows"],
+              "persistent_lattice_tables": bool(getattr(getattr(nm, "_pipe", None), "persistent_tables", False)),
+              "mlp_evals_note": "evaluations of the last timed frame: with the persistent tables, entries of rows the "
+                                "frame did not update are carried over; roofline.mlp_evals_per_launch is a full "
+                                "recompute of a frame's entries (the kernel timed alone)"}
+    if not args.full:
+        return {**out_common, **headline, "config": config, **({"dump_outputs": dumped} if dumped else {})}
 
     def sustainable_mfma():
         """What the f16 MFMA pipe of THIS box sustains when nothing else is issued (bnv_probe_mfma_rate: every CU, two
@@ -1211,25 +1243,13 @@ def run_bench(args, rank, world, dev, dist, backend):
             if args.input == "depth":
                 extras["optimize"] = optimize_entry(nm, model, [frames[i] for i in pool[:32]], args.mlp_mode)
 
-    m = args.mlp_mode
     peak = PEAK_TFLOPS[m]
     roof = dict(roofline_of(m, kern_run, kern_note), **({"power_limited_mfma_ceiling": power_ceiling} if power_ceiling else {}))
     out = dict(out_common)
+    out.update(headline)
     out.update({
-        "value": main_run["fps"], "ms_per_step": 1e3 * main_run["elapsed"] / args.steps, "scaling": "weak",
-        "value_note": f"the {args.steps} timed steps run right behind {args.preheat} untimed pre-heat frames + "
-                      f"{args.warmup} warm-up steps (clock settled under the package power limit); `burst` is the same "
-                      "steps from an idle GPU",
         "burst": entry(burst_run),
-        "config": {"workload": workload, "grid": args.grid, "voxel_size": voxel, "preroll_frames": args.preroll,
-                   "preheat_frames": args.preheat, "frames_per_step": 1, "mlp_mode": MODE_NAME[m],
-                   "voxels_per_frame": main_run["n_vox"], "sdf_values_per_frame": 27.0 * main_run["n_vox"],
-                   "decode_live_fraction": main_run["live"], "parallelism": "1 GPU",
-                   "mlp_evals_last_timed_frame": main_run["rows"],
-                   "persistent_lattice_tables": bool(getattr(getattr(nm, "_pipe", None), "persistent_tables", False)),
-                   "mlp_evals_note": "evaluations of the last timed frame: with the persistent tables, entries of rows the "
-                                     "frame did not update are carried over; roofline.mlp_evals_per_launch is a full "
-                                     "recompute of a frame's entries (the kernel timed alone)"},
+        "config": config,
         "roofline": roof,
         "traffic_source": (roof["traffic_source"] or {}).get("file") if roof.get("traffic") else None,
         "kernels": {"pointnet_scatter": {"avg_ms": kern_run["enc_ms"], "tflops": kern_run["enc_tflops"],

@@ -30,7 +30,7 @@ def agg(d):
 
 stats = glob.glob(f"{src}/trace/**/*kernel_stats.csv", recursive=True)[0]
 shutil.copy(stats, f"{dst}/{R}_bench_kernel_stats.csv")
-# (bench_line_with_traffic.json: `python bench.py` run again AFTER this script has written the PMC summary, so that its
+# (bench_line_with_traffic.json: `python bench.py --full` run again AFTER this script has written the PMC summary, so that its
 # roofline.traffic is filled from it; preferred when present)
 d = last_json(f"{src}/bench_line_with_traffic.json" if os.path.exists(f"{src}/bench_line_with_traffic.json") else f"{src}/bench_line.json")
 dt = last_json(f"{src}/bench_line_tcnn.json")
@@ -88,7 +88,7 @@ else:
   except (OSError, ValueError):
     pass
 json.dump({"commit": commit, "decode_hip_sha256": decode_sha,
-           "command": "python3 bench.py --no-cpu-baseline --no-alt-mode --no-stream-overlap --no-power-probe",
+           "command": "python3 bench.py --full --no-cpu-baseline --no-alt-mode --no-stream-overlap --no-power-probe",
            "mlp_evals_per_launch": dp["roofline"]["mlp_evals_per_launch"], "dominant_kernel_trace": tail},
           open(f"{dst}/{R}_pmc_meta.json", "w"))
 
@@ -123,7 +123,7 @@ with open(f"{dst}/{R}_README.md", "w") as f:
     su = d.get("sustained", {})
     gr = d.get("growth", {})
     sq = d.get("sequence", {})
-    W("* `%s_bench_line.json` -- `python bench.py` (defaults: 50 steps, 5 warm-up behind 1,000 pre-heat frames; fp32 checkpoint, split_f16 MLP mode): `value` **%.1f frames/s** (%.3f ms/frame; a sustained rate), the same steps from an idle GPU (`burst`) %.1f; `sustained` pass over %d frames %.1f frames/s at %.0f MHz / %.0f W (%.2f J per frame); exact-fp32 MFMA mode %.1f frames/s (decode kernel %.3f of the fp32 MFMA peak); growing from the reference's 100,000-row capacity %.1f frames/s over the first %d frames; moving-camera `sequence` (%d frames, 512^3, growth inside the loop) %.1f frames/s to %d rows, oracle checks %s; parity vs the oracle on %d voxels: SDF max-abs-err %.1e (bar 1e-4), mask decisions equal: %s; CPU oracle baseline %.4f frames/s (%d threads of %d cores).\n" % (
+    W("* `%s_bench_line.json` -- `python bench.py --full` (defaults: 50 steps, 5 warm-up behind 1,000 pre-heat frames; fp32 checkpoint, split_f16 MLP mode): `value` **%.1f frames/s** (%.3f ms/frame; a sustained rate), the same steps from an idle GPU (`burst`) %.1f; `sustained` pass over %d frames %.1f frames/s at %.0f MHz / %.0f W (%.2f J per frame); exact-fp32 MFMA mode %.1f frames/s (decode kernel %.3f of the fp32 MFMA peak); growing from the reference's 100,000-row capacity %.1f frames/s over the first %d frames; moving-camera `sequence` (%d frames, 512^3, growth inside the loop) %.1f frames/s to %d rows, oracle checks %s; parity vs the oracle on %d voxels: SDF max-abs-err %.1e (bar 1e-4), mask decisions equal: %s; CPU oracle baseline %.4f frames/s (%d threads of %d cores).\n" % (
         R, d["value"], d["ms_per_step"], d.get("burst", {}).get("value", 0), su.get("frames", 0), su.get("value", 0), su.get("mean_sclk_mhz") or 0, su.get("mean_package_power_w") or 0, su.get("joules_per_frame") or 0,
         fe.get("value", 0), fe.get("roofline", {}).get("frac", 0), gr.get("value", 0), gr.get("frames", 0),
         sq.get("frames", 0), sq.get("value", 0), sq.get("rows_end", 0), ", ".join("%.1e" % c["sdf_max_abs_err"] for c in sq.get("parity_checks", sq.get("oracle_checks", []))),
@@ -148,7 +148,7 @@ with open(f"{dst}/{R}_README.md", "w") as f:
         enc_t = [k for k in acc if "k_pointnet_scatter_tb" in k]
         if enc_t and "WRITE_SIZE" in acc[enc_t[0]]:
             wkb = sum(acc[enc_t[0]]["WRITE_SIZE"]) / len(acc[enc_t[0]]["WRITE_SIZE"])
-            W(f"* `{R}_bench_kernel_stats_tcnn.csv`, `{R}_pmc_summary_tcnn.csv` -- kernel table and WRITE_SIZE / FETCH_SIZE passes of `bench.py --checkpoint tcnn --no-stream-overlap`: the block encoder `k_pointnet_scatter_tb` writes **{wkb * 1024 / 1e6:.0f} MB per launch** (one LDS table per workgroup and 16x16-pixel patch; one table per wave and 8x4 block: 101 MB; round 2's per-tile scatter: 366 MB, every device-scope atomic tallied at 64 B).\n")
+            W(f"* `{R}_bench_kernel_stats_tcnn.csv`, `{R}_pmc_summary_tcnn.csv` -- kernel table and WRITE_SIZE / FETCH_SIZE passes of `bench.py --full --checkpoint tcnn --no-stream-overlap`: the block encoder `k_pointnet_scatter_tb` writes **{wkb * 1024 / 1e6:.0f} MB per launch** (one LDS table per workgroup and 16x16-pixel patch; one table per wave and 8x4 block: 101 MB; round 2's per-tile scatter: 366 MB, every device-scope atomic tallied at 64 B).\n")
     sp8 = glob.glob(f"{src}/trace_sp8/**/*kernel_stats.csv", recursive=True)
     if sp8:
         shutil.copy(sp8[0], f"{dst}/{R}_spatial_world8_kernel_stats.csv")
@@ -157,8 +157,8 @@ with open(f"{dst}/{R}_README.md", "w") as f:
         if os.path.exists(f"{src}/bench_line_grid{G}.json"):
             dg = last_json(f"{src}/bench_line_grid{G}.json")
             open(f"{dst}/{R}_bench_line_grid{G}.json", "w").write(json.dumps(dg) + "\n")
-            W(f"* `{R}_bench_line_grid{G}.json` -- `python bench.py --grid {G}` (voxel {dg['config']['voxel_size']}): {dg['value']:.1f} frames/s, {dg['config']['voxels_per_frame']:.0f} voxels decoded per frame, parity on {dg['parity']['voxels_checked']} voxels {dg['parity']['sdf_max_abs_err_vs_oracle']:.1e}, mask decisions equal: {dg['parity']['mask_decisions_equal']}.\n")
-    W(f"* `{R}_bench_kernel_stats.csv` -- `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline --no-alt-mode --no-stream-overlap --no-power-probe` (the default workload: 30 fuse-only pre-roll frames + 55 fuse+decode frames; one stream, so every kernel's duration is its own).  `{R}_bench_line_profiled_run.json` is the line that very run printed: its HIP-event average for the dominant kernel (the last {tail.get('n', 0)} launches: the kernel-alone pass behind its pre-heat frames) is {dp['roofline']['avg_kernel_ms']:.3f} ms; rocprofv3's kernel trace over the same {tail.get('n', 0)} launches: **{tail.get('last_ms', 0):.3f} ms**; the table's {kt[lat]/1e6:.3f} ms averages all {tail.get('launches', 0)} launches of the run, whose first {tail.get('n', 0)} (idle GPU) take {tail.get('first_ms', 0):.3f} ms -- the package heats up and the clock settles ~20 % lower.\n")
+            W(f"* `{R}_bench_line_grid{G}.json` -- `python bench.py --full --grid {G}` (voxel {dg['config']['voxel_size']}): {dg['value']:.1f} frames/s, {dg['config']['voxels_per_frame']:.0f} voxels decoded per frame, parity on {dg['parity']['voxels_checked']} voxels {dg['parity']['sdf_max_abs_err_vs_oracle']:.1e}, mask decisions equal: {dg['parity']['mask_decisions_equal']}.\n")
+    W(f"* `{R}_bench_kernel_stats.csv` -- `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-alt-mode --no-stream-overlap --no-power-probe` (the default workload: 30 fuse-only pre-roll frames + 55 fuse+decode frames; one stream, so every kernel's duration is its own).  `{R}_bench_line_profiled_run.json` is the line that very run printed: its HIP-event average for the dominant kernel (the last {tail.get('n', 0)} launches: the kernel-alone pass behind its pre-heat frames) is {dp['roofline']['avg_kernel_ms']:.3f} ms; rocprofv3's kernel trace over the same {tail.get('n', 0)} launches: **{tail.get('last_ms', 0):.3f} ms**; the table's {kt[lat]/1e6:.3f} ms averages all {tail.get('launches', 0)} launches of the run, whose first {tail.get('n', 0)} (idle GPU) take {tail.get('first_ms', 0):.3f} ms -- the package heats up and the clock settles ~20 % lower.\n")
     W(f"* `{R}_pmc_summary.csv` (+ `{R}_pmc_meta.json`: commit and MLP evaluations per launch of the profiled run) -- three separate `rocprofv3 --pmc ... --kernel-trace` passes of that command (SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA | FETCH_SIZE GRBM_GUI_ACTIVE | WRITE_SIZE), mean per launch.\n")
     def tail_of(name, n=3):
         pth = f"{dst}/{R}_{name}.txt"
@@ -171,7 +171,7 @@ with open(f"{dst}/{R}_README.md", "w") as f:
         d8 = last_json(f"{src}/bench_line_4rank_gloo.json")
         open(f"{dst}/{R}_bench_line_4rank_gloo_functional.json", "w").write(json.dumps(d8) + "\n")
         pr = d8.get("spatial_sharding", {}).get("per_rank", [])
-        W(f"* `{R}_bench_line_4rank_gloo_functional.json` -- `BNV_DIST_BACKEND=gloo python bench.py --gpus 4 --steps 20 --preheat 64`: FOUR ranks sharing this one GPU over gloo (functional: its rates mean nothing), the real exchange among 4 shards: `spatial_sharding.per_rank[].mlp_evals_per_frame` = {[int(x['mlp_evals_per_frame']) for x in pr]}; parity of rank 0's outputs against the oracle {d8.get('spatial_sharding', {}).get('parity', {}).get('sdf_max_abs_err_vs_oracle')}.\n")
+        W(f"* `{R}_bench_line_4rank_gloo_functional.json` -- `BNV_DIST_BACKEND=gloo python bench.py --full --gpus 4 --steps 20 --preheat 64`: FOUR ranks sharing this one GPU over gloo (functional: its rates mean nothing), the real exchange among 4 shards: `spatial_sharding.per_rank[].mlp_evals_per_frame` = {[int(x['mlp_evals_per_frame']) for x in pr]}; parity of rank 0's outputs against the oracle {d8.get('spatial_sharding', {}).get('parity', {}).get('sdf_max_abs_err_vs_oracle')}.\n")
     W(f"* `{R}_spatial_world8_all_ranks_256_delay30.txt`, `{R}_spatial_world8_all_ranks_512_delay30.txt` -- the same with `--exchange-delay 30` (a 30 us spin kernel behind the stand-in all-gather: the latency of a real 8-rank collective): {tail_of('spatial_world8_all_ranks_256_delay30', 3)} || 512^3: {tail_of('spatial_world8_all_ranks_512_delay30', 3)}.\n")
     ost = glob.glob(f"{src}/trace_optimize/**/*kernel_stats.csv", recursive=True)
     if ost:
@@ -184,7 +184,7 @@ with open(f"{dst}/{R}_README.md", "w") as f:
     if os.path.exists(f"{src}/bench_line_2rank_gloo.json") and os.path.getsize(f"{src}/bench_line_2rank_gloo.json") > 10:
         d2 = last_json(f"{src}/bench_line_2rank_gloo.json")
         open(f"{dst}/{R}_bench_line_2rank_gloo_functional.json", "w").write(json.dumps(d2) + "\n")
-        W(f"* `{R}_bench_line_2rank_gloo_functional.json` -- `BNV_DIST_BACKEND=gloo python bench.py --gpus 2`: FUNCTIONAL evidence only (two ranks share one GPU, the collectives go through the host): the line a multi-GPU run prints -- `value` = the spatially sharded mode ({d2['scaling']}), `spatial_sharding` and `frame_parallel` entries with their own parity checks (spatial: SDF max-abs-err {d2['spatial_sharding']['parity']['sdf_max_abs_err_vs_oracle']:.1e}, mask decisions equal: {d2['spatial_sharding']['parity']['mask_decisions_equal']}), `distributed` = what the backend saw.  Its rates say nothing about RCCL over xGMI.\n")
+        W(f"* `{R}_bench_line_2rank_gloo_functional.json` -- `BNV_DIST_BACKEND=gloo python bench.py --full --gpus 2`: FUNCTIONAL evidence only (two ranks share one GPU, the collectives go through the host): the line a multi-GPU run prints -- `value` = the spatially sharded mode ({d2['scaling']}), `spatial_sharding` and `frame_parallel` entries with their own parity checks (spatial: SDF max-abs-err {d2['spatial_sharding']['parity']['sdf_max_abs_err_vs_oracle']:.1e}, mask decisions equal: {d2['spatial_sharding']['parity']['mask_decisions_equal']}), `distributed` = what the backend saw.  Its rates say nothing about RCCL over xGMI.\n")
     W(f"* `{R}_queue_probe.txt` -- `tools/queue_probe.py`: which pool streams overlap the default stream (those that share its hardware queue run strictly behind it); `{R}_mlp_launch_overhead.txt` -- `tools/mlp_launch_overhead.py`: duration of the two MLP kernels against the work per launch, down to an empty launch.\n\n")
     n_small = sum(1 for s in frame_kernels if kname(s))
     W(f"A frame is **{n_small + 2} kernel launches** ({n_small} small kernels + the two MLP kernels; the upsert also stamps the decode's origins and the frame's counters come back through a read-back launch, not through copies); the kernels that are not an MLP take **{non_mlp_us:.0f} us** per frame together.\n\n")
@@ -237,7 +237,7 @@ with open(f"{dst}/{R}_README.md", "w") as f:
     if os.path.exists(f"{dst}/{R}_bench_line_final_tree.json"):
         ft = last_json(f"{dst}/{R}_bench_line_final_tree.json")
         npt = ft.get("without_persistent_tables")
-        notes.append(f"* `{R}_bench_line_final_tree.json` -- `python bench.py` of the round's final tree (another box than "
+        notes.append(f"* `{R}_bench_line_final_tree.json` -- `python bench.py --full` of the round's final tree (another box than "
                      f"`{R}_bench_line.json`; same kernels): {ft['value']:.1f} frames/s"
                      + (f"; the A/B inside that run with the persistent lattice tables off (`without_persistent_tables`): "
                         f"{npt['value']:.1f} frames/s, {npt['mlp_evals_last_timed_frame'] / 1e6:.2f} M evaluations per frame "
