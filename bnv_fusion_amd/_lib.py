@@ -37,7 +37,8 @@ SYMBOLS = [
     "bnv_mesh_post_workspace_bytes", "bnv_mesh_post_process",
     "bnv_depth_to_points_gated", "bnv_depth_to_points_padded_gated", "bnv_encode_begin_depth_gated",
     "bnv_frame_begin_depth_gated",
-    
+    "bnv_train_param_floats", "bnv_train_running_floats", "bnv_train_workspace_bytes", "bnv_train_step",
+    "bnv_train_eval_loss",
 ]
 
 
@@ -287,6 +288,12 @@ def load():
                                             C.c_float, vp, vp, vp]),
         "bnv_mesh_post_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
         "bnv_mesh_post_process": (C.c_int, [vp, i64, vp, i64, C.c_double, vp, i64, vp, vp, vp, vp]),
+        "bnv_train_param_floats": (i64, []),
+        "bnv_train_running_floats": (i64, []),
+        "bnv_train_workspace_bytes": (sz, [i64, i32, i64]),
+        "bnv_train_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, C.c_float, C.c_float, C.c_float,
+                                     C.c_float, i64, vp, vp, sz, vp]),
+        "bnv_train_eval_loss": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

@@ -324,3 +324,120 @@ def write_sequence(data_dir, scan_id, depths_u16, intrinsics, poses, dimensions,
             fh.write(" ".join(repr(float(v)) for v in np.asarray(T, dtype=np.float64).reshape(-1)) + "\n")
         open(os.path.join(root, "image", f"{i}.jpg"), "wb").close()
     return root
+
+
+# --------------------------------------------------------------------------- #
+# local shape patches for training the embedding (the reference's fusion_pointnet_dataset)
+# --------------------------------------------------------------------------- #
+PATCH_CATEGORIES = ("03001627_noise", "03636649_noise")
+N_LOCAL_SAMPLES = 64
+
+
+class _PatchUnpickler:
+    """pickle.Unpickler that admits only dicts, lists, tuples, scalars and numpy arrays: a patch file cannot name
+    any other class or function."""
+    _ALLOWED = {("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
+                ("numpy.core.multiarray", "scalar"), ("numpy._core.multiarray", "scalar"),
+                ("numpy", "ndarray"), ("numpy", "dtype")}
+
+    @classmethod
+    def load(cls, fh):
+        import importlib
+        import pickle
+
+        class U(pickle.Unpickler):
+            def find_class(self, module, name):
+                if (module, name) not in cls._ALLOWED:
+                    raise pickle.UnpicklingError(f"patch files may not reference {module}.{name}")
+                return getattr(importlib.import_module(module), name)
+        return U(fh).load()
+
+
+def read_local_patch(path):
+    """One reference patch pickle: {input_pts [k, 6], center [1, 3], training_pts [M, 3], gt_sdf [M]}."""
+    with open(path, "rb") as fh:
+        data = _PatchUnpickler.load(fh)
+    if not isinstance(data, dict) or not {"input_pts", "center", "training_pts", "gt_sdf"} <= set(data):
+        raise ValueError(f"{path}: not a local patch (input_pts, center, training_pts, gt_sdf)")
+    return data
+
+
+def write_local_patches(data_dir, category, seq, patches):
+    """Writes ``patches`` (dicts with input_pts [k, 6], center [1, 3], training_pts [M, 3], gt_sdf [M]) as
+    <data_dir>/local_shapes/<category>/<seq>/<i>.pkl, the layout the reference's fusion_pointnet_dataset reads."""
+    import pickle
+    d = os.path.join(data_dir, "local_shapes", category, seq)
+    os.makedirs(d, exist_ok=True)
+    paths = []
+    for i, p in enumerate(patches):
+        path = os.path.join(d, f"{i:06d}.pkl")
+        with open(path, "wb") as fh:
+            pickle.dump({k: np.asarray(p[k]) for k in ("input_pts", "center", "training_pts", "gt_sdf")}, fh,
+                        protocol=4)
+        paths.append(path)
+    return paths
+
+
+class LocalPatchDataset:
+    """The reference's FusionPointNetDataset (src/datasets/fusion_pointnet_dataset.py) for stage "train" / "val":
+    <data_dir>/local_shapes/{03001627,03636649}_noise/<seq>/*.pkl; train = sorted(seqs)[10:] (one item per patch),
+    val = sorted(seqs)[:10] (one item per sequence: up to 500 of its patches in random order, patches of fewer than
+    16 points skipped).  ``input_pts`` is resized to 64 points as ``_resize_input_pts`` does: drawn with replacement
+    to 64 when there are fewer, then the first 64 of a random permutation.  ``seed`` seeds the draws (the reference
+    uses the global numpy / torch RNGs)."""
+
+    def __init__(self, data_dir, stage, seed=0, n_local_samples=N_LOCAL_SAMPLES):
+        if stage not in ("train", "val"):
+            raise ValueError(f"stage {stage!r}: 'train' or 'val'")
+        self.stage, self.n_local_samples = stage, n_local_samples
+        self.rng = np.random.default_rng(seed)
+        root = os.path.join(data_dir, "local_shapes")
+        self.file_paths = []
+        for cat in PATCH_CATEGORIES:
+            seq_dir = os.path.join(root, cat)
+            if not os.path.isdir(seq_dir):
+                continue
+            seqs = sorted(os.listdir(seq_dir))
+            seqs = seqs[:10] if stage == "val" else seqs[10:]
+            for seq in seqs:
+                files = [os.path.join(seq_dir, seq, f) for f in sorted(os.listdir(os.path.join(seq_dir, seq)))]
+                if stage == "val":
+                    self.file_paths.append(files)
+                else:
+                    self.file_paths.extend(files)
+
+    def __len__(self):
+        return len(self.file_paths)
+
+    def resize_input_pts(self, pts):
+        pts = np.asarray(pts, np.float32)
+        if len(pts) < self.n_local_samples:
+            pts = pts[self.rng.integers(0, len(pts), self.n_local_samples)]
+        return self.rng.permutation(pts)[: self.n_local_samples]
+
+    def _item(self, data):
+        return {"input_pts": self.resize_input_pts(data["input_pts"]),
+                "sample_center": np.asarray(data["center"], np.float32)[0],
+                "training_pts": np.asarray(data["training_pts"], np.float32),
+                "gt": np.asarray(data["gt_sdf"], np.float32)}
+
+    def __getitem__(self, idx):
+        if self.stage == "train":
+            return self._item(read_local_patch(self.file_paths[idx]))
+        items = []
+        for p in self.rng.permutation(np.array(self.file_paths[idx], dtype=object))[:500]:
+            data = read_local_patch(p)
+            if len(data["input_pts"]) < 16:
+                continue
+            items.append(self._item(data))
+        return {k: np.stack([it[k] for it in items]) for k in ("input_pts", "sample_center", "training_pts", "gt")}
+
+    def batches(self, batch_size, shuffle=True, drop_last=False):
+        """Stacked batches of training items (train stage)."""
+        order = self.rng.permutation(len(self)) if shuffle else np.arange(len(self))
+        for s in range(0, len(order), batch_size):
+            ids = order[s: s + batch_size]
+            if drop_last and len(ids) < batch_size:
+                break
+            items = [self[int(i)] for i in ids]
+            yield {k: np.stack([it[k] for it in items]) for k in ("input_pts", "training_pts", "gt")}

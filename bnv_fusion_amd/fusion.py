@@ -463,16 +463,19 @@ class _PointNetParams(nn.Module):
         self.bn4 = nn.BatchNorm1d(feat_dims)
 
 
-def load_pretrained(device="cuda:0", voxel_size=0.01, min_pts_in_grid=8, path=None, tiny_cuda=False):
+def load_pretrained(device="cuda:0", voxel_size=0.01, min_pts_in_grid=8, path=None, tiny_cuda=False, state_dict=None):
     """Model with a converted reference checkpoint (weights/pointnet_fp32.npz, or pointnet_tcnn.npz when
-    ``tiny_cuda``), frozen, on device."""
+    ``tiny_cuda``), frozen, on device.  ``state_dict``: the weights themselves instead of a file (e.g.
+    ``EmbeddingTrainer.state_dict()``)."""
     cfg = {"trainer": {"dense_volume": False},
            "model": {"feature_vector_size": 8, "voxel_size": voxel_size, "tiny_cuda": tiny_cuda,
                      "min_pts_in_grid": min_pts_in_grid,
                      "nerf": {"hidden_size": 256, "num_layers": 4, "num_encoding_fn_xyz": 1,
                               "interpolate_decode": True}}}
     model = LitFusionPointNet(cfg)
-    model.load_state_dict(weights.load_npz(path or (weights.DEFAULT_TCNN if tiny_cuda else weights.DEFAULT_FP32)))
+    if state_dict is None:
+        state_dict = weights.load_npz(path or (weights.DEFAULT_TCNN if tiny_cuda else weights.DEFAULT_FP32))
+    model.load_state_dict(state_dict)
     model.eval()
     model.to(device)
     model.freeze()

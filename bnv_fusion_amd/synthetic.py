@@ -234,3 +234,146 @@ def arkit_capture(n_frames, voxel_size=0.01, seed=0):
         outliers.append(np.argwhere(sprinkle))
     return {"depths": depths, "confs": confs, "intrinsics": intrinsics(H, W), "poses": poses,
             "dimensions": [dims] * 3, "center": ARKIT_CENTER.copy(), "outliers": outliers}
+
+
+# --------------------------------------------------------------------------- #
+# local surface patches for training the embedding (train.EmbeddingTrainer)
+# --------------------------------------------------------------------------- #
+PATCH_KINDS = ("plane", "sphere", "cylinder", "box")
+
+
+def _rotation(rng):
+    q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+    q = q * np.sign(np.diag(r))
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q
+
+
+def _unit(rng, k=None):
+    v = rng.normal(size=(3,) if k is None else (k, 3))
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def patch_shape(rng):
+    """A random analytic shape whose surface passes through a point q of [-0.3, 0.3]^3, in voxel units: a plane, a
+    sphere or a cylinder of radius 0.5 .. 8 voxels, or a box with half extents 0.5 .. 3 voxels, at a random pose."""
+    kind = PATCH_KINDS[int(rng.integers(len(PATCH_KINDS)))]
+    q = rng.uniform(-0.3, 0.3, 3)
+    nrm = _unit(rng)
+    if kind == "plane":
+        return {"kind": kind, "point": q, "normal": nrm}
+    r = float(np.exp(rng.uniform(np.log(0.5), np.log(8.0))))
+    if kind == "sphere":
+        return {"kind": kind, "center": q - r * nrm, "radius": r}
+    if kind == "cylinder":
+        a = _unit(rng)
+        a = a - np.dot(a, nrm) * nrm
+        a /= np.linalg.norm(a)
+        return {"kind": kind, "center": q - r * nrm, "axis": a, "radius": r}
+    R = _rotation(rng)
+    h = rng.uniform(0.5, 3.0, 3)
+    local = rng.uniform(-0.8, 0.8, 3) * h      # q on the +z face, off its centre
+    local[2] = h[2]
+    return {"kind": kind, "center": q - R @ local, "rotation": R, "half": h}
+
+
+def shape_sdf(s, p):
+    """Exact signed distance (negative inside) of ``patch_shape`` s at points p [..., 3]."""
+    k = s["kind"]
+    if k == "plane":
+        return (p - s["point"]) @ s["normal"]
+    if k == "sphere":
+        return np.linalg.norm(p - s["center"], axis=-1) - s["radius"]
+    if k == "cylinder":
+        d = p - s["center"]
+        d = d - (d @ s["axis"])[..., None] * s["axis"]
+        return np.linalg.norm(d, axis=-1) - s["radius"]
+    loc = (p - s["center"]) @ s["rotation"]
+    d = np.abs(loc) - s["half"]
+    return np.linalg.norm(np.maximum(d, 0.0), axis=-1) + np.minimum(d.max(-1), 0.0)
+
+
+def shape_closest(s, p):
+    """Closest surface point and the outward unit normal there, for points p [k, 3]."""
+    k = s["kind"]
+    if k == "plane":
+        n = np.broadcast_to(s["normal"], p.shape)
+        return p - shape_sdf(s, p)[:, None] * n, n.copy()
+    if k == "sphere":
+        d = p - s["center"]
+        n = d / np.maximum(np.linalg.norm(d, axis=-1, keepdims=True), 1e-12)
+        return s["center"] + s["radius"] * n, n
+    if k == "cylinder":
+        d = p - s["center"]
+        ax = (d @ s["axis"])[:, None] * s["axis"]
+        radial = d - ax
+        n = radial / np.maximum(np.linalg.norm(radial, axis=-1, keepdims=True), 1e-12)
+        return s["center"] + ax + s["radius"] * n, n
+    R, h = s["rotation"], s["half"]
+    loc = (p - s["center"]) @ R
+    inside = np.all(np.abs(loc) <= h, axis=-1)
+    c = np.clip(loc, -h, h)
+    # interior points move to the nearest face
+    gap = h - np.abs(loc)
+    axis = np.argmin(gap, axis=-1)
+    rows = np.nonzero(inside)[0]
+    c[rows, axis[rows]] = np.sign(loc[rows, axis[rows]]) * h[axis[rows]]
+    # normal: the face the closest point lies on (the largest |c| / h)
+    ratio = np.abs(c) / h - 1.0
+    face = np.argmax(ratio, axis=-1)
+    n_loc = np.zeros_like(c)
+    n_loc[np.arange(len(c)), face] = np.where(c[np.arange(len(c)), face] >= 0, 1.0, -1.0)
+    return s["center"] + c @ R.T, n_loc @ R.T
+
+
+def _surface_samples(s, k, rng):
+    """k points on the surface near the cube [-1, 1]^3 and their normals: a box's faces sampled uniformly by area
+    (a closest-point map would pile points onto its edges), other shapes: uniform points of the cube mapped to their
+    closest surface point."""
+    if s["kind"] != "box":
+        return shape_closest(s, rng.uniform(-1.0, 1.0, (k, 3)))
+    h = s["half"]
+    area = np.array([h[1] * h[2], h[0] * h[2], h[0] * h[1]]).repeat(2)
+    face = rng.choice(6, size=k, p=area / area.sum())
+    axis, sign = face // 2, np.where(face % 2 == 0, -1.0, 1.0)
+    loc = rng.uniform(-1.0, 1.0, (k, 3)) * h
+    loc[np.arange(k), axis] = sign * h[axis]
+    n_loc = np.zeros((k, 3))
+    n_loc[np.arange(k), axis] = sign
+    return s["center"] + loc @ s["rotation"].T, n_loc @ s["rotation"].T
+
+
+def local_patches(n, M, seed=0, noise=0.0, n_pts=64, near_fraction=0.5, near_sigma=0.15):
+    """``n`` training patches from analytic shapes with exact SDF, in the units of the reference's local shapes: the
+    cube [-1, 1]^3 around one lattice vertex, in voxel units, ``gt`` in voxel units as well.
+
+    Returns {"input_pts" [n, 64, 6] f32 (surface points inside the cube + outward unit normals; Gaussian position
+    noise of std ``noise`` voxels), "training_pts" [n, M, 3] f32 (a ``near_fraction`` of them a Gaussian step of std
+    ``near_sigma`` off surface points, the rest uniform in the cube, all clipped into it), "gt" [n, M] f32 (exact
+    SDF), "shapes" (the shape of every patch, see ``patch_shape``)}."""
+    rng = np.random.default_rng(seed)
+    inp = np.zeros((n, n_pts, 6), np.float32)
+    tp = np.zeros((n, M, 3), np.float32)
+    gt = np.zeros((n, M), np.float32)
+    shapes = []
+    for i in range(n):
+        while True:
+            s = patch_shape(rng)
+            cand, nrm = _surface_samples(s, 4 * n_pts, rng)
+            keep = np.all(np.abs(cand) <= 1.0, axis=-1)
+            if keep.sum() >= 8:
+                break
+        cand, nrm = cand[keep], nrm[keep]
+        idx = rng.permutation(len(cand))[:n_pts] if len(cand) >= n_pts else rng.integers(0, len(cand), n_pts)
+        pts = cand[idx] + rng.normal(scale=noise, size=(n_pts, 3)) if noise > 0 else cand[idx]
+        inp[i, :, :3] = pts
+        inp[i, :, 3:] = nrm[idx]
+        n_near = int(round(near_fraction * M))
+        base = cand[rng.integers(0, len(cand), n_near)]
+        near = base + rng.normal(scale=near_sigma, size=(n_near, 3))
+        q = np.clip(np.concatenate([near, rng.uniform(-1.0, 1.0, (M - n_near, 3))]), -1.0, 1.0).astype(np.float32)
+        tp[i] = q
+        gt[i] = shape_sdf(s, q.astype(np.float64))
+        shapes.append(s)
+    return {"input_pts": inp, "training_pts": tp, "gt": gt, "shapes": shapes}

@@ -1,0 +1,266 @@
+"""Training of the local shape embedding (point encoder + SDF decoder) on the GPU: the reference's
+``LitFusionPointNet.training_step`` with ``training_global=False`` (local_point_fusion.py:381-460, src/train.py).
+
+One ``EmbeddingTrainer.step`` is ONE call into the shared library (csrc/train.hip, include/bnv_fusion.h:
+bnv_train_step): encoder forward with train-mode BatchNorm, decoder forward, loss, the gradient of every parameter,
+the running-stat update and an Adam step, all on the caller's stream, in exact fp32, with every row sum reduced in a
+fixed order -- a run is bit-reproducible.  The parameters live on the device in one flat buffer in state_dict order;
+``state_dict()`` / ``save_npz`` / ``save_ckpt`` / ``to_model`` hand them to the inference side.
+
+Stated differences from the reference: fp32 instead of fp16 AMP; the number of input points per step
+``n`` is drawn from the trainer's own seeded generator instead of torch's global RNG; reductions run in a fixed order.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+N_LOCAL_SAMPLES = 64        # fusion_pointnet_dataset.yaml: n_local_samples
+MIN_PTS_IN_GRID = 8         # fusion_pointnet_model.yaml: min_pts_in_grid; a step draws n in [min_pts / 2, 64)
+LOSS_WEIGHTS = {"bce_loss": 1.0, "reg_loss": 0.001}   # fusion_pointnet_model.yaml:36-38 (fixed in the kernels)
+LR_STEP_SIZE, LR_GAMMA = 20000, 0.5                   # configs/optimizer/adam.yaml: StepLR, interval epoch
+
+_CONV = [(6, 128), (128, 128), (128, 128), (128, 8)]
+_GEO = [(17, 256), (256, 256), (256, 256), (256, 256)]
+
+# trainable tensors in the order of the flat device buffer (include/bnv_fusion.h: bnv_train_step)
+PARAM_SHAPES = (
+    [(f"pointnet_backbone.conv{i + 1}.{p}", (o, c, 1) if p == "weight" else (o,))
+     for i, (c, o) in enumerate(_CONV) for p in ("weight", "bias")]
+    + [(f"pointnet_backbone.bn{i + 1}.{p}", (o,)) for i, (_, o) in enumerate(_CONV) for p in ("weight", "bias")]
+    + [(f"nerf.geo_layer{i}.{p}", (o, c) if p == "weight" else (o,))
+       for i, (c, o) in enumerate(_GEO) for p in ("weight", "bias")]
+    + [("nerf.fc_alpha.weight", (1, 256)), ("nerf.fc_alpha.bias", (1,))])
+# running statistics, per BatchNorm layer: running_mean then running_var
+RUNNING_SHAPES = [(f"pointnet_backbone.bn{i + 1}.{p}", (o,)) for i, (_, o) in enumerate(_CONV)
+                  for p in ("running_mean", "running_var")]
+# the reference's colour head: in its state_dict (strict loading), never evaluated (modules.py:912-920)
+COLOR_HEAD_SHAPES = [("nerf.color_layer0.weight", (128, 295)), ("nerf.color_layer0.bias", (128,)),
+                     ("nerf.color_layer1.weight", (128, 128)), ("nerf.color_layer1.bias", (128,)),
+                     ("nerf.fc_rgb.weight", (3, 128)), ("nerf.fc_rgb.bias", (3,))]
+
+
+def state_dict_keys():
+    """Keys of weights/pointnet_fp32.npz, in its order."""
+    keys = [f"pointnet_backbone.conv{i + 1}.{p}" for i in range(4) for p in ("weight", "bias")]
+    for i in range(4):
+        keys += [f"pointnet_backbone.bn{i + 1}.{p}"
+                 for p in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")]
+    keys += [f"nerf.geo_layer{i}.{p}" for i in range(4) for p in ("weight", "bias")]
+    return keys + ["nerf.fc_alpha.weight", "nerf.fc_alpha.bias"]
+
+
+def default_state_dict(seed=0):
+    """PyTorch's default initialisation of the reference's Conv1d / BatchNorm1d / Linear layers, from ``seed``."""
+    g = torch.Generator().manual_seed(int(seed))
+    sd = {}
+
+    def uniform(shape, bound):
+        return ((torch.rand(shape, generator=g, dtype=torch.float64) * 2 - 1) * bound).float().numpy()
+
+    def linear(prefix, c_in, shape_w, c_out):
+        # kaiming_uniform_(a=sqrt(5)) on the weight and U(-1/sqrt(fan_in), 1/sqrt(fan_in)) on the bias: both bounds
+        # are 1 / sqrt(fan_in)
+        bound = 1.0 / np.sqrt(c_in)
+        sd[prefix + ".weight"] = uniform(shape_w, bound)
+        sd[prefix + ".bias"] = uniform((c_out,), bound)
+
+    for i, (c, o) in enumerate(_CONV):
+        linear(f"pointnet_backbone.conv{i + 1}", c, (o, c, 1), o)
+    for i, (_, o) in enumerate(_CONV):
+        p = f"pointnet_backbone.bn{i + 1}"
+        sd[p + ".weight"] = np.ones(o, np.float32)
+        sd[p + ".bias"] = np.zeros(o, np.float32)
+        sd[p + ".running_mean"] = np.zeros(o, np.float32)
+        sd[p + ".running_var"] = np.ones(o, np.float32)
+        sd[p + ".num_batches_tracked"] = np.array(0, np.int64)
+    for i, (c, o) in enumerate(_GEO):
+        linear(f"nerf.geo_layer{i}", c, (o, c), o)
+    linear("nerf.fc_alpha", 256, (1, 256), 1)
+    return {k: sd[k] for k in state_dict_keys()}
+
+
+def _np(v):
+    return v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+
+
+def check_shapes(input_pts, training_pts, gt, n):
+    """ValueError unless input_pts [B, 64, 6], training_pts [B, M, 3], gt [B, M] (or [B, M, 1]), 1 <= n <= 64 and
+    B n >= 2 (the batch statistics need two rows)."""
+    if input_pts.dim() != 3 or input_pts.shape[1] != N_LOCAL_SAMPLES or input_pts.shape[2] != 6:
+        raise ValueError(f"input_pts must be [B, {N_LOCAL_SAMPLES}, 6], got {tuple(input_pts.shape)}")
+    B = input_pts.shape[0]
+    if training_pts.dim() != 3 or training_pts.shape[0] != B or training_pts.shape[2] != 3:
+        raise ValueError(f"training_pts must be [B={B}, M, 3], got {tuple(training_pts.shape)}")
+    M = training_pts.shape[1]
+    if tuple(gt.shape) not in ((B, M), (B, M, 1)):
+        raise ValueError(f"gt must be [B={B}, M={M}], got {tuple(gt.shape)}")
+    if not 1 <= n <= N_LOCAL_SAMPLES:
+        raise ValueError(f"n={n}: 1 .. {N_LOCAL_SAMPLES} input points per patch")
+    if B * n < 2:
+        raise ValueError(f"B * n = {B * n}: train-mode BatchNorm needs at least two rows")
+    if M < 1:
+        raise ValueError("M must be >= 1")
+    return B, M
+
+
+class EmbeddingTrainer:
+    """Trains the point encoder and SDF decoder with Adam (torch defaults, ``lr``) and an epoch-wise StepLR
+    (step 20000, gamma 0.5), batch after batch, on ``device``.
+
+    ``state_dict``: initial weights in the reference's key layout (``weights.load_npz``, a checkpoint's
+    ``state_dict``); None: PyTorch's default initialisation from ``seed``.  ``seed`` also seeds the draw of ``n``."""
+
+    def __init__(self, state_dict=None, seed=0, lr=1e-3, device="cuda:0", betas=(0.9, 0.999), eps=1e-8):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("EmbeddingTrainer runs on the GPU (device='cuda:<i>')")
+        self.lib = _lib.require_device(self.device.index or 0)
+        sd = default_state_dict(seed) if state_dict is None else {k: _np(v) for k, v in state_dict.items()}
+        missing = [k for k in state_dict_keys() if k not in sd]
+        if missing:
+            raise ValueError(f"state_dict lacks {missing}")
+        for k, shape in PARAM_SHAPES + RUNNING_SHAPES:
+            if tuple(np.shape(sd[k])) != shape:
+                raise ValueError(f"{k}: shape {np.shape(sd[k])}, expected {shape}")
+        n_par = int(self.lib.bnv_train_param_floats())
+        n_run = int(self.lib.bnv_train_running_floats())
+        flat = np.concatenate([np.asarray(sd[k], np.float32).ravel() for k, _ in PARAM_SHAPES])
+        run = np.concatenate([np.asarray(sd[k], np.float32).ravel() for k, _ in RUNNING_SHAPES])
+        assert flat.size == n_par and run.size == n_run, (flat.size, n_par, run.size, n_run)
+        self.params = torch.from_numpy(flat).to(self.device)
+        self.running = torch.from_numpy(run).to(self.device)
+        self.grads = torch.zeros_like(self.params)
+        self.exp_avg = torch.zeros_like(self.params)
+        self.exp_avg_sq = torch.zeros_like(self.params)
+        self.num_batches_tracked = [int(np.asarray(sd[f"pointnet_backbone.bn{i + 1}.num_batches_tracked"]))
+                                    for i in range(4)]
+        self.base_lr, self.betas, self.eps = float(lr), tuple(float(b) for b in betas), float(eps)
+        self.adam_step = 0
+        self.epoch = 0
+        self.rng = np.random.default_rng(seed)
+        self._ws = {}
+
+    # ---- schedule ----
+    @property
+    def lr(self):
+        """StepLR(step_size=20000, gamma=0.5) over epochs."""
+        return self.base_lr * LR_GAMMA ** (self.epoch // LR_STEP_SIZE)
+
+    def end_epoch(self):
+        self.epoch += 1
+
+    # ---- steps ----
+    def _workspace(self, B, n, M):
+        key = (B, M)
+        ws = self._ws.get(key)
+        nbytes = int(self.lib.bnv_train_workspace_bytes(B, N_LOCAL_SAMPLES, M))   # the largest n: one per (B, M)
+        if ws is None:
+            if nbytes == 0:
+                raise ValueError(f"shape B={B}, M={M} out of range")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ws = {key: ws}
+        return ws
+
+    def _inputs(self, input_pts, training_pts, gt):
+        f = [torch.as_tensor(t).to(self.device, torch.float32).contiguous() for t in (input_pts, training_pts, gt)]
+        return f[0], f[1], f[2]
+
+    def draw_n(self):
+        """n = randint(min_pts_in_grid / 2, n_local_samples), drawn once per step (local_point_fusion.py:411-415)."""
+        return int(self.rng.integers(MIN_PTS_IN_GRID // 2, N_LOCAL_SAMPLES))
+
+    def step(self, input_pts, training_pts, gt, n=None):
+        """One training step on a batch: input_pts [B, 64, 6], training_pts [B, M, 3], gt [B, M].  The first ``n``
+        points of every patch feed the encoder (None: drawn).  Returns the loss terms as device tensors
+        ({"loss", "bce_loss", "reg_loss"}); nothing synchronises."""
+        if n is None:
+            n = self.draw_n()
+        n = int(n)
+        x, p, g = self._inputs(input_pts, training_pts, gt)
+        B, M = check_shapes(x, p, g, n)
+        ws = self._workspace(B, n, M)
+        loss = torch.empty(3, dtype=torch.float32, device=self.device)
+        self.adam_step += 1
+        with torch.cuda.device(self.device):
+            rc = self.lib.bnv_train_step(
+                _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                _lib.ptr(self.running), _lib.ptr(x), _lib.ptr(p), _lib.ptr(g), B, n, M, C.c_float(self.lr),
+                C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.adam_step,
+                _lib.ptr(loss), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        if rc != 0:
+            self.adam_step -= 1
+        _lib.check(rc, "bnv_train_step")
+        self.num_batches_tracked = [v + 1 for v in self.num_batches_tracked]
+        return {"loss": loss[0], "bce_loss": loss[1], "reg_loss": loss[2]}
+
+    def eval_loss(self, batch, n=N_LOCAL_SAMPLES):
+        """Validation loss (local_point_fusion.py:462-480): eval-mode BatchNorm, all 64 points; returns the L1 term
+        (``val_loss``) as a device scalar.  ``batch``: a dict with input_pts, training_pts, gt."""
+        x, p, g = self._inputs(batch["input_pts"], batch["training_pts"], batch["gt"])
+        B, M = check_shapes(x, p, g, n)
+        ws = self._workspace(B, n, M)
+        loss = torch.empty(3, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bnv_train_eval_loss(_lib.ptr(self.params), _lib.ptr(self.running), _lib.ptr(x), _lib.ptr(p),
+                                              _lib.ptr(g), B, n, M, _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
+                                              _lib.stream_ptr())
+        _lib.check(rc, "bnv_train_eval_loss")
+        return loss[1]
+
+    # ---- weights out ----
+    def parameters(self):
+        """name -> device tensor view into the flat parameter buffer, in state_dict shapes."""
+        out, o = {}, 0
+        for k, shape in PARAM_SHAPES:
+            size = int(np.prod(shape))
+            out[k] = self.params[o: o + size].view(shape)
+            o += size
+        return out
+
+    def gradients(self):
+        """name -> device tensor view of the last step's gradients."""
+        out, o = {}, 0
+        for k, shape in PARAM_SHAPES:
+            size = int(np.prod(shape))
+            out[k] = self.grads[o: o + size].view(shape)
+            o += size
+        return out
+
+    def state_dict(self):
+        """The weights as numpy arrays with exactly the keys, shapes and dtypes of weights/pointnet_fp32.npz."""
+        par = self.params.cpu().numpy()
+        run = self.running.cpu().numpy()
+        sd, o = {}, 0
+        for k, shape in PARAM_SHAPES:
+            size = int(np.prod(shape))
+            sd[k] = par[o: o + size].reshape(shape).copy()
+            o += size
+        o = 0
+        for k, shape in RUNNING_SHAPES:
+            sd[k] = run[o: o + shape[0]].copy()
+            o += shape[0]
+        for i in range(4):
+            sd[f"pointnet_backbone.bn{i + 1}.num_batches_tracked"] = np.array(self.num_batches_tracked[i], np.int64)
+        return {k: sd[k] for k in state_dict_keys()}
+
+    def save_npz(self, path):
+        """Writes the weights in the layout of weights/pointnet_fp32.npz (``load_pretrained(path=...)`` reads it)."""
+        with open(path, "wb") as fh:
+            np.savez(fh, **self.state_dict())
+
+    def save_ckpt(self, path):
+        """Writes ``{"state_dict": ...}`` that the reference's LitFusionPointNet loads strictly (run_e2e.py:232-233):
+        the trained tensors plus the never-evaluated colour head as zeros."""
+        sd = {k: torch.from_numpy(v) for k, v in self.state_dict().items()}
+        for k, shape in COLOR_HEAD_SHAPES:
+            sd[k] = torch.zeros(shape, dtype=torch.float32)
+        torch.save({"state_dict": sd}, path)
+
+    def to_model(self, voxel_size=0.01, min_pts_in_grid=MIN_PTS_IN_GRID, device=None):
+        """A frozen LitFusionPointNet with these weights, repacked for the inference kernels (``NeuralMap``)."""
+        from .fusion import load_pretrained
+        return load_pretrained(device=device or self.device, voxel_size=voxel_size, min_pts_in_grid=min_pts_in_grid,
+                               state_dict=self.state_dict())

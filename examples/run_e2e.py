@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--voxel-size", type=float, default=0.01)
     ap.add_argument("--tiny-cuda", action="store_true", help="the reference's default tiny-cuda-nn checkpoint")
+    ap.add_argument("--weights", metavar="PATH", help="fp32 embedding weights (.npz, e.g. examples/train_embedding.py's "
+                    "last.npz) instead of the shipped checkpoint")
     ap.add_argument("--skip-images", type=int, default=1)
     ap.add_argument("--optim-interval", type=int, default=100)        # fusion_pointnet_model.yaml:48
     ap.add_argument("--mode", default="offline", choices=["demo", "offline"])
@@ -104,7 +106,7 @@ def main():
                                      skip_images=args.skip_images, device=dev)
     else:
         data = datasets.FusionInferenceDataset(args.data_dir, args.scan_id, skip_images=args.skip_images, device=dev)
-    model = bnv.load_pretrained(device=dev, voxel_size=args.voxel_size, tiny_cuda=args.tiny_cuda)
+    model = bnv.load_pretrained(device=dev, voxel_size=args.voxel_size, tiny_cuda=args.tiny_cuda, path=args.weights)
     nm = bnv.NeuralMap(data.dimensions, args.voxel_size, model, capacity=1 << 20, device=dev, tsdf=True,
                        max_depth=data.max_depth)
     t_local = t_global = 0.0

@@ -956,6 +956,38 @@ int bnv_mesh_post_process(const float* vertices, int64_t n_vertices, const int64
                           double vertex_threshold, void* workspace, int64_t ws_bytes, float* vertices_out,
                           int64_t* faces_out, int64_t* counts, bnv_stream_t stream);
 
+/* ---- Training of the local shape embedding (bnv_fusion_amd/csrc/train.hip): the reference's
+ * LitFusionPointNet.training_step with training_global=False (local_point_fusion.py:381-460), in exact fp32.
+ *
+ * params: f32 [bnv_train_param_floats()], every trainable tensor of the state_dict, flattened in state_dict order:
+ * conv1..4 (weight, bias), bn1..4 (weight, bias), geo_layer0..3 (weight, bias), fc_alpha (weight, bias).  running:
+ * f32 [bnv_train_running_floats()], per BatchNorm layer its running_mean then its running_var.  grads, adam_m, adam_v:
+ * f32 like params.  input_pts f32 [B, 64, 6] (xyz, normal; rows 0..n-1 of each patch are read), training_pts f32
+ * [B, M, 3] and gt f32 [B, M], in voxel units.  Shapes: B >= 1, 1 <= n <= 64, B n >= 2, M >= 1, B M <= 2^24;
+ * anything else is BNV_ERR_INVALID_ARGUMENT.
+ *
+ * bnv_train_step: encoder forward with train-mode BatchNorm (batch statistics over the B n rows, biased variance,
+ * eps 1e-5; running stats updated with momentum 0.1 and the unbiased variance), per-patch mean -> feats [B, 8];
+ * decoder over the B M rows [xyz, sin xyz, cos xyz, feat]; loss_out f32 [3] = {l1 + 0.001 reg, l1, reg} with
+ * l1 = mean |pred - gt|, reg = mean_b |feats_b|; the gradient of every parameter into grads (overwritten; the conv
+ * biases' is written as its exact value 0, train-mode BatchNorm removing them); then one
+ * Adam step (torch's formula, step number adam_step >= 1) on params.  num_batches_tracked is the caller's.
+ * bnv_train_eval_loss: the same forward with eval-mode BatchNorm (running stats), nothing written but
+ * loss_out = {l1, l1, reg}.  Every sum over rows is reduced in a fixed order with no float atomics: results are
+ * bit-reproducible for a given shape.  Both are a fixed sequence of launches on stream: no allocation,
+ * synchronisation or host read.  Workspace: bnv_train_workspace_bytes(B, n, M) (0 for an invalid shape); one
+ * workspace serves both entries for that shape. */
+int64_t bnv_train_param_floats(void);
+int64_t bnv_train_running_floats(void);
+size_t bnv_train_workspace_bytes(int64_t B, int32_t n, int64_t M);
+int bnv_train_step(float* params, float* grads, float* adam_m, float* adam_v, float* running, const float* input_pts,
+                   const float* training_pts, const float* gt, int64_t B, int32_t n, int64_t M, float lr, float beta1,
+                   float beta2, float eps, int64_t adam_step, float* loss_out, void* workspace, size_t ws_bytes,
+                   bnv_stream_t stream);
+int bnv_train_eval_loss(const float* params, const float* running, const float* input_pts, const float* training_pts,
+                        const float* gt, int64_t B, int32_t n, int64_t M, float* loss_out, void* workspace,
+                        size_t ws_bytes, bnv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
