@@ -39,6 +39,8 @@ SYMBOLS = [
     "bnv_frame_begin_depth_gated",
     "bnv_train_param_floats", "bnv_train_running_floats", "bnv_train_workspace_bytes", "bnv_train_step",
     "bnv_train_eval_loss",
+    "bnv_train_tcnn_param_floats", "bnv_train_tcnn_workspace_bytes", "bnv_train_tcnn_step", "bnv_train_tcnn_eval_loss",
+    "bnv_train_tcnn_forward",
 ]
 
 
@@ -294,6 +296,12 @@ def load():
         "bnv_train_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, C.c_float, C.c_float, C.c_float,
                                      C.c_float, i64, vp, vp, sz, vp]),
         "bnv_train_eval_loss": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
+        "bnv_train_tcnn_param_floats": (i64, []),
+        "bnv_train_tcnn_workspace_bytes": (sz, [i64, i32, i64]),
+        "bnv_train_tcnn_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, C.c_float, C.c_float,
+                                          C.c_float, C.c_float, vp, vp, sz, vp]),
+        "bnv_train_tcnn_eval_loss": (C.c_int, [vp, vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
+        "bnv_train_tcnn_forward": (C.c_int, [vp, vp, vp, i64, i32, i64, vp, vp, vp, sz, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

@@ -264,3 +264,174 @@ class EmbeddingTrainer:
         from .fusion import load_pretrained
         return load_pretrained(device=device or self.device, voxel_size=voxel_size, min_pts_in_grid=min_pts_in_grid,
                                state_dict=self.state_dict())
+
+
+# ---- the tiny-cuda-nn embedding (tiny_cuda: True, the reference's default) ----
+TCNN_KEYS = ("pointnet_backbone.model.params", "nerf.model.params")
+TCNN_WIDTHS = {"pointnet_backbone.model.params": (16, 64, 64, 64, 16), "nerf.model.params": (32, 64, 64, 64, 16)}
+TCNN_SHAPES = [(k, (sum(a * b for a, b in zip(w[:-1], w[1:])),)) for k, w in TCNN_WIDTHS.items()]   # 10240, 11264
+
+
+def tcnn_default_state_dict(seed=0):
+    """Initial weights from ``seed``: Xavier-uniform per matrix, bound sqrt(6 / (fan_in + fan_out)) on the padded
+    widths, drawn from torch.Generator(seed) as float64 U(-1, 1) * bound, encoder matrices then decoder matrices, each
+    in layer order.  A documented replacement of tiny-cuda-nn's own initial_params stream, which cannot be reproduced
+    (its FullyFusedMLP also initialises Xavier-uniform per matrix, from memory; unverified)."""
+    g = torch.Generator().manual_seed(int(seed))
+    sd = {}
+    for k, w in TCNN_WIDTHS.items():
+        mats = []
+        for fan_in, fan_out in zip(w[:-1], w[1:]):
+            bound = np.sqrt(6.0 / (fan_in + fan_out))
+            mats.append(((torch.rand((fan_out, fan_in), generator=g, dtype=torch.float64) * 2 - 1) * bound).ravel())
+        sd[k] = torch.cat(mats).float().numpy()
+    return sd
+
+
+def check_tcnn_shapes(input_pts, training_pts, gt, n):
+    """ValueError unless input_pts [B, 64, 6], training_pts [B, M, 3], gt [B, M] (or [B, M, 1]), 1 <= n <= 64, M >= 1
+    and B M <= 2^24 (no BatchNorm: B n = 1 is valid)."""
+    if input_pts.dim() != 3 or input_pts.shape[0] < 1 or input_pts.shape[1] != N_LOCAL_SAMPLES or \
+            input_pts.shape[2] != 6:
+        raise ValueError(f"input_pts must be [B >= 1, {N_LOCAL_SAMPLES}, 6], got {tuple(input_pts.shape)}")
+    B = input_pts.shape[0]
+    if training_pts.dim() != 3 or training_pts.shape[0] != B or training_pts.shape[2] != 3:
+        raise ValueError(f"training_pts must be [B={B}, M, 3], got {tuple(training_pts.shape)}")
+    M = training_pts.shape[1]
+    if tuple(gt.shape) not in ((B, M), (B, M, 1)):
+        raise ValueError(f"gt must be [B={B}, M={M}], got {tuple(gt.shape)}")
+    if not 1 <= n <= N_LOCAL_SAMPLES:
+        raise ValueError(f"n={n}: 1 .. {N_LOCAL_SAMPLES} input points per patch")
+    if M < 1 or B * M > (1 << 24):
+        raise ValueError(f"B * M = {B * M}: 1 .. 2^24 query points")
+    return B, M
+
+
+class TcnnEmbeddingTrainer(EmbeddingTrainer):
+    """Trains the tiny-cuda-nn point encoder and SDF decoder (the reference's default, ``tiny_cuda: True``) with Adam
+    and an epoch-wise StepLR, like ``EmbeddingTrainer``: csrc/train_tcnn.hip, include/bnv_fusion.h
+    (bnv_train_tcnn_step).  Forward in the f16 arithmetic of MLP mode 2, backward straight-through with hi + lo f16
+    gradient products, on the matrix cores.  A step whose loss or gradients are not finite is skipped on the device
+    (the reference's AMP gradient scaler): ``step`` reports it in ``"skipped"``.
+
+    ``state_dict``: initial weights with the two keys of weights/pointnet_tcnn.npz (``weights.load_npz(
+    weights.DEFAULT_TCNN)`` fine-tunes the shipped checkpoint); None: ``tcnn_default_state_dict(seed)``.  ``seed`` also
+    seeds the draw of ``n``."""
+
+    def __init__(self, state_dict=None, seed=0, lr=1e-3, device="cuda:0", betas=(0.9, 0.999), eps=1e-8):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("TcnnEmbeddingTrainer runs on the GPU (device='cuda:<i>')")
+        self.lib = _lib.require_device(self.device.index or 0)
+        sd = tcnn_default_state_dict(seed) if state_dict is None else {k: _np(v) for k, v in state_dict.items()}
+        for k, shape in TCNN_SHAPES:
+            if k not in sd:
+                raise ValueError(f"state_dict lacks {k}")
+            if tuple(np.shape(sd[k])) != shape:
+                raise ValueError(f"{k}: shape {np.shape(sd[k])}, expected {shape}")
+        flat = np.concatenate([np.asarray(sd[k], np.float32).ravel() for k in TCNN_KEYS])
+        assert flat.size == int(self.lib.bnv_train_tcnn_param_floats())
+        self.params = torch.from_numpy(flat).to(self.device)
+        self.grads = torch.zeros_like(self.params)
+        self.exp_avg = torch.zeros_like(self.params)
+        self.exp_avg_sq = torch.zeros_like(self.params)
+        self.adam_step = torch.zeros(1, dtype=torch.int64, device=self.device)   # advanced on the device
+        self.base_lr, self.betas, self.eps = float(lr), tuple(float(b) for b in betas), float(eps)
+        self.epoch = 0
+        self.rng = np.random.default_rng(seed)
+        self._ws = {}
+
+    def _workspace(self, B, n, M):
+        key = (B, M)
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = int(self.lib.bnv_train_tcnn_workspace_bytes(B, N_LOCAL_SAMPLES, M))   # the largest n
+            if nbytes == 0:
+                raise ValueError(f"shape B={B}, M={M} out of range")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ws = {key: ws}
+        return ws
+
+    def step(self, input_pts, training_pts, gt, n=None):
+        """One training step on a batch: input_pts [B, 64, 6], training_pts [B, M, 3], gt [B, M].  The first ``n``
+        points of every patch feed the encoder (None: drawn).  Returns device tensors {"loss", "bce_loss",
+        "reg_loss", "skipped"} (skipped: bool, the step left the weights and Adam's state as they were); nothing
+        synchronises."""
+        if n is None:
+            n = self.draw_n()
+        n = int(n)
+        x, p, g = self._inputs(input_pts, training_pts, gt)
+        B, M = check_tcnn_shapes(x, p, g, n)
+        ws = self._workspace(B, n, M)
+        loss = torch.empty(4, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bnv_train_tcnn_step(
+                _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                _lib.ptr(self.adam_step), _lib.ptr(x), _lib.ptr(p), _lib.ptr(g), B, n, M, C.c_float(self.lr),
+                C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), _lib.ptr(loss),
+                _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "bnv_train_tcnn_step")
+        return {"loss": loss[0], "bce_loss": loss[1], "reg_loss": loss[2], "skipped": loss[3] != 0}
+
+    def eval_loss(self, batch, n=N_LOCAL_SAMPLES):
+        """Validation loss: all 64 points; returns the L1 term as a device scalar.  ``batch``: a dict with input_pts,
+        training_pts, gt."""
+        x, p, g = self._inputs(batch["input_pts"], batch["training_pts"], batch["gt"])
+        B, M = check_tcnn_shapes(x, p, g, n)
+        ws = self._workspace(B, n, M)
+        loss = torch.empty(3, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bnv_train_tcnn_eval_loss(_lib.ptr(self.params), _lib.ptr(x), _lib.ptr(p), _lib.ptr(g), B, n,
+                                                   M, _lib.ptr(loss), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "bnv_train_tcnn_eval_loss")
+        return loss[1]
+
+    def forward(self, input_pts, training_pts, n=N_LOCAL_SAMPLES):
+        """feats [B, 8] and pred [B, M] of the current weights (device tensors, f16 values)."""
+        x, p, _ = self._inputs(input_pts, training_pts, torch.zeros(np.shape(training_pts)[:2]))
+        B, M = check_tcnn_shapes(x, p, torch.zeros(x.shape[0], p.shape[1]), n)
+        ws = self._workspace(B, n, M)
+        feats = torch.empty(B, 8, dtype=torch.float32, device=self.device)
+        pred = torch.empty(B, M, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.bnv_train_tcnn_forward(_lib.ptr(self.params), _lib.ptr(x), _lib.ptr(p), B, n, M,
+                                                 _lib.ptr(feats), _lib.ptr(pred), _lib.ptr(ws), ws.numel(),
+                                                 _lib.stream_ptr())
+        _lib.check(rc, "bnv_train_tcnn_forward")
+        return feats, pred
+
+    def _views(self, buf):
+        out, o = {}, 0
+        for k, shape in TCNN_SHAPES:
+            out[k] = buf[o: o + shape[0]]
+            o += shape[0]
+        return out
+
+    def parameters(self):
+        """name -> device tensor view into the flat parameter buffer (the two flat master vectors)."""
+        return self._views(self.params)
+
+    def gradients(self):
+        """name -> device tensor view of the last step's gradients."""
+        return self._views(self.grads)
+
+    def state_dict(self):
+        """The weights as numpy arrays with exactly the keys, shapes and dtypes of weights/pointnet_tcnn.npz."""
+        return {k: v.cpu().numpy().copy() for k, v in self._views(self.params).items()}
+
+    def save_npz(self, path):
+        """Writes the weights in the layout of weights/pointnet_tcnn.npz (``load_pretrained(tiny_cuda=True,
+        path=...)`` reads it)."""
+        with open(path, "wb") as fh:
+            np.savez(fh, **self.state_dict())
+
+    def save_ckpt(self, path):
+        """Writes ``{"state_dict": {the two flat vectors}}``, what the reference's LitFusionPointNet(tiny_cuda=True)
+        loads strictly (its pretrained/pointnet_tcnn.ckpt holds exactly these keys)."""
+        torch.save({"state_dict": {k: torch.from_numpy(v) for k, v in self.state_dict().items()}}, path)
+
+    def to_model(self, voxel_size=0.01, min_pts_in_grid=MIN_PTS_IN_GRID, device=None):
+        """A frozen tiny-cuda-nn LitFusionPointNet with these weights, repacked for the inference kernels."""
+        from .fusion import load_pretrained
+        return load_pretrained(device=device or self.device, voxel_size=voxel_size, min_pts_in_grid=min_pts_in_grid,
+                               tiny_cuda=True, state_dict=self.state_dict())

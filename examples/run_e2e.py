@@ -40,8 +40,8 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--voxel-size", type=float, default=0.01)
     ap.add_argument("--tiny-cuda", action="store_true", help="the reference's default tiny-cuda-nn checkpoint")
-    ap.add_argument("--weights", metavar="PATH", help="fp32 embedding weights (.npz, e.g. examples/train_embedding.py's "
-                    "last.npz) instead of the shipped checkpoint")
+    ap.add_argument("--weights", metavar="PATH", help="embedding weights (.npz, e.g. examples/train_embedding.py's "
+                    "last.npz; fp32 networks, or tiny-cuda-nn ones with --tiny-cuda) instead of the shipped checkpoint")
     ap.add_argument("--skip-images", type=int, default=1)
     ap.add_argument("--optim-interval", type=int, default=100)        # fusion_pointnet_model.yaml:48
     ap.add_argument("--mode", default="offline", choices=["demo", "offline"])

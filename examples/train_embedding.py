@@ -7,7 +7,9 @@ fusion_pointnet model (training_global=False), batch 100, Adam lr 1e-3, StepLR(2
 --data-dir: the reference's local-patch layout (<DATA>/local_shapes/{03001627,03636649}_noise/<seq>/*.pkl);
 --synthetic N: N patches of analytic shapes with exact SDF (synthetic.local_patches), a tenth more held out for
 validation.  Prints the train and val loss per epoch; writes <out>/last.npz (load_pretrained(path=...),
-run_e2e.py --weights) and <out>/last.ckpt (the reference's checkpoint layout).
+run_e2e.py --weights) and <out>/last.ckpt (the reference's checkpoint layout).  --tiny-cuda: the reference's default
+tiny-cuda-nn networks (tiny_cuda: True); the files are then in the pointnet_tcnn layout (run_e2e.py --tiny-cuda
+--weights <out>/last.npz).
 """
 import argparse
 import os
@@ -28,6 +30,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--M", type=int, default=256, help="--synthetic: training points per patch")
+    ap.add_argument("--tiny-cuda", action="store_true",
+                    help="the reference's default tiny-cuda-nn networks (TcnnEmbeddingTrainer, pointnet_tcnn layout)")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
 
@@ -40,10 +44,11 @@ def main():
     if args.init == "scratch":
         init = None
     elif args.init == "pretrained":
-        init = weights.load_npz()
+        init = weights.load_npz(weights.DEFAULT_TCNN if args.tiny_cuda else weights.DEFAULT_FP32)
     else:
         init = weights.load_npz(args.init)
-    trainer = train.EmbeddingTrainer(init, seed=args.seed, lr=args.lr, device="cuda:0")
+    cls = train.TcnnEmbeddingTrainer if args.tiny_cuda else train.EmbeddingTrainer
+    trainer = cls(init, seed=args.seed, lr=args.lr, device="cuda:0")
     rng = np.random.default_rng(args.seed)
 
     if args.synthetic:

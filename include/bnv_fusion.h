@@ -988,6 +988,52 @@ int bnv_train_eval_loss(const float* params, const float* running, const float* 
                         const float* gt, int64_t B, int32_t n, int64_t M, float* loss_out, void* workspace,
                         size_t ws_bytes, bnv_stream_t stream);
 
+/* ---- Training of the tiny-cuda-nn embedding (bnv_fusion_amd/csrc/train_tcnn.hip): the reference's default networks
+ * (tiny_cuda: True; tcnnPointNetEncoder and tcnnNeRFModel, FullyFusedMLP 64 wide, 3 hidden layers, ReLU, no bias)
+ * under LitFusionPointNet.training_step with training_global=False (local_point_fusion.py:381-460).
+ *
+ * params: f32 [bnv_train_tcnn_param_floats()] = 21,504: pointnet_backbone.model.params [10,240] (widths
+ * 16 | 64 | 64 | 64 | 16) then nerf.model.params [11,264] (32 | 64 | 64 | 64 | 16), each the row-major [out, in]
+ * matrices in layer order.  grads, adam_m, adam_v: f32 like params.  adam_step: int64 [1] on the device, the number
+ * of Adam steps taken so far (0 at the start).  input_pts f32 [B, 64, 6] (rows 0..n-1 of each patch are read),
+ * training_pts f32 [B, M, 3], gt f32 [B, M].  Shapes: B >= 1, 1 <= n <= 64, M >= 1, B M <= 2^24; anything else is
+ * BNV_ERR_INVALID_ARGUMENT.
+ *
+ * Forward, the mode-2 arithmetic of the inference kernels: the input padded with 1.0 to 16 (encoder) / 32 (decoder)
+ * columns and rounded to f16, weights rounded to f16, each layer an f16 product accumulated in fp32, ReLU after the
+ * hidden layers, each layer output rounded to f16.  Encoder over the B n points, outputs 0..7; feats_b = f16(mean over
+ * the patch's n points).  Decoder over the B M queries on [p, sin p, cos p, feats_b] (the decode path's encoding);
+ * pred = output 0.  Loss: l1 = mean |pred - gt|, reg = mean_b |feats_b|_2, loss = l1 + 0.001 reg.
+ * Backward: every f16 rounding is the identity (straight-through), sign(0) = 0, ReLU'(0) = 0; the gradient of every
+ * weight (pad columns included; output rows nothing reads -- encoder 8..15, decoder 1..15 -- exactly 0).  Precision:
+ * activations and weights are exact f16; each layer's incoming gradient is split into hi + lo f16 parts, two f16
+ * products accumulated in fp32, near fp32.  End to end, with the f16 forward's rounding decisions (a value one ulp
+ * off flips sign(pred - gt) or a ReLU), every gradient is within 5e-3 of its tensor's largest |gradient| of the
+ * float64 restatement.
+ *
+ * bnv_train_tcnn_step: forward, loss, grads (overwritten), then, unless the loss or a gradient is not finite, one
+ * Adam step (torch's formula; lr, betas, eps) on params with step number *adam_step + 1, which it stores.  loss_out
+ * f32 [4] = {loss, l1, reg, skipped}: skipped = 1 when the step was skipped (params, adam_m, adam_v and *adam_step
+ * untouched), else 0.
+ * bnv_train_tcnn_eval_loss: forward and loss only; loss_out f32 [3] = {loss, l1, reg}.
+ * bnv_train_tcnn_forward: forward only; feats f32 [B, 8], pred f32 [B, M] (f16 values).
+ * Every sum over rows (weight gradients, patch means, d feats over M, the loss) is reduced in a fixed order with no
+ * float atomics: results are bit-reproducible for a given shape.  Each entry is a fixed sequence of launches on
+ * stream: no allocation, synchronisation or host read.  Workspace: bnv_train_tcnn_workspace_bytes(B, n, M) (0 for an
+ * invalid shape); a workspace sized for n = 64 serves every n and all three entries. */
+int64_t bnv_train_tcnn_param_floats(void);
+size_t bnv_train_tcnn_workspace_bytes(int64_t B, int32_t n, int64_t M);
+int bnv_train_tcnn_step(float* params, float* grads, float* adam_m, float* adam_v, int64_t* adam_step,
+                        const float* input_pts, const float* training_pts, const float* gt, int64_t B, int32_t n,
+                        int64_t M, float lr, float beta1, float beta2, float eps, float* loss_out, void* workspace,
+                        size_t ws_bytes, bnv_stream_t stream);
+int bnv_train_tcnn_eval_loss(const float* params, const float* input_pts, const float* training_pts, const float* gt,
+                             int64_t B, int32_t n, int64_t M, float* loss_out, void* workspace, size_t ws_bytes,
+                             bnv_stream_t stream);
+int bnv_train_tcnn_forward(const float* params, const float* input_pts, const float* training_pts, int64_t B,
+                           int32_t n, int64_t M, float* feats, float* pred, void* workspace, size_t ws_bytes,
+                           bnv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
