@@ -46,13 +46,13 @@ __device__ __forceinline__ float relu_bits(float x) {
 // cvt, pack).  Bit-identical to that form, subnormals and overflow included (tools/probe_split_mix.hip).  Plain asm
 // (not volatile): the compiler still schedules and dead-code-eliminates it; its inputs come out of a v_max_i32 or a
 // plain move, so no MFMA-result hazard is hidden from it.
-typedef _Float16 bnv_half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void split_pair_f16(float a, float b, unsigned& hi, unsigned& lo) {
   asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
   asm("v_fma_mixlo_f16 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(a));
   asm("v_fma_mixhi_f16 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(b));
 }
-__device__ __forceinline__ void split8_f16(const float (&x)[8], bnv_half8& hi, bnv_half8& lo) {
+__device__ __forceinline__ void split8_f16(const float (&x)[8], half8& hi, half8& lo) {
   typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
   u32x4_t h, l;
 #pragma unroll
@@ -62,8 +62,8 @@ __device__ __forceinline__ void split8_f16(const float (&x)[8], bnv_half8& hi, b
     h[p] = hh;
     l[p] = ll;
   }
-  hi = __builtin_bit_cast(bnv_half8, h);
-  lo = __builtin_bit_cast(bnv_half8, l);
+  hi = __builtin_bit_cast(half8, h);
+  lo = __builtin_bit_cast(half8, l);
 }
 
 // Cooperative global -> LDS copy of `bytes` (a multiple of 16; src and dst 16-byte aligned) by the NT threads of a

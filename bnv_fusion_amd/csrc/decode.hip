@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "bnv_common.hpp"
+#include "tcnn_mlp.hpp"
 
 namespace bnv {
 
@@ -41,7 +42,6 @@ constexpr int SH_W2 = SH_W1 + 8 * 16 * 2 * 64 * 8;
 constexpr int SH_W3 = SH_W2 + 8 * 16 * 2 * 64 * 8;
 constexpr int SH_TOTAL = SH_W3 + 8 * 16 * 2 * 64 * 8;   // 409,600 halves
 constexpr int SD_PACK_FLOATS = SD_TOTAL + SH_TOTAL / 2;
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // weight fragment fetch through a buffer descriptor: wave-uniform base (SGPRs) + one shared per-lane
@@ -446,71 +446,20 @@ __device__ __forceinline__ void stage_input_h(float* __restrict__ lds, int j, co
 // 17 inputs padded to 32 with 1.0 -> 64 -> 64 -> 64 -> 16 (output 0 used), ReLU, no bias, fp16.
 // The network is small enough that ONE wave runs all layers for 32 evaluations in registers (no
 // barriers between layers); waves 0..3 of the workgroup cover the tile's 128 evaluations.
-// Pack (halves): W0 [2 mb][2 ks][64 lane][8] | W1, W2 [2 mb][4 g][64][8] | W3 [4 g][64][8] (rows >= 16 zero).
-constexpr int ST_W0 = 0;
-constexpr int ST_W1 = ST_W0 + 2 * 2 * 64 * 8;
-constexpr int ST_W2 = ST_W1 + 2 * 4 * 64 * 8;
-constexpr int ST_W3 = ST_W2 + 2 * 4 * 64 * 8;
-constexpr int ST_TOTAL = ST_W3 + 4 * 64 * 8;  // 12,288 halves
-static_assert(ST_TOTAL == 12288, "tcnn SDF pack size (weights.py: pack_sdf_tcnn)");
-
-__device__ __forceinline__ half8 relu_half8(const f32x16& v, int base) {
-  half8 r;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) r[e] = (_Float16)relu1(v[base + e]);
-  return r;
-}
+// Network, pack layout and wave tile: tcnn_mlp.hpp (NK0 = 2).
+typedef TcnnPack<2> SdfPack;
 
 __device__ __forceinline__ void sdf_mlp_tile_t(float* __restrict__ lds, const float* __restrict__ pack) {
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = lane & 31, h = lane >> 5;
   if (w < 4) {
-    const _Float16* ph = (const _Float16*)pack;
     const int col = w * 32 + j;
-    f32x16 a0[2], a1[2];
+    half8 x[2];
 #pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a0[mb][r] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const half8 b = *(const half8*)&lds[L_HL + ((ks * 2 + h) * DM + col) * 4];
-        a0[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&ph[ST_W0 + ((mb * 2 + ks) * 64 + lane) * 8], b,
-                                                        a0[mb], 0, 0, 0);
-      }
-    }
-    half8 s[4];
-    auto layer64 = [&](int woff, const f32x16 (&in)[2], f32x16 (&out)[2]) {
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        s[nb * 2] = relu_half8(in[nb], 0);
-        s[nb * 2 + 1] = relu_half8(in[nb], 8);
-      }
-#pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[mb][r] = 0.f;
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          out[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&ph[woff + ((mb * 4 + g) * 64 + lane) * 8],
-                                                          s[g], out[mb], 0, 0, 0);
-      }
-    };
-    layer64(ST_W1, a0, a1);
-    layer64(ST_W2, a1, a0);
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-      s[nb * 2] = relu_half8(a0[nb], 0);
-      s[nb * 2 + 1] = relu_half8(a0[nb], 8);
-    }
-    f32x16 o;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      o = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&ph[ST_W3 + (g * 64 + lane) * 8], s[g], o, 0, 0, 0);
-    // output 0 = row 0 of the tile = register 0 of the lanes with h == 0; the network returns fp16
+    for (int ks = 0; ks < 2; ++ks) x[ks] = *(const half8*)&lds[L_HL + ((ks * 2 + h) * DM + col) * 4];
+    const f32x16 o = tcnn_forward<2>((const _Float16*)pack, lane, x);
+    // output 0 = register 0 of the lanes with h == 0; the network returns fp16
     if (h == 0) lds[L_ALPHA + col] = (float)(_Float16)o[0];
   }
   __syncthreads();
@@ -520,22 +469,11 @@ __device__ __forceinline__ void sdf_mlp_tile_t(float* __restrict__ lds, const fl
 __device__ __forceinline__ void stage_input_t(float* __restrict__ lds, int j, const float (&loc)[3],
                                               const float (&feat)[8]) {
   float in[32];
-#pragma unroll
-  for (int f = 0; f < 32; ++f) in[f] = 1.0f;
-  in[0] = loc[0]; in[1] = loc[1]; in[2] = loc[2];
-  in[3] = sinf(loc[0]); in[4] = sinf(loc[1]); in[5] = sinf(loc[2]);
-  in[6] = cosf(loc[0]); in[7] = cosf(loc[1]); in[8] = cosf(loc[2]);
-#pragma unroll
-  for (int f = 0; f < 8; ++f) in[9 + f] = feat[f];
+  tcnn_sdf_inputs(loc, feat, in);
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      half8 v;
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) v[jj] = (_Float16)in[16 * ks + 8 * (jj >> 2) + 4 * hh + (jj & 3)];
-      *(half8*)&lds[L_HL + ((ks * 2 + hh) * DM + j) * 4] = v;
-    }
+    for (int hh = 0; hh < 2; ++hh) *(half8*)&lds[L_HL + ((ks * 2 + hh) * DM + j) * 4] = tcnn_input_frag(in, ks, hh);
   }
 }
 
@@ -1448,16 +1386,6 @@ constexpr int TB_W0T = TB_W1T + 2 * 4 * 64 * 8;
 constexpr int TB_W3R = TB_W0T + 4 * 64 * 8;   // 64 floats
 constexpr int TB_TOTAL = TB_W3R + 128;        // 10,368 halves = 5,184 floats
 
-__device__ __forceinline__ uint32_t positive_bits32(const f32x16 (&a)[2]) {
-  uint32_t m = 0u;
-#pragma unroll
-  for (int mb = 1; mb >= 0; --mb) {
-#pragma unroll
-    for (int r = 15; r >= 0; --r) m = (m << 1) | (uint32_t)(a[mb][r] > 0.f);
-  }
-  return m;
-}
-
 __global__ __launch_bounds__(512, 2) void k_decode_pts_bwd_t(DecodeBwdArgs B) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const DecodeArgs& A = B.d;
@@ -1486,54 +1414,18 @@ __global__ __launch_bounds__(512, 2) void k_decode_pts_bwd_t(DecodeBwdArgs B) {
       const _Float16* pb = (const _Float16*)B.bwd_pack;
       const int col = w * 32 + j;
       // ---- forward, keeping the sign bits of the three hidden pre-activations -------------------------
+      half8 x[2];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) x[ks] = *(const half8*)&lds[L_HL + ((ks * 2 + h) * DM + col) * 4];
       f32x16 a0[2], a1[2];
-#pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a0[mb][r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const half8 b = *(const half8*)&lds[L_HL + ((ks * 2 + h) * DM + col) * 4];
-          a0[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&ph[ST_W0 + ((mb * 2 + ks) * 64 + lane) * 8],
-                                                          b, a0[mb], 0, 0, 0);
-        }
-      }
       half8 s[4];
-      auto fill_relu = [&](const f32x16 (&in)[2]) {
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-          s[nb * 2] = relu_half8(in[nb], 0);
-          s[nb * 2 + 1] = relu_half8(in[nb], 8);
-        }
-      };
-      auto fill_masked = [&](const f32x16 (&in)[2], uint32_t m) {
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-#pragma unroll
-          for (int ksl = 0; ksl < 2; ++ksl) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-              s[nb * 2 + ksl][e] = (_Float16)(((m >> (nb * 16 + ksl * 8 + e)) & 1u) ? in[nb][ksl * 8 + e] : 0.f);
-          }
-        }
-      };
-      auto layer64 = [&](const _Float16* wp, f32x16 (&out)[2]) {
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) out[mb][r] = 0.f;
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            out[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wp[((mb * 4 + g) * 64 + lane) * 8], s[g],
-                                                            out[mb], 0, 0, 0);
-        }
-      };
+      tcnn_first_layer<2>(ph + SdfPack::W0, lane, x, a0);
       const uint32_t m0 = positive_bits32(a0);
-      fill_relu(a0);
-      layer64(ph + ST_W1, a1);
+      tcnn_relu_round(a0, s);
+      tcnn_hidden_layer(ph + SdfPack::W1, lane, s, a1);
       const uint32_t m1 = positive_bits32(a1);
-      fill_relu(a1);
-      layer64(ph + ST_W2, a0);
+      tcnn_relu_round(a1, s);
+      tcnn_hidden_layer(ph + SdfPack::W2, lane, s, a0);
       const uint32_t m2 = positive_bits32(a0);
       // ---- backward with a unit seed: delta_2 = W3[0, :] * [z2 > 0] ------------------------------------
       {
@@ -1548,17 +1440,23 @@ __global__ __launch_bounds__(512, 2) void k_decode_pts_bwd_t(DecodeBwdArgs B) {
           }
         }
       }
+      auto fill_masked = [&](const f32x16 (&in)[2], uint32_t m) {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+#pragma unroll
+          for (int ksl = 0; ksl < 2; ++ksl) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              s[nb * 2 + ksl][e] = (_Float16)(((m >> (nb * 16 + ksl * 8 + e)) & 1u) ? in[nb][ksl * 8 + e] : 0.f);
+          }
+        }
+      };
       fill_masked(a0, m2);
-      layer64(pb + TB_W2T, a1);
+      tcnn_hidden_layer(pb + TB_W2T, lane, s, a1);
       fill_masked(a1, m1);
-      layer64(pb + TB_W1T, a0);
+      tcnn_hidden_layer(pb + TB_W1T, lane, s, a0);
       fill_masked(a0, m0);
-      f32x16 g;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) g[r] = 0.f;
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq)
-        g = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&pb[TB_W0T + (gq * 64 + lane) * 8], s[gq], g, 0, 0, 0);
+      const f32x16 g = tcnn_output_layer(pb + TB_W0T, lane, s);
       const float sc = lds[L_ALPHA + col];
       const int row = l_row[col];
       if (sc != 0.f && row >= 0) {
@@ -2044,8 +1942,8 @@ __global__ __launch_bounds__(512, 2) void k_lattice_table_x(DecodeArgs A) {
 // order as the generic kernel: bit-identical tables (tests/test_gpu_parity.py).
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lattice_table_t(DecodeArgs A) {
-  __shared__ __attribute__((aligned(16))) _Float16 wh[ST_TOTAL];
-  stage_to_lds<256>(A.pack, wh, ST_TOTAL * 2);
+  __shared__ __attribute__((aligned(16))) _Float16 wh[SdfPack::TOTAL];
+  stage_to_lds<256>(A.pack, wh, SdfPack::TOTAL * 2);
   __syncthreads();
   const float voxel = A.grid.voxel_size;
   const int lane = threadIdx.x & 63;
@@ -2084,56 +1982,11 @@ __global__ __launch_bounds__(256) void k_lattice_table_t(DecodeArgs A) {
 #pragma unroll
       for (int f = 0; f < 17; ++f) in[f] = 0.f;      // (an empty column; its output is not written)
     }
-    // operand slot jj of K-step ks of this lane half: input 16 ks + 8 (jj >> 2) + 4 h + (jj & 3)  (stage_input_t)
     half8 b[2];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) {
-        const float lo = in[16 * ks + 8 * (jj >> 2) + (jj & 3)], hi = in[16 * ks + 8 * (jj >> 2) + 4 + (jj & 3)];
-        b[ks][jj] = (_Float16)(h ? hi : lo);
-      }
-    f32x16 a0[2], a1[2];
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a0[mb][r] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        a0[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wh[ST_W0 + ((mb * 2 + ks) * 64 + lane) * 8], b[ks],
-                                                        a0[mb], 0, 0, 0);
-    }
-    half8 s4[4];
-    auto layer64 = [&](int woff, const f32x16 (&inp)[2], f32x16 (&out)[2]) {
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        s4[nb * 2] = relu_half8(inp[nb], 0);
-        s4[nb * 2 + 1] = relu_half8(inp[nb], 8);
-      }
-#pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[mb][r] = 0.f;
-#pragma unroll
-        for (int gk = 0; gk < 4; ++gk)
-          out[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wh[woff + ((mb * 4 + gk) * 64 + lane) * 8],
-                                                          s4[gk], out[mb], 0, 0, 0);
-      }
-    };
-    layer64(ST_W1, a0, a1);
-    layer64(ST_W2, a1, a0);
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-      s4[nb * 2] = relu_half8(a0[nb], 0);
-      s4[nb * 2 + 1] = relu_half8(a0[nb], 8);
-    }
-    f32x16 o;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.f;
-#pragma unroll
-    for (int gk = 0; gk < 4; ++gk)
-      o = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wh[ST_W3 + (gk * 64 + lane) * 8], s4[gk], o, 0, 0, 0);
-    // output 0 = row 0 of the tile = register 0 of the lanes with h == 0; the network returns fp16, and
+    for (int ks = 0; ks < 2; ++ks) b[ks] = tcnn_input_frag(in, ks, h);
+    const f32x16 o = tcnn_forward<2>(wh, lane, b);
+    // output 0 = register 0 of the lanes with h == 0; the network returns fp16, and
     // half tensor * python float stays half (sparse_volume.py:813)
     if (h == 0 && ent >= 0) {
       float av = __fmul_rn((float)(_Float16)o[0], voxel);

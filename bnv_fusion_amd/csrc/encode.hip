@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "frontend.hpp"
+#include "tcnn_mlp.hpp"
 
 namespace bnv {
 
@@ -1078,8 +1079,6 @@ __global__ __launch_bounds__(512, 2) void k_pointnet_scatter(
 // f16 subnormals are kept by the MFMA) and a.b ~ ah.bh + ah.bl + al.bh on the f16 MFMA with fp32 accumulation:
 // fp32-class results at 16/3 x the fp32 MFMA rate (mode 3: ah.bh only).
 // ------------------------------------------------------------------------------------------
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 // LDS reads of the split-operand encoder go through a handful of OPAQUE 32-bit base addresses plus compile-time
 // byte offsets that fit the 16-bit immediate of ds_read_b128.  Written as plain pointer arithmetic on the 150 KB
 // weight image the compiler kept ~40 VGPRs of pre-added addresses alive across the tile loop (and spilled the
@@ -1477,37 +1476,17 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(120))) void 
 // src/models/tcnn_config.json): 6 inputs padded to 16 with 1.0 -> 64 -> 64 -> 64 -> 16 (first 8 used),
 // ReLU, no bias, fp16 weights and activations.  Here: f16 MFMA with fp32 accumulation, activations
 // rounded to f16 between layers and at the output, as the CUDA kernel stores them.
-// Pack (halves): W1 [2 mb][64 lane][8] | W2, W3 [2 mb][4 g][64][8] | W4 [4 g][64][8] (rows >= 16 zero).
+// Network, pack layout and wave tile: tcnn_mlp.hpp (NK0 = 1).
 // ------------------------------------------------------------------------------------------
-constexpr int PT_W1 = 0;
-constexpr int PT_W2 = PT_W1 + 2 * 64 * 8;
-constexpr int PT_W3 = PT_W2 + 2 * 4 * 64 * 8;
-constexpr int PT_W4 = PT_W3 + 2 * 4 * 64 * 8;
-constexpr int PT_TOTAL = PT_W4 + 4 * 64 * 8;  // 11,264 halves = 22,528 B
-
-__device__ __forceinline__ half8 to_half8_relu(const f32x16& v, int base) {
-  half8 r;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    r[e] = (_Float16)relu_bits(v[base + e]);
-  }
-  return r;
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 v;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) v[r] = 0.f;
-  return v;
-}
+typedef TcnnPack<1> PointPack;
 
 __global__ __launch_bounds__(256) void k_pointnet_scatter_t(
     const float* __restrict__ pts, int n_points, bnv_grid_t g, const float* __restrict__ wpack,
     const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ word_prefix,
     int32_t* __restrict__ counts, long long* __restrict__ acc, const int32_t* __restrict__ pair_list,
     const int32_t* __restrict__ n_pairs) {
-  __shared__ __attribute__((aligned(16))) _Float16 wh[PT_TOTAL];
-  stage_to_lds<256>(wpack, wh, PT_TOTAL * 2);
+  __shared__ __attribute__((aligned(16))) _Float16 wh[PointPack::TOTAL];
+  stage_to_lds<256>(wpack, wh, PointPack::TOTAL * 2);
   __syncthreads();
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1553,38 +1532,8 @@ __global__ __launch_bounds__(256) void k_pointnet_scatter_t(
     }
     if (__ballot(slot >= 0) == 0ULL) continue;
     (void)valid;
-    f32x16 ha[2], hb[2];
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-      ha[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wh[PT_W1 + (mb * 64 + lane) * 8], b, zero16(),
-                                                      0, 0, 0);
-    half8 s[4];
-    auto layer64 = [&](int woff, const f32x16 (&in)[2], f32x16 (&out)[2]) {
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        s[nb * 2] = to_half8_relu(in[nb], 0);
-        s[nb * 2 + 1] = to_half8_relu(in[nb], 8);
-      }
-#pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
-        out[mb] = zero16();
-#pragma unroll
-        for (int gk = 0; gk < 4; ++gk)
-          out[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wh[woff + ((mb * 4 + gk) * 64 + lane) * 8],
-                                                          s[gk], out[mb], 0, 0, 0);
-      }
-    };
-    layer64(PT_W2, ha, hb);
-    layer64(PT_W3, hb, ha);
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-      s[nb * 2] = to_half8_relu(ha[nb], 0);
-      s[nb * 2 + 1] = to_half8_relu(ha[nb], 8);
-    }
-    f32x16 o = zero16();
-#pragma unroll
-    for (int gk = 0; gk < 4; ++gk)
-      o = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wh[PT_W4 + (gk * 64 + lane) * 8], s[gk], o, 0, 0, 0);
+    const half8 x[1] = {b};
+    f32x16 o = tcnn_forward<1>(wh, lane, x);
     // the network returns fp16; lane (j, h) holds outputs 4h .. 4h+3 of pair j
 #pragma unroll
     for (int q = 0; q < 4; ++q) o[q] = (float)(_Float16)o[q];
@@ -1628,7 +1577,7 @@ __global__ __launch_bounds__(64 * kTbWaves) void k_pointnet_scatter_tb(
     const float* __restrict__ pts, int n_points, int frame_w, bnv_grid_t g, const float* __restrict__ wpack,
     const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ word_prefix, int32_t* __restrict__ counts,
     long long* __restrict__ acc) {
-  __shared__ __attribute__((aligned(16))) _Float16 wh[PT_TOTAL];
+  __shared__ __attribute__((aligned(16))) _Float16 wh[PointPack::TOTAL];
   __shared__ WgAcc T;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1641,7 +1590,7 @@ __global__ __launch_bounds__(64 * kTbWaves) void k_pointnet_scatter_tb(
   T.cnt[threadIdx.x] = 0;
 #pragma unroll
   for (int f = 0; f < 8; ++f) T.sum[threadIdx.x][f] = 0ull;
-  stage_to_lds<64 * kTbWaves>(wpack, wh, PT_TOTAL * 2);
+  stage_to_lds<64 * kTbWaves>(wpack, wh, PointPack::TOTAL * 2);
   __syncthreads();
   const int j = lane & 31, h = lane >> 5;
   const int nyz = g.n_xyz[1] * g.n_xyz[2];
@@ -1743,38 +1692,8 @@ __global__ __launch_bounds__(64 * kTbWaves) void k_pointnet_scatter_tb(
           bop[1] = hn2;
         }
       }
-      f32x16 ha[2], hb[2];
-#pragma unroll
-      for (int mb = 0; mb < 2; ++mb)
-        ha[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wh[PT_W1 + (mb * 64 + lane) * 8], bop, zero16(),
-                                                        0, 0, 0);
-      half8 s4[4];
-      auto layer64 = [&](int woff, const f32x16 (&in)[2], f32x16 (&out)[2]) {
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-          s4[nb * 2] = to_half8_relu(in[nb], 0);
-          s4[nb * 2 + 1] = to_half8_relu(in[nb], 8);
-        }
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-          out[mb] = zero16();
-#pragma unroll
-          for (int gk = 0; gk < 4; ++gk)
-            out[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wh[woff + ((mb * 4 + gk) * 64 + lane) * 8],
-                                                            s4[gk], out[mb], 0, 0, 0);
-        }
-      };
-      layer64(PT_W2, ha, hb);
-      layer64(PT_W3, hb, ha);
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        s4[nb * 2] = to_half8_relu(ha[nb], 0);
-        s4[nb * 2 + 1] = to_half8_relu(ha[nb], 8);
-      }
-      f32x16 o = zero16();
-#pragma unroll
-      for (int gk = 0; gk < 4; ++gk)
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const half8*)&wh[PT_W4 + (gk * 64 + lane) * 8], s4[gk], o, 0, 0, 0);
+      const half8 x[1] = {bop};
+      f32x16 o = tcnn_forward<1>(wh, lane, x);
       // the network returns fp16; lane (j, h) holds outputs 4h .. 4h+3 of pair j
 #pragma unroll
       for (int q = 0; q < 4; ++q) o[q] = (float)(_Float16)o[q];

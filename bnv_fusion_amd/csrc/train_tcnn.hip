@@ -8,8 +8,8 @@
 // (11,264).  The input is padded with 1.0 to 16 / 32 columns (the pad columns act as biases).
 //
 // Forward = the mode-2 arithmetic of the inference kernels (encode.hip k_pointnet_scatter_tb, decode.hip
-// sdf_mlp_tile_t): inputs and weights rounded to f16, every layer an f16 MFMA with fp32 accumulation, ReLU after
-// the hidden layers, every layer output rounded to f16.
+// sdf_mlp_tile_t), from the same code (tcnn_mlp.hpp): inputs and weights rounded to f16, every layer an f16 MFMA with
+// fp32 accumulation, ReLU after the hidden layers, every layer output rounded to f16.
 //
 // Backward: every f16 rounding counts as the identity (straight-through).  The activations and weights are exact
 // f16 values; the incoming gradient of each layer is split into hi + lo f16 parts (hi = rn16(g), lo = rn16(g - hi)),
@@ -29,7 +29,7 @@
 //   -> k_tcnn_tile<enc, train> (forward RECOMPUTED, backward) -> k_tcnn_dw + k_tcnn_sum (encoder dW)
 //   -> k_tcnn_loss (loss terms, finite check, device-side Adam step count) -> k_tcnn_adam.
 // One wave runs all layers of a 32-row tile with the activations in registers (32x32x16 f16 MFMA; the layer output
-// tile feeds the next MFMA as its B operand with no data movement, decode.hip sdf_mlp_tile_t).  Weight fragments
+// tile feeds the next MFMA as its B operand with no data movement, tcnn_mlp.hpp).  Weight fragments
 // are read from the f16 images in global memory (45 KB per network, cache-resident), as the inference decoder does.
 // Every sum over rows -- weight gradients (per-chunk partials summed in chunk order), patch means, d feats over M,
 // the loss -- runs in a fixed order with no float atomics: a run is bit-reproducible for a given shape.
@@ -39,11 +39,10 @@
 #include <math.h>
 
 #include "bnv_common.hpp"
+#include "tcnn_mlp.hpp"
 
 namespace bnv {
 namespace train_tcnn {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 constexpr int kMaxN = 64, kF = 8, kW = 64;
 constexpr int64_t kEncParams = 16 * 64 + 64 * 64 * 2 + 64 * 16;   // 10,240
@@ -52,13 +51,12 @@ constexpr int64_t kParams = kEncParams + kDecParams;
 constexpr float kW_L1 = 1.0f, kW_Reg = 0.001f;                   // fusion_pointnet_model.yaml:36-38
 constexpr int kMaxChunks = 64;                                   // row chunks of the weight-gradient partials
 
-// fragment images (halves): forward [layer][mb][k-step][64 lanes][8], transposed the same with the roles swapped
+// fragment images (halves): forward = the inference pack (tcnn_mlp.hpp: TcnnPack), transposed the same with the roles
+// swapped
 __host__ __device__ constexpr int fwd_halves(int nk0) { return 128 * 8 * nk0 + 1280 * 8; }
+static_assert(fwd_halves(1) == TcnnPack<1>::TOTAL && fwd_halves(2) == TcnnPack<2>::TOTAL,
+              "the forward image is the inference pack");
 constexpr int kBwdHalves = 1408 * 8;   // W3^T [2][1] | W2^T [2][4] | W1^T [2][4] | W0^T [1][4]
-
-// operand slot jj of lane half h holds feature 8 (jj >> 2) + 4 h + (jj & 3) of a 16-deep K-step: the row order of
-// a 32x32 MFMA result's registers, so a layer's output feeds the next layer unmoved (weights.py: _slot_feature)
-__host__ __device__ constexpr int sf(int jj, int h) { return 8 * (jj >> 2) + 4 * h + (jj & 3); }
 
 __device__ __forceinline__ int layer_in(int l, int nin0) { return l == 0 ? nin0 : kW; }
 __device__ __forceinline__ int layer_out(int l) { return l == 3 ? 16 : kW; }
@@ -95,9 +93,9 @@ __global__ void k_tcnn_pack(const float* __restrict__ params, _Float16* __restri
   const int q = e - base, jj = q & 7, lane = (q >> 3) & 63, rest = q >> 9;
   const int g = rest % ng, mb = rest / ng, r = lane & 31, h = lane >> 5;
   const int I = layer_in(l, nin0), O = layer_out(l);
-  // forward: A[o = 32 mb + r][k = 16 g + sf];  transposed: A[i = 32 mb + r][k = o = 16 g + sf]
-  const int o = transposed ? 16 * g + sf(jj, h) : 32 * mb + r;
-  const int i = transposed ? 32 * mb + r : 16 * g + sf(jj, h);
+  // forward: A[o = 32 mb + r][k = 16 g + slot feature];  transposed: A[i = 32 mb + r][k = o = 16 g + slot feature]
+  const int o = transposed ? 16 * g + tcnn_slot_feature(jj, h) : 32 * mb + r;
+  const int i = transposed ? 32 * mb + r : 16 * g + tcnn_slot_feature(jj, h);
   const float v = (o < O && i < I) ? W[layer_poff(l, nin0) + (int64_t)o * I + i] : 0.0f;
   out[idx] = (_Float16)v;
 }
@@ -122,23 +120,16 @@ struct TileArgs {
   _Float16* Zl[4];           //                          lo part
 };
 
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) z[r] = 0.0f;
-  return z;
-}
 __device__ __forceinline__ half8 frag(const _Float16* img, int idx8) {
   return *reinterpret_cast<const half8*>(img + (int64_t)idx8 * 8);
 }
-__device__ __forceinline__ f32x16 mfma(half8 a, half8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-// ReLU + f16 of registers base .. base + 7 of an accumulator (the activation of K-step 2 nb + base / 8)
-__device__ __forceinline__ half8 relu_half8(const f32x16& v, int base) {
+// The trainer's one departure from the inference tile (tcnn_mlp.hpp: relu_half8, which drops a NaN whose sign bit is
+// set): the same bits for every number, but NaN stays NaN, so that a forward that overflowed f16 (inf - inf in the
+// next layer) reaches the loss and the step is skipped.
+__device__ __forceinline__ half8 relu_half8_keep_nan(const f32x16& v, int base) {
   half8 r;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) r[e] = (_Float16)(!(v[base + e] <= 0.0f) ? v[base + e] : 0.0f);   // NaN stays NaN
+  for (int e = 0; e < 8; ++e) r[e] = (_Float16)(!(v[base + e] <= 0.0f) ? v[base + e] : 0.0f);
   return r;
 }
 __device__ __forceinline__ void split_half8(const f32x16& v, int base, half8& hi, half8& lo) {
@@ -149,24 +140,16 @@ __device__ __forceinline__ void split_half8(const f32x16& v, int base, half8& hi
     lo[e] = (_Float16)(v[base + e] - (float)t);
   }
 }
-__device__ __forceinline__ uint32_t relu_mask(const f32x16 (&a)[2]) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) m |= (a[mb][r] > 0.0f ? 1u : 0u) << (mb * 16 + r);
-  return m;
-}
 __device__ __forceinline__ void apply_mask(f32x16 (&d)[2], uint32_t m) {
 #pragma unroll
   for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
     for (int r = 0; r < 16; ++r) d[mb][r] = ((m >> (mb * 16 + r)) & 1u) ? d[mb][r] : 0.0f;
 }
-// image [tile][F][32]: feature 16 g + sf(jj, h) of row j
+// image [tile][F][32]: feature 16 g + tcnn_slot_feature(jj, h) of row j
 __device__ __forceinline__ void store_frag(_Float16* img, int64_t tile, int F, int g, int j, int h, half8 v) {
 #pragma unroll
-  for (int jj = 0; jj < 8; ++jj) img[((tile * F) + 16 * g + sf(jj, h)) * 32 + j] = v[jj];
+  for (int jj = 0; jj < 8; ++jj) img[((tile * F) + 16 * g + tcnn_slot_feature(jj, h)) * 32 + j] = v[jj];
 }
 
 // NET 0: encoder, 1: decoder.  TRAIN 0: forward (encoder: point outputs; decoder: pred / loss partials), 1: forward
@@ -184,68 +167,48 @@ __global__ __launch_bounds__(256) void k_tcnn_tile(TileArgs a) {
 #pragma unroll
   for (int f = 0; f < NIN; ++f) in[f] = valid ? 1.0f : 0.0f;   // rows past R: all zero, so they add nothing
   if (valid) {
-    if (NET == 0) {
+    if constexpr (NET == 0) {
       b = row / a.n;
       const float* src = a.input_pts + (b * kMaxN + (row - b * a.n)) * 6;
 #pragma unroll
       for (int c = 0; c < 6; ++c) in[c] = src[c];
     } else {
-      // [p, sin p, cos p, feat]: the expressions of decode.hip stage_input_t, so a (point, feature) pair gives the
-      // bits NeuralMap's mode-2 decode gives
+      // the encoding NeuralMap's mode-2 decode stages (decode.hip: stage_input_t)
       b = row / a.M;
       const float* p = a.xyz + row * 3;
       const float loc[3] = {p[0], p[1], p[2]};
-      in[0] = loc[0]; in[1] = loc[1]; in[2] = loc[2];
-      in[3] = sinf(loc[0]); in[4] = sinf(loc[1]); in[5] = sinf(loc[2]);
-      in[6] = cosf(loc[0]); in[7] = cosf(loc[1]); in[8] = cosf(loc[2]);
+      float feat[kF];
 #pragma unroll
-      for (int c = 0; c < kF; ++c) in[9 + c] = a.feats[b * kF + c];
+      for (int c = 0; c < kF; ++c) feat[c] = a.feats[b * kF + c];
+      tcnn_sdf_inputs(loc, feat, in);
     }
   }
   half8 xin[NK0];
 #pragma unroll
-  for (int ks = 0; ks < NK0; ++ks)
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) xin[ks][jj] = (_Float16)(h ? in[16 * ks + sf(jj, 1)] : in[16 * ks + sf(jj, 0)]);
+  for (int ks = 0; ks < NK0; ++ks) xin[ks] = tcnn_input_frag(in, ks, h);
 
-  // ---- forward ----
-  constexpr int F1 = 128 * NK0, F2 = F1 + 512, F3 = F2 + 512;   // layer offsets in the image, in fragments
+  // ---- forward: the layers of tcnn_mlp.hpp; between them the ReLU masks and (TRAIN) the layer inputs are kept ----
+  typedef TcnnPack<NK0> P;
   f32x16 acc[2];
-#pragma unroll
-  for (int mb = 0; mb < 2; ++mb) {
-    acc[mb] = zero16();
-#pragma unroll
-    for (int ks = 0; ks < NK0; ++ks) acc[mb] = mfma(frag(a.wf, (mb * NK0 + ks) * 64 + lane), xin[ks], acc[mb]);
-  }
+  tcnn_first_layer<NK0>(a.wf + P::W0, lane, xin, acc);
   if (TRAIN) {
 #pragma unroll
     for (int ks = 0; ks < NK0; ++ks) store_frag(a.X[0], tile, NIN, ks, j, h, xin[ks]);
   }
   uint32_t mask[3];
   half8 s[4];
-  f32x16 o = zero16();
 #pragma unroll
   for (int l = 1; l <= 3; ++l) {
-    mask[l - 1] = relu_mask(acc);
+    mask[l - 1] = positive_bits32(acc);
 #pragma unroll
-    for (int g = 0; g < 4; ++g) s[g] = relu_half8(acc[g >> 1], 8 * (g & 1));
+    for (int g = 0; g < 4; ++g) s[g] = relu_half8_keep_nan(acc[g >> 1], 8 * (g & 1));
     if (TRAIN) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) store_frag(a.X[l], tile, kW, g, j, h, s[g]);
     }
-    if (l < 3) {
-      const int off = l == 1 ? F1 : F2;
-#pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
-        acc[mb] = zero16();
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc[mb] = mfma(frag(a.wf, off + (mb * 4 + g) * 64 + lane), s[g], acc[mb]);
-      }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) o = mfma(frag(a.wf, F3 + g * 64 + lane), s[g], o);
-    }
+    if (l < 3) tcnn_hidden_layer(a.wf + (l == 1 ? P::W1 : P::W2), lane, s, acc);
   }
+  const f32x16 o = tcnn_output_layer(a.wf + P::W3, lane, s);
   // output rows 4 h + r (r < 4) and 8 + 4 h + r (r = 4 .. 7) of row j; the networks return f16
   float sg = 0.0f;
   if (NET == 0) {
@@ -292,8 +255,8 @@ __global__ __launch_bounds__(256) void k_tcnn_tile(TileArgs a) {
 #pragma unroll
   for (int mb = 0; mb < 2; ++mb) {
     const half8 w = frag(a.wt, mb * 64 + lane);
-    d[mb] = mfma(w, dl, zero16());
-    d[mb] = mfma(w, dh, d[mb]);
+    d[mb] = mfma_f16(w, dl, zero16());
+    d[mb] = mfma_f16(w, dh, d[mb]);
   }
   apply_mask(d, mask[2]);
 #pragma unroll
@@ -313,8 +276,8 @@ __global__ __launch_bounds__(256) void k_tcnn_tile(TileArgs a) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const half8 w = frag(a.wt, off + (mb * 4 + g) * 64 + lane);
-          d[mb] = mfma(w, zl[g], d[mb]);
-          d[mb] = mfma(w, zh[g], d[mb]);
+          d[mb] = mfma_f16(w, zl[g], d[mb]);
+          d[mb] = mfma_f16(w, zh[g], d[mb]);
         }
       }
       apply_mask(d, mask[l - 1]);
@@ -324,8 +287,8 @@ __global__ __launch_bounds__(256) void k_tcnn_tile(TileArgs a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const half8 w = frag(a.wt, T0 + g * 64 + lane);
-        x = mfma(w, zl[g], x);
-        x = mfma(w, zh[g], x);
+        x = mfma_f16(w, zl[g], x);
+        x = mfma_f16(w, zh[g], x);
       }
       if (valid) {
         float* dst = a.dfrows + row * kF;
@@ -400,8 +363,8 @@ __global__ __launch_bounds__(64) void k_tcnn_dw(DwArgs a) {
       const half8 ah = ok_o ? *reinterpret_cast<const half8*>(zh + (t * O + o) * 32 + ko) : zero;
       const half8 al = ok_o ? *reinterpret_cast<const half8*>(zl + (t * O + o) * 32 + ko) : zero;
       const half8 bx = ok_i ? *reinterpret_cast<const half8*>(x + (t * I + i) * 32 + ko) : zero;
-      acc = mfma(al, bx, acc);
-      acc = mfma(ah, bx, acc);
+      acc = mfma_f16(al, bx, acc);
+      acc = mfma_f16(ah, bx, acc);
     }
   }
   float* dst = a.part + chunk * a.P + a.poff[l];

@@ -304,12 +304,12 @@ def _pack_tcnn(mats):
 
 
 def pack_pointnet_tcnn(params):
-    """tcnnPointNetEncoder (pointnet_utils.py:269-294): 16 | 64 | 64 | 64 | 16 -> PT_* layout of csrc/encode.hip."""
+    """tcnnPointNetEncoder (pointnet_utils.py:269-294): 16 | 64 | 64 | 64 | 16 -> TcnnPack<1> of csrc/tcnn_mlp.hpp."""
     return _pack_tcnn(_split_tcnn(params, 16))
 
 
 def pack_sdf_tcnn(params):
-    """tcnnNeRFModel (modules.py:136-253): 32 | 64 | 64 | 64 | 16 -> ST_* layout of csrc/decode.hip."""
+    """tcnnNeRFModel (modules.py:136-253): 32 | 64 | 64 | 64 | 16 -> TcnnPack<2> of csrc/tcnn_mlp.hpp."""
     return _pack_tcnn(_split_tcnn(params, 32))
 
 

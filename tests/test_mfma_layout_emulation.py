@@ -407,6 +407,7 @@ def test_pointnet_x_pack_matches_direct_mlp():
 
 # ---------------------------------------------------------------------------------------------
 # tcnn (FullyFusedMLP) layouts: f16 operands only, activations rounded to f16 between layers
+# (the wave tile and its pack layout: csrc/tcnn_mlp.hpp)
 # ---------------------------------------------------------------------------------------------
 def _emulate_tcnn(halves, first_nks, x_padded, n_out_rows):
     """x_padded [32 evals, 16 * first_nks] -> network outputs [32, n_out_rows] with the kernels' index math."""
