@@ -41,6 +41,7 @@ SYMBOLS = [
     "bnv_train_eval_loss",
     "bnv_train_tcnn_param_floats", "bnv_train_tcnn_workspace_bytes", "bnv_train_tcnn_step", "bnv_train_tcnn_eval_loss",
     "bnv_train_tcnn_forward",
+    "bnv_mesh_sdf_workspace_bytes", "bnv_mesh_sdf_build", "bnv_mesh_sdf_query",
 ]
 
 
@@ -302,6 +303,9 @@ def load():
                                           C.c_float, C.c_float, vp, vp, sz, vp]),
         "bnv_train_tcnn_eval_loss": (C.c_int, [vp, vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
         "bnv_train_tcnn_forward": (C.c_int, [vp, vp, vp, i64, i32, i64, vp, vp, vp, sz, vp]),
+        "bnv_mesh_sdf_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+        "bnv_mesh_sdf_build": (C.c_int, [vp, i64, vp, i64, vp, i64, vp]),
+        "bnv_mesh_sdf_query": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

@@ -1,0 +1,749 @@
+// Exact signed distance from arbitrary points to a triangle mesh: the ground truth of embedding-training patches cut
+// from a user's meshes (bnv_fusion_amd/patches.py) and a public query of its own (evaluate.MeshSDF).  The reference
+// has no counterpart: its patches (<data_dir>/local_shapes/*_noise) were made by a program that is not part of it.
+//
+// Index (bnv_mesh_sdf_build, all in the caller's workspace): per face the three vertices gathered next to each other,
+// angle-weighted vertex pseudonormals and edge pseudonormals (Baerentzen & Aanaes 2005) as 64-bit fixed-point sums,
+// the number of faces on every edge (1: boundary, > 2: non-manifold), and two uniform grids of triangle ids (count /
+// scan / fill), the second with cells four times larger for queries far from the mesh.  Query (bnv_mesh_sdf_query):
+// one thread per query walks the fine grid ring by ring, then the coarse one, until a lower bound on the distance to
+// every unvisited cell exceeds the best distance; the closest point on a triangle is the seven-region case analysis
+// in fp32 (one rounding per operation: -ffp-contract=off), the sign is that of (query - closest) . pseudonormal of the
+// closest feature, taken in float64.  Results are bitwise reproducible: no float atomic feeds a result (the sums are
+// integer), and a tie in d^2 goes to the lowest face index, so the order the grid's integer atomics give the
+// triangles inside a cell does not matter.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/bnv_fusion.h"
+#include "bnv_common.hpp"
+
+namespace bnv {
+namespace {
+
+constexpr int kLevels = 24;               // candidate cell sizes h0 * kLadder^l; the last one is a single cell
+constexpr double kLadder = 1.5;
+constexpr double kCellTarget = 2.0;       // h0 = sqrt(kCellTarget * S / n_faces), S = half the bounding box's surface
+constexpr int64_t kCellsPerFace = 8;      // the grid has at most kCellsPerFace * n_faces + 64 cells
+constexpr int64_t kPairsPerFace = 8;      // ... and at most kPairsPerFace * n_faces + 64 (triangle, cell) pairs
+constexpr int kFineRings = 4;             // rings of the fine grid before a query moves on to the coarse grid
+constexpr int kCoarseShift = 2;           // coarse cell = fine cell >> 2 on every axis
+constexpr double kStopSlack = 1e-5;       // relative slack of the stop test on the distance
+constexpr double kNormalScale = 1099511627776.0;   // 2^40: fixed point of the pseudonormal sums
+constexpr unsigned long long kNoEdge = ~0ull;
+constexpr uint32_t kMagic = 0x4653444du;
+constexpr int kScanThreads = 256, kScanItems = 4, kScanTile = kScanThreads * kScanItems;
+constexpr int64_t kMaxFaces = 1 << 27, kMaxVertices = INT32_MAX;
+
+struct Level {
+  double h, inv_h;
+  int32_t dims[3];
+  int32_t pad;
+};
+
+struct Header {
+  uint32_t bmin[3], bmax[3];   // order-preserving encodings of the finite vertices' bounding box (first: memset)
+  unsigned long long tests;    // byte 24: triangle tests of all queries since the build (BNV_MESHSDF_COUNT_TESTS builds
+                               // only; tools/mesh_sdf_bench.py reads it)
+  uint32_t magic, pad0;
+  int64_t n_vertices, n_faces, bytes;
+  double lo[3], fmin[3], fmax[3];
+  Level level[kLevels];
+  unsigned long long pairs[kLevels];   // (triangle, cell) pairs the grid of every level would hold
+  int32_t chosen, pad1;
+  int32_t n_cells[2];                  // fine, coarse; 0: no valid triangle
+  int32_t dims[2][3];
+  double h, inv_h;                     // the fine grid's
+  double eps_abs;                      // absolute slack of the stop test: 8 ulp of the largest coordinate
+};
+static_assert(offsetof(Header, tests) == 24, "tools/mesh_sdf_bench.py reads the counter at byte 24");
+
+struct Ws {
+  Header* H;
+  float4* tri;                 // [3 F]: (vertex k, bitcast(vertex index)); index -1: a skipped face
+  long long* vacc;             // [3 V] angle-weighted normal sums, fixed point
+  uint32_t* vflag;             // [V] 0x10 boundary, 0x20 non-manifold
+  unsigned long long* ekey;    // [ecap] (lo vertex << 32) | hi vertex, kNoEdge: empty
+  long long* eacc;             // [3 ecap] sums of the incident unit face normals, fixed point
+  uint32_t* ecnt;              // [ecap] incident faces
+  uint32_t* count[2];          // [cellcap + 2]
+  uint32_t* start[2];          // [cellcap + 2]
+  uint32_t* ids[2];            // [paircap]
+  uint64_t* scan_state;        // [2 tiles]
+  uint32_t ecap;
+  int64_t cellcap, paircap, tiles;
+};
+
+__host__ __device__ inline size_t msdf_layout(int64_t nv, int64_t nf, char* base, Ws* w) {
+  uint32_t ecap = 64;
+  while ((int64_t)ecap < 4 * nf) ecap <<= 1;
+  const int64_t cellcap = kCellsPerFace * nf + 64, paircap = kPairsPerFace * nf + 64;
+  const int64_t n_bins = cellcap + 2, tiles = (n_bins + kScanTile - 1) / kScanTile;
+  size_t off = 0;
+  size_t o[14];
+  const size_t bytes[14] = {sizeof(Header), (size_t)nf * 48, (size_t)nv * 24, (size_t)nv * 4, (size_t)ecap * 8,
+                            (size_t)ecap * 24, (size_t)ecap * 4, (size_t)n_bins * 4, (size_t)n_bins * 4,
+                            (size_t)n_bins * 4, (size_t)n_bins * 4, (size_t)paircap * 4, (size_t)paircap * 4,
+                            (size_t)tiles * 2 * 8};
+  for (int k = 0; k < 14; ++k) {
+    o[k] = off;
+    off += (bytes[k] + 255) / 256 * 256;
+  }
+  if (w) {
+    w->H = (Header*)(base + o[0]);
+    w->tri = (float4*)(base + o[1]);
+    w->vacc = (long long*)(base + o[2]);
+    w->vflag = (uint32_t*)(base + o[3]);
+    w->ekey = (unsigned long long*)(base + o[4]);
+    w->eacc = (long long*)(base + o[5]);
+    w->ecnt = (uint32_t*)(base + o[6]);
+    w->count[0] = (uint32_t*)(base + o[7]);
+    w->start[0] = (uint32_t*)(base + o[8]);
+    w->count[1] = (uint32_t*)(base + o[9]);
+    w->start[1] = (uint32_t*)(base + o[10]);
+    w->ids[0] = (uint32_t*)(base + o[11]);
+    w->ids[1] = (uint32_t*)(base + o[12]);
+    w->scan_state = (uint64_t*)(base + o[13]);
+    w->ecap = ecap;
+    w->cellcap = cellcap;
+    w->paircap = paircap;
+    w->tiles = tiles;
+  }
+  return off;
+}
+
+__device__ __forceinline__ uint32_t f2ord(float x) {   // order-preserving float -> uint32
+  const uint32_t b = __builtin_bit_cast(uint32_t, x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t k) {
+  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+__device__ __forceinline__ int cell_axis(float x, double lo, double inv_h, int dim) {
+  double t = floor(((double)x - lo) * inv_h);
+  t = fmin(fmax(t, 0.0), (double)(dim - 1));
+  return (int)t;
+}
+
+__device__ __forceinline__ uint32_t edge_slot0(unsigned long long key, uint32_t ecap) { return mix64(key) & (ecap - 1); }
+__device__ __forceinline__ unsigned long long edge_key(int32_t a, int32_t b) {
+  const uint32_t lo = (uint32_t)min(a, b), hi = (uint32_t)max(a, b);
+  return ((unsigned long long)lo << 32) | hi;
+}
+
+// =====================================================================================================================
+// Index build
+// =====================================================================================================================
+// bounding box of the finite vertices (eval.hip's k_nn_bbox: wave reduction, LDS, one integer atomic per block)
+__global__ __launch_bounds__(256) void k_msdf_bbox(const float* __restrict__ V, int64_t n, Header* __restrict__ H) {
+  uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float x = V[i * 3], y = V[i * 3 + 1], z = V[i * 3 + 2];
+    if (!finite3(x, y, z)) continue;
+    const uint32_t k[3] = {f2ord(x), f2ord(y), f2ord(z)};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      mn[d] = min(mn[d], k[d]);
+      mx[d] = max(mx[d], k[d]);
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+      mn[d] = min(mn[d], (uint32_t)__shfl_xor((int)mn[d], s, 64));
+      mx[d] = max(mx[d], (uint32_t)__shfl_xor((int)mx[d], s, 64));
+    }
+  __shared__ uint32_t s_mn[4][3], s_mx[4][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0)
+    for (int d = 0; d < 3; ++d) {
+      s_mn[wave][d] = mn[d];
+      s_mx[wave][d] = mx[d];
+    }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int d = threadIdx.x;
+    uint32_t a = s_mn[0][d], b = s_mx[0][d];
+    for (int w = 1; w < 4; ++w) {
+      a = min(a, s_mn[w][d]);
+      b = max(b, s_mx[w][d]);
+    }
+    atomicMin(&H->bmin[d], a);
+    atomicMax(&H->bmax[d], b);
+  }
+}
+
+// The ladder of candidate grids over the bounding box.  Which level is used is decided once the (triangle, cell) pairs
+// of every level are counted (k_msdf_pick): the workspace is a function of the two counts alone, so the grid adapts to
+// it, not the other way round.
+__global__ void k_msdf_levels(Header* __restrict__ H, int64_t n_vertices, int64_t n_faces, int64_t bytes) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  H->n_vertices = n_vertices;
+  H->n_faces = n_faces;
+  H->bytes = bytes;
+  double L[3] = {0.0, 0.0, 0.0};
+  if (H->bmin[0] <= H->bmax[0]) {
+    for (int d = 0; d < 3; ++d) {
+      H->fmin[d] = H->lo[d] = (double)ord2f(H->bmin[d]);
+      H->fmax[d] = (double)ord2f(H->bmax[d]);
+      L[d] = H->fmax[d] - H->fmin[d];
+    }
+  }
+  const double n = (double)n_faces;
+  const double S = L[0] * L[1] + L[1] * L[2] + L[2] * L[0];
+  const double Lmax = fmax(L[0], fmax(L[1], L[2]));
+  double h = S > 0.0 ? sqrt(kCellTarget * S / n) : (Lmax > 0.0 ? kCellTarget * Lmax / n : 1.0);
+  if (!(h > 0.0) || !isfinite(h)) h = Lmax > 0.0 && isfinite(Lmax) ? Lmax : 1.0;
+  for (int l = 0; l < kLevels; ++l) {
+    if (l == kLevels - 1) h = fmax(h, 2.0 * Lmax + 1.0);   // one cell
+    H->level[l].h = h;
+    H->level[l].inv_h = 1.0 / h;
+    for (int d = 0; d < 3; ++d) H->level[l].dims[d] = (int32_t)fmin(floor(L[d] / h) + 1.0, 2147483647.0);
+    h *= kLadder;
+  }
+  double amax = 0.0;
+  for (int d = 0; d < 3; ++d) amax = fmax(amax, fmax(fabs(H->fmin[d]), fabs(H->fmax[d])));
+  H->eps_abs = 8.0 * 1.1920928955078125e-07 * amax;
+}
+
+// fixed-point add of a float64 vector (integer atomics: any order of the adds gives the same sum)
+__device__ __forceinline__ void fixed_add3(long long* __restrict__ acc, const double v[3], double w) {
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+    atomicAdd((unsigned long long*)&acc[d], (unsigned long long)__double2ll_rn(v[d] * w * kNormalScale));
+}
+
+// Per face: validity (k_face_area_prefix's rule: fp32 area 0.5 |e1 x e2| positive and finite, indices in range), the
+// gathered vertices, the pseudonormal sums of its three vertices (weight: the face's angle there) and three edges
+// (weight 1), and the number of cells its bounding box overlaps on every level of the ladder.
+__global__ __launch_bounds__(256) void k_msdf_faces(const float* __restrict__ V, int64_t n_vertices,
+                                                    const int32_t* __restrict__ Fc, int64_t n_faces, Ws W) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  Header* __restrict__ H = W.H;
+  bool valid = false;
+  float p[3][3];
+  double P[3][3], nrm[3];
+  int32_t idx[3] = {-1, -1, -1};
+  if (f < n_faces) {
+    idx[0] = Fc[f * 3];
+    idx[1] = Fc[f * 3 + 1];
+    idx[2] = Fc[f * 3 + 2];
+    valid = idx[0] >= 0 && idx[1] >= 0 && idx[2] >= 0 && idx[0] < n_vertices && idx[1] < n_vertices &&
+            idx[2] < n_vertices;
+    if (valid) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          p[k][d] = V[(int64_t)idx[k] * 3 + d];
+          P[k][d] = (double)p[k][d];
+        }
+      float e1[3], e2[3], c[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        e1[d] = p[1][d] - p[0][d];
+        e2[d] = p[2][d] - p[0][d];
+      }
+      c[0] = e1[1] * e2[2] - e1[2] * e2[1];
+      c[1] = e1[2] * e2[0] - e1[0] * e2[2];
+      c[2] = e1[0] * e2[1] - e1[1] * e2[0];
+      const float len = (float)sqrt((double)((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]));
+      const float af = 0.5f * len;
+      // the unit normal in float64 from the fp32 positions; a face whose fp32 area is rounding noise over an exactly
+      // zero cross product has no normal and is skipped as well
+      double a[3], b[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        a[d] = P[1][d] - P[0][d];
+        b[d] = P[2][d] - P[0][d];
+      }
+      nrm[0] = a[1] * b[2] - a[2] * b[1];
+      nrm[1] = a[2] * b[0] - a[0] * b[2];
+      nrm[2] = a[0] * b[1] - a[1] * b[0];
+      const double l = sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+      valid = af > 0.0f && af <= 3.4028234663852886e38f && l > 0.0;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) nrm[d] /= l;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      W.tri[f * 3 + k] = valid ? make_float4(p[k][0], p[k][1], p[k][2], __builtin_bit_cast(float, idx[k]))
+                               : make_float4(0.f, 0.f, 0.f, __builtin_bit_cast(float, (int32_t)-1));
+  }
+  if (valid) {
+    for (int k = 0; k < 3; ++k) {
+      const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+      double a[3], b[3], x[3];
+      for (int d = 0; d < 3; ++d) {
+        a[d] = P[k1][d] - P[k][d];
+        b[d] = P[k2][d] - P[k][d];
+      }
+      x[0] = a[1] * b[2] - a[2] * b[1];
+      x[1] = a[2] * b[0] - a[0] * b[2];
+      x[2] = a[0] * b[1] - a[1] * b[0];
+      const double angle = atan2(sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]), a[0] * b[0] + a[1] * b[1] + a[2] * b[2]);
+      fixed_add3(&W.vacc[(int64_t)idx[k] * 3], nrm, angle);
+      // the edge (k, k1)
+      const unsigned long long key = edge_key(idx[k], idx[k1]);
+      uint32_t s = edge_slot0(key, W.ecap);
+      for (uint32_t probe = 0; probe < W.ecap; ++probe) {
+        const unsigned long long prev = atomicCAS(&W.ekey[s], kNoEdge, key);
+        if (prev == kNoEdge || prev == key) {
+          fixed_add3(&W.eacc[(int64_t)s * 3], nrm, 1.0);
+          atomicAdd(&W.ecnt[s], 1u);
+          break;
+        }
+        s = (s + 1) & (W.ecap - 1);
+      }
+    }
+  }
+  // cells the bounding box overlaps on every level, summed over the wave (every lane of the block arrives here)
+  float mn[3] = {0.f, 0.f, 0.f}, mx[3] = {0.f, 0.f, 0.f};
+  if (valid) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      mn[d] = fminf(p[0][d], fminf(p[1][d], p[2][d]));
+      mx[d] = fmaxf(p[0][d], fmaxf(p[1][d], p[2][d]));
+    }
+  }
+  for (int l = 0; l < kLevels; ++l) {
+    const Level& G = H->level[l];
+    double n = 1.0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      n *= (double)(cell_axis(mx[d], H->lo[d], G.inv_h, G.dims[d]) - cell_axis(mn[d], H->lo[d], G.inv_h, G.dims[d]) + 1);
+    unsigned long long v = valid ? (unsigned long long)fmin(n, 4294967296.0) : 0ull;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&H->pairs[l], v);
+  }
+}
+
+// the first level whose grid fits the workspace: cells and (triangle, cell) pairs; the last level (one cell) always does
+__global__ void k_msdf_pick(Header* __restrict__ H, int64_t cellcap, int64_t paircap) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int l = 0;
+  for (; l < kLevels - 1; ++l) {
+    const Level& G = H->level[l];
+    const double cells = (double)G.dims[0] * (double)G.dims[1] * (double)G.dims[2];
+    if (cells <= (double)cellcap && H->pairs[l] <= (unsigned long long)paircap) break;
+  }
+  const Level& G = H->level[l];
+  H->chosen = l;
+  H->h = G.h;
+  H->inv_h = G.inv_h;
+  const bool any = H->pairs[kLevels - 1] > 0;   // a valid triangle exists
+  for (int g = 0; g < 2; ++g) {
+    int64_t n = 1;
+    for (int d = 0; d < 3; ++d) {
+      H->dims[g][d] = g == 0 ? G.dims[d] : ((G.dims[d] - 1) >> kCoarseShift) + 1;
+      n *= H->dims[g][d];
+    }
+    H->n_cells[g] = any ? (int32_t)n : 0;
+  }
+  H->tests = 0;
+  H->magic = kMagic;
+}
+
+// a vertex inherits the flags of its edges: on the boundary if an incident edge has one face, non-manifold if an
+// incident edge has more than two
+__global__ __launch_bounds__(256) void k_msdf_vflags(Ws W) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= W.ecap) return;
+  const unsigned long long key = W.ekey[s];
+  if (key == kNoEdge) return;
+  const uint32_t c = W.ecnt[s];
+  const uint32_t flag = c == 1 ? 0x10u : (c > 2 ? 0x20u : 0u);
+  if (flag) {
+    atomicOr(&W.vflag[(uint32_t)(key >> 32)], flag);
+    atomicOr(&W.vflag[(uint32_t)key], flag);
+  }
+}
+
+// cell range of a triangle's bounding box on grid g (coarse cell = fine cell >> kCoarseShift, so a triangle overlaps
+// no more coarse cells than fine ones)
+__device__ __forceinline__ void tri_cells(const Header& H, int g, const float4 a, const float4 b, const float4 c,
+                                          int c0[3], int c1[3]) {
+  const float mn[3] = {fminf(a.x, fminf(b.x, c.x)), fminf(a.y, fminf(b.y, c.y)), fminf(a.z, fminf(b.z, c.z))};
+  const float mx[3] = {fmaxf(a.x, fmaxf(b.x, c.x)), fmaxf(a.y, fmaxf(b.y, c.y)), fmaxf(a.z, fmaxf(b.z, c.z))};
+  const int sh = g ? kCoarseShift : 0;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    c0[d] = cell_axis(mn[d], H.lo[d], H.inv_h, H.dims[0][d]) >> sh;
+    c1[d] = cell_axis(mx[d], H.lo[d], H.inv_h, H.dims[0][d]) >> sh;
+  }
+}
+
+// FILL = false: count the triangles of every cell; FILL = true: write the ids (the slot inside a cell follows the
+// order of the atomics; results do not depend on it -- tie rule)
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_msdf_cells(Ws W, int g) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const Header& H = *W.H;
+  if (f >= H.n_faces || H.n_cells[g] == 0) return;
+  const float4 a = W.tri[f * 3], b = W.tri[f * 3 + 1], c = W.tri[f * 3 + 2];
+  if (__builtin_bit_cast(int32_t, a.w) < 0) return;
+  int c0[3], c1[3];
+  tri_cells(H, g, a, b, c, c0, c1);
+  for (int x = c0[0]; x <= c1[0]; ++x)
+    for (int y = c0[1]; y <= c1[1]; ++y)
+      for (int z = c0[2]; z <= c1[2]; ++z) {
+        const int64_t cell = ((int64_t)x * H.dims[g][1] + y) * H.dims[g][2] + z;
+        if (FILL) {
+          const uint32_t left = atomicSub(&W.count[g][cell], 1u);
+          const uint64_t slot = (uint64_t)W.start[g][cell] + left - 1u;
+          if (slot < (uint64_t)W.paircap) W.ids[g][slot] = (uint32_t)f;
+        } else {
+          atomicAdd(&W.count[g][cell], 1u);
+        }
+      }
+}
+
+// exclusive scan of count[0 .. n_bins) -> start (bnv_common.hpp's uint32 block scan + decoupled look-back)
+__global__ __launch_bounds__(kScanThreads) void k_msdf_scan(const uint32_t* __restrict__ count, int64_t n_bins,
+                                                            uint32_t* __restrict__ start, uint64_t* __restrict__ state,
+                                                            uint32_t epoch) {
+  __shared__ uint32_t wave_tot[kScanThreads / 64];
+  __shared__ uint32_t s_excl;
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  uint32_t v[kScanItems], s = 0;
+#pragma unroll
+  for (int e = 0; e < kScanItems; ++e) {
+    v[e] = base + e < n_bins ? count[base + e] : 0u;
+    s += v[e];
+  }
+  uint32_t total;
+  uint32_t run = block_exclusive_scan<kScanThreads>(s, wave_tot, &total);
+  if (threadIdx.x < 64) {
+    const uint32_t excl = lookback_exclusive(state, (int)blockIdx.x, total, epoch);
+    if (threadIdx.x == 0) s_excl = excl;
+  }
+  __syncthreads();
+  run += s_excl;
+#pragma unroll
+  for (int e = 0; e < kScanItems; ++e) {
+    if (base + e < n_bins) start[base + e] = run;
+    run += v[e];
+  }
+}
+
+// =====================================================================================================================
+// Query
+// =====================================================================================================================
+struct Best {
+  float d2;
+  int32_t face;
+  int32_t code;   // 0 face | 1 edge ab, 2 edge bc, 3 edge ca | 4 vertex a, 5 vertex b, 6 vertex c
+  float c[3];
+};
+
+// Closest point of triangle (a, b, c) to q: the seven Voronoi regions of the triangle (three vertices, three edges,
+// the face), decided by the signs of the projections d1 .. d6 and of the barycentric numerators va, vb, vc.  fp32, one
+// rounding per operation.  (d2, face) lexicographic: the lowest face index wins a tie.
+__device__ __forceinline__ void tri_test(const float q[3], const float4 A, const float4 B, const float4 C, int32_t f,
+                                         Best& best) {
+  const float ab[3] = {B.x - A.x, B.y - A.y, B.z - A.z}, ac[3] = {C.x - A.x, C.y - A.y, C.z - A.z};
+  const float ap[3] = {q[0] - A.x, q[1] - A.y, q[2] - A.z};
+  const float bp[3] = {q[0] - B.x, q[1] - B.y, q[2] - B.z};
+  const float cp[3] = {q[0] - C.x, q[1] - C.y, q[2] - C.z};
+  const float d1 = (ab[0] * ap[0] + ab[1] * ap[1]) + ab[2] * ap[2], d2 = (ac[0] * ap[0] + ac[1] * ap[1]) + ac[2] * ap[2];
+  const float d3 = (ab[0] * bp[0] + ab[1] * bp[1]) + ab[2] * bp[2], d4 = (ac[0] * bp[0] + ac[1] * bp[1]) + ac[2] * bp[2];
+  const float d5 = (ab[0] * cp[0] + ab[1] * cp[1]) + ab[2] * cp[2], d6 = (ac[0] * cp[0] + ac[1] * cp[1]) + ac[2] * cp[2];
+  const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+  float s = 0.0f, t = 0.0f;   // closest = a + s ab + t ac
+  int code;
+  if (d1 <= 0.0f && d2 <= 0.0f) {
+    code = 4;
+  } else if (d3 >= 0.0f && d4 <= d3) {
+    code = 5;
+    s = 1.0f;
+  } else if (d6 >= 0.0f && d5 <= d6) {
+    code = 6;
+    t = 1.0f;
+  } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
+    code = 1;
+    s = d1 / (d1 - d3);
+  } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
+    code = 3;
+    t = d2 / (d2 - d6);
+  } else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {
+    code = 2;
+    t = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+    s = 1.0f - t;
+  } else {
+    code = 0;
+    const float denom = 1.0f / ((va + vb) + vc);
+    s = vb * denom;
+    t = vc * denom;
+  }
+  float c[3];
+  if (code == 5) {
+    c[0] = B.x; c[1] = B.y; c[2] = B.z;
+  } else if (code == 6) {
+    c[0] = C.x; c[1] = C.y; c[2] = C.z;
+  } else if (code == 2) {   // b + t (c - b)
+    c[0] = B.x + t * (C.x - B.x);
+    c[1] = B.y + t * (C.y - B.y);
+    c[2] = B.z + t * (C.z - B.z);
+  } else {
+    c[0] = (A.x + s * ab[0]) + t * ac[0];
+    c[1] = (A.y + s * ab[1]) + t * ac[1];
+    c[2] = (A.z + s * ab[2]) + t * ac[2];
+  }
+  const float dx = q[0] - c[0], dy = q[1] - c[1], dz = q[2] - c[2];
+  const float dd = (dx * dx + dy * dy) + dz * dz;
+  if (dd < best.d2 || (dd == best.d2 && f < best.face)) {
+    best.d2 = dd;
+    best.face = f;
+    best.code = code;
+    best.c[0] = c[0];
+    best.c[1] = c[1];
+    best.c[2] = c[2];
+  }
+}
+
+// Can the search stop after ring r of grid g (cell edge hh)?  A point of a triangle lies in a cell the triangle is
+// listed in.  If that cell was visited, the triangle was tested as a whole; otherwise the point lies beyond one face
+// of the box of visited cells on some axis and inside the bounding box on the others (eval.hip: nn_can_stop).  Stop
+// when that lower bound on the distance exceeds the best fp32 distance by the relative and the absolute slack (the
+// fp32 closest point carries a few ulp of the largest coordinate), or when the ring covers the grid.
+__device__ __forceinline__ bool can_stop(const Header& H, int g, double hh, const int c[3], int r, const double q[3],
+                                         float best_d2) {
+  double gd2[3], base = 0.0;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const double gap = fmax(fmax(H.fmin[d] - q[d], q[d] - H.fmax[d]), 0.0);
+    gd2[d] = gap * gap;
+    base += gd2[d];
+  }
+  double lb = INFINITY;
+  bool open = false;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const int dim = H.dims[g][d];
+    const double slack = 1e-12 * (fabs(q[d]) + fabs(H.lo[d]) + (double)dim * hh) + 1e-9 * hh;
+    if (c[d] - r > 0) {
+      open = true;
+      const double f = fmax(q[d] - (H.lo[d] + (double)(c[d] - r) * hh) - slack, 0.0);
+      lb = fmin(lb, f * f + (base - gd2[d]));
+    }
+    if (c[d] + r < dim - 1) {
+      open = true;
+      const double f = fmax((H.lo[d] + (double)(c[d] + r + 1) * hh) - q[d] - slack, 0.0);
+      lb = fmin(lb, f * f + (base - gd2[d]));
+    }
+  }
+  if (!open) return true;
+  const double bd = sqrt((double)best_d2) * (1.0 + kStopSlack) + H.eps_abs;
+  return lb > bd * bd;
+}
+
+// ring search of one query on grid g, rings 0 .. rmax, until the stop test proves `best` final (-> true)
+__device__ __forceinline__ bool rings(const Header& H, const Ws& W, int g, const float qf[3], const double q[3],
+                                      int rmax, Best& best, uint32_t& tests) {
+  const int sh = g ? kCoarseShift : 0;
+  const double hh = H.h * (double)(1 << sh);
+  const int c[3] = {cell_axis(qf[0], H.lo[0], H.inv_h, H.dims[0][0]) >> sh,
+                    cell_axis(qf[1], H.lo[1], H.inv_h, H.dims[0][1]) >> sh,
+                    cell_axis(qf[2], H.lo[2], H.inv_h, H.dims[0][2]) >> sh};
+  const int D0 = H.dims[g][0], D1 = H.dims[g][1], D2 = H.dims[g][2];
+  const uint32_t* __restrict__ start = W.start[g];
+  const uint32_t* __restrict__ ids = W.ids[g];
+  const float4* __restrict__ tri = W.tri;
+  for (int r = 0; r <= rmax; ++r) {
+    const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, D0 - 1);
+    const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, D1 - 1);
+    const int zl = c[2] - r, zh = c[2] + r;
+    for (int x = x0; x <= x1; ++x)
+      for (int y = y0; y <= y1; ++y) {
+        const bool shell = x == c[0] - r || x == c[0] + r || y == c[1] - r || y == c[1] + r;
+        // the ring's cells of this (x, y) column: a contiguous z-run on the shell, else its two ends
+        for (int part = 0; part < (shell ? 1 : 2); ++part) {
+          int za, zb;
+          if (shell) {
+            za = max(zl, 0);
+            zb = min(zh, D2 - 1);
+          } else {
+            za = zb = part == 0 ? zl : zh;
+            if (za < 0 || za >= D2) continue;
+          }
+          if (za > zb) continue;
+          const int64_t col = ((int64_t)x * D1 + y) * D2;
+          const uint32_t e = start[col + zb + 1];
+          for (uint32_t k = start[col + za]; k < e; ++k) {
+            const uint32_t f = ids[k];
+            tri_test(qf, tri[(int64_t)f * 3], tri[(int64_t)f * 3 + 1], tri[(int64_t)f * 3 + 2], (int32_t)f, best);
+            ++tests;
+          }
+        }
+      }
+    if (can_stop(H, g, hh, c, r, q, best.d2)) return true;
+  }
+  return false;
+}
+
+// One thread per query (eval.hip's k_nn_query: cells hold a handful of triangles, too few for 64 lanes).  A query that
+// the first kFineRings rings of the fine grid do not settle goes on, with the best it has, on the coarse grid, whose
+// search is exact on its own; a triangle seen twice changes nothing under the tie rule.
+__global__ __launch_bounds__(256) void k_msdf_query(char* __restrict__ ws, int64_t ws_bytes,
+                                                    const float* __restrict__ Q, int64_t n_query,
+                                                    float* __restrict__ sdf_out, int32_t* __restrict__ face_out,
+                                                    float* __restrict__ closest_out, uint8_t* __restrict__ feature_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_query) return;
+  const Header& H = *(const Header*)ws;
+  const float qf[3] = {Q[i * 3], Q[i * 3 + 1], Q[i * 3 + 2]};
+  const bool ok = H.magic == kMagic && H.bytes <= ws_bytes && H.n_cells[0] > 0 && finite3(qf[0], qf[1], qf[2]);
+  float sdf = __builtin_nanf("");
+  int32_t face = -1;
+  uint32_t feature = 0;
+  float cpt[3] = {sdf, sdf, sdf};
+  if (ok) {
+    Ws W;
+    msdf_layout(H.n_vertices, H.n_faces, ws, &W);
+    const double q[3] = {(double)qf[0], (double)qf[1], (double)qf[2]};
+    Best best;
+    best.d2 = INFINITY;
+    best.face = INT32_MAX;
+    best.code = 0;
+    best.c[0] = best.c[1] = best.c[2] = 0.0f;
+    uint32_t tests = 0;
+    if (!rings(H, W, 0, qf, q, kFineRings, best, tests))
+      rings(H, W, 1, qf, q, max(H.dims[1][0], max(H.dims[1][1], H.dims[1][2])), best, tests);
+#ifdef BNV_MESHSDF_COUNT_TESTS
+    atomicAdd(&W.H->tests, (unsigned long long)tests);
+#endif
+    if (best.face != INT32_MAX) {   // (always: the coarse search covers the grid, which holds a valid triangle)
+    // the sign: (q - closest) . pseudonormal of the closest feature, in float64
+    const float4 T[3] = {W.tri[(int64_t)best.face * 3], W.tri[(int64_t)best.face * 3 + 1],
+                         W.tri[(int64_t)best.face * 3 + 2]};
+    const int32_t vi0 = __builtin_bit_cast(int32_t, T[0].w), vi1 = __builtin_bit_cast(int32_t, T[1].w),
+                  vi2 = __builtin_bit_cast(int32_t, T[2].w);
+    double dot;
+    if (best.code == 0) {
+      // the face: (q - a) . (ab x ac), which equals (q - closest) . n for a closest point in the face's plane
+      const double a[3] = {(double)T[1].x - (double)T[0].x, (double)T[1].y - (double)T[0].y, (double)T[1].z - (double)T[0].z};
+      const double b[3] = {(double)T[2].x - (double)T[0].x, (double)T[2].y - (double)T[0].y, (double)T[2].z - (double)T[0].z};
+      const double n[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+      dot = ((q[0] - (double)T[0].x) * n[0] + (q[1] - (double)T[0].y) * n[1]) + (q[2] - (double)T[0].z) * n[2];
+    } else {
+      const double d[3] = {q[0] - (double)best.c[0], q[1] - (double)best.c[1], q[2] - (double)best.c[2]};
+      const long long* acc = nullptr;
+      if (best.code >= 4) {
+        const int32_t v = best.code == 4 ? vi0 : (best.code == 5 ? vi1 : vi2);
+        acc = &W.vacc[(int64_t)v * 3];
+        feature = 2u | W.vflag[v];
+      } else {
+        const unsigned long long key = best.code == 1 ? edge_key(vi0, vi1)
+                                       : (best.code == 2 ? edge_key(vi1, vi2) : edge_key(vi2, vi0));
+        uint32_t s = edge_slot0(key, W.ecap);
+        feature = 1u;
+        for (uint32_t probe = 0; probe < W.ecap; ++probe) {
+          const unsigned long long have = W.ekey[s];
+          if (have == key) {
+            acc = &W.eacc[(int64_t)s * 3];
+            const uint32_t cnt = W.ecnt[s];
+            feature |= cnt == 1 ? 0x10u : (cnt > 2 ? 0x20u : 0u);
+            break;
+          }
+          if (have == kNoEdge) break;
+          s = (s + 1) & (W.ecap - 1);
+        }
+      }
+      dot = acc ? (d[0] * (double)acc[0] + d[1] * (double)acc[1]) + d[2] * (double)acc[2] : 0.0;
+    }
+    const float dist = (float)sqrt((double)best.d2);
+    sdf = dot < 0.0 ? -dist : dist;
+    face = best.face;
+    cpt[0] = best.c[0];
+    cpt[1] = best.c[1];
+    cpt[2] = best.c[2];
+    }
+  }
+  sdf_out[i] = sdf;
+  if (face_out) face_out[i] = face;
+  if (closest_out) {
+    closest_out[i * 3] = cpt[0];
+    closest_out[i * 3 + 1] = cpt[1];
+    closest_out[i * 3 + 2] = cpt[2];
+  }
+  if (feature_out) feature_out[i] = (uint8_t)feature;
+}
+
+bool counts_ok(int64_t nv, int64_t nf) { return nv > 0 && nf > 0 && nv <= kMaxVertices && nf <= kMaxFaces; }
+
+}  // namespace
+}  // namespace bnv
+
+using namespace bnv;
+
+extern "C" {
+
+int bnv_mesh_sdf_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t* bytes) {
+  if (!bytes || !counts_ok(n_vertices, n_faces)) return BNV_ERR_INVALID_ARGUMENT;
+  *bytes = (int64_t)msdf_layout(n_vertices, n_faces, nullptr, nullptr);
+  return BNV_OK;
+}
+
+int bnv_mesh_sdf_build(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                       void* workspace, int64_t ws_bytes, bnv_stream_t stream) {
+  if (!vertices || !faces || !workspace || !counts_ok(n_vertices, n_faces)) return BNV_ERR_INVALID_ARGUMENT;
+  const int64_t need = (int64_t)msdf_layout(n_vertices, n_faces, nullptr, nullptr);
+  if (ws_bytes < need) return BNV_ERR_INVALID_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  Ws W;
+  msdf_layout(n_vertices, n_faces, (char*)workspace, &W);
+  const int64_t n_bins = W.cellcap + 2;
+  // everything the build accumulates into starts from a known state on every call
+  BNV_HIP_CHECK(hipMemsetAsync(W.H, 0, sizeof(Header), s));
+  BNV_HIP_CHECK(hipMemsetAsync(W.H, 0xff, 3 * sizeof(uint32_t), s));   // bmin (first member) = the largest key
+  BNV_HIP_CHECK(hipMemsetAsync(W.vacc, 0, (size_t)n_vertices * 24, s));
+  BNV_HIP_CHECK(hipMemsetAsync(W.vflag, 0, (size_t)n_vertices * 4, s));
+  BNV_HIP_CHECK(hipMemsetAsync(W.ekey, 0xff, (size_t)W.ecap * 8, s));
+  BNV_HIP_CHECK(hipMemsetAsync(W.eacc, 0, (size_t)W.ecap * 24, s));
+  BNV_HIP_CHECK(hipMemsetAsync(W.ecnt, 0, (size_t)W.ecap * 4, s));
+  BNV_HIP_CHECK(hipMemsetAsync(W.count[0], 0, (size_t)n_bins * 4, s));
+  BNV_HIP_CHECK(hipMemsetAsync(W.count[1], 0, (size_t)n_bins * 4, s));
+  BNV_HIP_CHECK(hipMemsetAsync(W.scan_state, 0, (size_t)W.tiles * 2 * 8, s));
+  const unsigned bbox_blocks = (unsigned)std::min<int64_t>((n_vertices + 255) / 256, 2048);
+  const dim3 face_blocks((unsigned)((n_faces + 255) / 256));
+  hipLaunchKernelGGL(k_msdf_bbox, dim3(bbox_blocks), dim3(256), 0, s, vertices, n_vertices, W.H);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_msdf_levels, dim3(1), dim3(64), 0, s, W.H, n_vertices, n_faces, need);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_msdf_faces, face_blocks, dim3(256), 0, s, vertices, n_vertices, faces, n_faces, W);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_msdf_pick, dim3(1), dim3(64), 0, s, W.H, W.cellcap, W.paircap);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_msdf_vflags, dim3((W.ecap + 255) / 256), dim3(256), 0, s, W);
+  BNV_LAUNCH_CHECK();
+  for (int g = 0; g < 2; ++g) {
+    hipLaunchKernelGGL(k_msdf_cells<false>, face_blocks, dim3(256), 0, s, W, g);
+    BNV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_msdf_scan, dim3((unsigned)W.tiles), dim3(kScanThreads), 0, s, W.count[g], n_bins, W.start[g],
+                       W.scan_state + g * W.tiles, next_epoch());
+    BNV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_msdf_cells<true>, face_blocks, dim3(256), 0, s, W, g);
+    BNV_LAUNCH_CHECK();
+  }
+  return BNV_OK;
+}
+
+int bnv_mesh_sdf_query(const void* workspace, int64_t ws_bytes, const float* query, int64_t n_query, float* sdf_out,
+                       int32_t* face_out, float* closest_out, uint8_t* feature_out, bnv_stream_t stream) {
+  if (!workspace || !query || !sdf_out || n_query <= 0 || n_query > INT32_MAX) return BNV_ERR_INVALID_ARGUMENT;
+  if (ws_bytes < (int64_t)msdf_layout(1, 1, nullptr, nullptr)) return BNV_ERR_INVALID_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_msdf_query, dim3((unsigned)((n_query + 255) / 256)), dim3(256), 0, s, (char*)workspace, ws_bytes,
+                     query, n_query, sdf_out, face_out, closest_out, feature_out);
+  BNV_LAUNCH_CHECK();
+  return BNV_OK;
+}
+
+}  // extern "C"

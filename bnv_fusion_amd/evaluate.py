@@ -4,7 +4,8 @@ src/scripts/compute_chamfer.py:36-75) on the GPU.
 The reference samples 100,000 points on each mesh (trimesh ``sample_surface``), finds every point's nearest neighbour on
 the other side (sklearn ball tree) and reports the pred -> gt mean distance, precision at 2.5 cm, the gt -> pred mean
 distance, recall at 2.5 cm and F1.  Here the sampling and the exact nearest-neighbour search are HIP kernels
-(csrc/eval.hip; include/bnv_fusion.h: bnv_mesh_sample_surface, bnv_nn_query); only the reductions that turn
+(csrc/eval.hip; include/bnv_fusion.h: bnv_mesh_sample_surface, bnv_nn_query), and so is the exact signed distance to a
+mesh (``MeshSDF``, csrc/meshsdf.hip); only the reductions that turn
 distances into figures (a mean, a count under the threshold) run in torch, in float64.  Inputs live on the GPU: a CPU
 tensor is refused, there is no CPU fallback.
 
@@ -126,6 +127,67 @@ def nearest_neighbors(query, ref):
     """-> (dist float64 [N] = sqrt(d2) taken in float64, idx int64 [N]); see ``nn_d2``."""
     d2, idx = nn_d2(query, ref)
     return torch.sqrt(d2.double()), idx.long()
+
+
+FEATURE_FACE, FEATURE_EDGE, FEATURE_VERTEX = 0, 1, 2
+FEATURE_CLASS_MASK = 0x0f
+FEATURE_BOUNDARY = 0x10        # the closest edge / vertex lies on the mesh boundary: the sign is not trustworthy
+FEATURE_NONMANIFOLD = 0x20     # ... has an edge with more than two faces
+
+
+class MeshSDF:
+    """Exact signed distance to a triangle mesh on the GPU (csrc/meshsdf.hip; include/bnv_fusion.h:
+    bnv_mesh_sdf_build / bnv_mesh_sdf_query): negative inside for outward-oriented faces, exact everywhere (no
+    truncation band), bitwise reproducible.  ``vertices`` fp32 [V, 3] and ``faces`` int [T, 3] device tensors, or a
+    TriMesh (uploaded to ``device``, default the current GPU) -- the conventions of ``sample_surface``.  The index is
+    built once; ``query`` may be called any number of times.
+
+        sdf, face, closest, feature = MeshSDF(mesh).query(points)
+    """
+
+    def __init__(self, vertices, faces=None, device=None):
+        v, f = _mesh_tensors(vertices, faces, device)
+        self.device = v.device
+        self.n_vertices, self.n_faces = int(v.shape[0]), int(f.shape[0])
+        lib = _lib.load()
+        ws_bytes = C.c_int64()
+        _lib.check(lib.bnv_mesh_sdf_workspace_bytes(self.n_vertices, self.n_faces, C.byref(ws_bytes)),
+                   "bnv_mesh_sdf_workspace_bytes")
+        self._ws_bytes = int(ws_bytes.value)
+        with torch.cuda.device(self.device):
+            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+            _lib.check(lib.bnv_mesh_sdf_build(_lib.ptr(v), self.n_vertices, _lib.ptr(f), self.n_faces,
+                                              _lib.ptr(self._ws), self._ws_bytes, _lib.stream_ptr()),
+                       "bnv_mesh_sdf_build")
+
+    def query(self, points):
+        """``points`` fp32 [..., 3] on the mesh's device -> (sdf fp32 [...], face int32 [...] -- the closest triangle,
+        the lowest index among equals --, closest fp32 [..., 3], feature uint8 [...]: ``FEATURE_FACE`` / ``_EDGE`` /
+        ``_VERTEX``, ``| FEATURE_BOUNDARY``, ``| FEATURE_NONMANIFOLD``).  A non-finite point gets (nan, -1, nan, 0)."""
+        q = _on_gpu(points, "points", torch.float32)
+        if q.dim() < 1 or q.shape[-1] != 3 or q.numel() == 0:
+            raise ValueError(f"points: expected a non-empty [..., 3] tensor, got {tuple(q.shape)}")
+        if q.device != self.device:
+            raise ValueError(f"points on {q.device}, mesh on {self.device}")
+        lead = tuple(q.shape[:-1])
+        q = q.reshape(-1, 3)
+        n = int(q.shape[0])
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            sdf = torch.empty(n, dtype=torch.float32, device=self.device)
+            face = torch.empty(n, dtype=torch.int32, device=self.device)
+            closest = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+            feature = torch.empty(n, dtype=torch.uint8, device=self.device)
+            _lib.check(lib.bnv_mesh_sdf_query(_lib.ptr(self._ws), self._ws_bytes, _lib.ptr(q), n, _lib.ptr(sdf),
+                                              _lib.ptr(face), _lib.ptr(closest), _lib.ptr(feature), _lib.stream_ptr()),
+                       "bnv_mesh_sdf_query")
+        return sdf.reshape(lead), face.reshape(lead), closest.reshape(lead + (3,)), feature.reshape(lead)
+
+
+def mesh_sdf(points, vertices, faces=None):
+    """One-shot ``MeshSDF(vertices, faces).query(points)``; a TriMesh goes to the device of ``points``."""
+    dev = points.device if isinstance(points, torch.Tensor) and points.is_cuda else None
+    return MeshSDF(vertices, faces, device=dev).query(points)
 
 
 def metrics_from_distances(d_pred_gt, d_gt_pred, threshold=0.025):

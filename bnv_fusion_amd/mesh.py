@@ -374,3 +374,35 @@ def load_ply(path):
     if len(faces) and (faces.min() < 0 or faces.max() >= len(verts)):
         raise ValueError(f"{path}: a face indexes a vertex that does not exist")
     return TriMesh(verts.astype(np.float32), faces)
+
+
+def load_obj(path):
+    """Wavefront OBJ -> TriMesh (ShapeNet's format): ``v x y z`` and ``f`` records only, everything else (normals,
+    texture coordinates, groups, materials) is read past.  Face corners may be ``a``, ``a/b``, ``a//c`` or ``a/b/c``
+    (the vertex index is the first field); indices are 1-based, negative ones count back from the vertices read so
+    far; quads and larger polygons are triangulated as fans."""
+    verts, polys = [], []
+    with open(path, "r", errors="replace") as fh:
+        for no, raw in enumerate(fh, 1):
+            tok = raw.split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                if len(tok) < 4:
+                    raise ValueError(f"{path}:{no}: vertex with {len(tok) - 1} coordinates")
+                verts.append((float(tok[1]), float(tok[2]), float(tok[3])))
+            elif tok[0] == "f":
+                poly = []
+                for corner in tok[1:]:
+                    i = int(corner.split("/")[0])
+                    i = i - 1 if i > 0 else len(verts) + i
+                    if i < 0 or i >= len(verts):
+                        raise ValueError(f"{path}:{no}: face corner {corner!r} indexes a vertex that does not exist")
+                    poly.append(i)
+                if len(poly) < 3:
+                    raise ValueError(f"{path}:{no}: face with {len(poly)} vertices")
+                polys.append(poly)
+    if not verts:
+        raise ValueError(f"{path}: no vertices")
+    return TriMesh(np.array(verts, dtype=np.float64).reshape(-1, 3).astype(np.float32),
+                   np.array(_fan(polys), dtype=np.int64).reshape(-1, 3))

@@ -866,6 +866,40 @@ int bnv_nn_workspace_bytes(int64_t n_ref, int64_t n_query, int64_t* bytes);
 int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_query, void* workspace,
                  int64_t ws_bytes, float* d2_out, int32_t* idx_out, bnv_stream_t stream);
 
+/* ---- Signed distance to a triangle mesh (bnv_fusion_amd/csrc/meshsdf.hip): the exact distance from arbitrary points
+ * to the mesh, everywhere (no truncation band), negative inside for outward-oriented faces.  The reference has no such
+ * entry; bnv_fusion_amd/patches.py cuts embedding-training patches with it.
+ *
+ * Index.  vertices fp32 [n_vertices, 3], faces int32 [n_faces, 3] (device).  A face is skipped when an index lies
+ * outside [0, n_vertices), when its fp32 area 0.5 |e1 x e2| is not positive and finite (the rule of
+ * bnv_mesh_sample_surface: zero area, a NaN / Inf vertex) or when its cross product is exactly zero in float64.  Of
+ * the others the index holds: unit face normals n_f (float64 from the fp32 positions); vertex pseudonormals sum_f
+ * angle_f(v) n_f and edge pseudonormals sum_f n_f over the incident faces (Baerentzen & Aanaes 2005), as 64-bit
+ * fixed-point integer sums (2^-40), so the same inputs give the same bits on every run; the number of incident faces
+ * of every edge (vertex index pairs: 1 = boundary, > 2 = non-manifold; a vertex inherits the flags of its edges); two
+ * uniform grids of triangle ids, a triangle listed in every cell its bounding box overlaps.  Everything lives in the
+ * caller's workspace (bytes: a function of the two counts alone; n_faces <= 2^27); the workspace IS the index and is
+ * passed to bnv_mesh_sdf_query as built.  No allocation, synchronisation or host read.
+ *
+ * Query.  query fp32 [n_query, 3] -> sdf_out fp32 [n_query]; face_out int32 [n_query], closest_out fp32 [n_query, 3],
+ * feature_out uint8 [n_query] (each may be NULL: not written).  Per triangle the closest point by the seven-region
+ * (vertex / edge / face) case analysis in fp32, one rounding per operation; d2 = (dx dx + dy dy) + dz dz to that
+ * point; the triangle of least d2 wins, the LOWEST face index among equals; |sdf| = sqrt(d2) correctly rounded.  The
+ * sign is that of (query - closest) . pseudonormal of the closest feature -- the face, the edge or the vertex -- in
+ * float64 (>= 0: outside).  feature = 0 face | 1 edge | 2 vertex, | BNV_MESH_SDF_BOUNDARY when that edge or vertex
+ * lies on the mesh boundary (the sign there is not trustworthy), | BNV_MESH_SDF_NONMANIFOLD when it is non-manifold.
+ * A query with a NaN / Inf coordinate, any query against an index without a valid face, or a workspace that does not
+ * hold an index of at most ws_bytes gets sdf = NaN, face = -1, closest = NaN, feature = 0.
+ * Null pointers (other than the optional outputs), counts <= 0 or out of range and a workspace smaller than
+ * bnv_mesh_sdf_workspace_bytes are BNV_ERR_INVALID_ARGUMENT before any HIP call. */
+#define BNV_MESH_SDF_BOUNDARY 0x10
+#define BNV_MESH_SDF_NONMANIFOLD 0x20
+int bnv_mesh_sdf_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t* bytes);
+int bnv_mesh_sdf_build(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                       void* workspace, int64_t ws_bytes, bnv_stream_t stream);
+int bnv_mesh_sdf_query(const void* workspace, int64_t ws_bytes, const float* query, int64_t n_query, float* sdf_out,
+                       int32_t* face_out, float* closest_out, uint8_t* feature_out, bnv_stream_t stream);
+
 /* ---- Rendering (bnv_fusion_amd/csrc/render.hip): depth and normal images of the map from a camera pose.  The
  * reference has no such entry; these are the semantics SparseVolume.render_depth / TSDFVolume.render_depth expose and
  * the tests replay in float32 (every operation below is one IEEE fp32 rounding, in the order written, sqrt and division
