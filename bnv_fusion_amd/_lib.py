@@ -42,6 +42,7 @@ SYMBOLS = [
     "bnv_train_tcnn_param_floats", "bnv_train_tcnn_workspace_bytes", "bnv_train_tcnn_step", "bnv_train_tcnn_eval_loss",
     "bnv_train_tcnn_forward",
     "bnv_mesh_sdf_workspace_bytes", "bnv_mesh_sdf_build", "bnv_mesh_sdf_query",
+    "bnv_mesh_ray_workspace_bytes", "bnv_mesh_ray_cast", "bnv_mesh_render_depth", "bnv_depth_sensor",
 ]
 
 
@@ -306,6 +307,12 @@ def load():
         "bnv_mesh_sdf_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
         "bnv_mesh_sdf_build": (C.c_int, [vp, i64, vp, i64, vp, i64, vp]),
         "bnv_mesh_sdf_query": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+        "bnv_mesh_ray_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+        "bnv_mesh_ray_cast": (C.c_int, [vp, i64, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+        "bnv_mesh_render_depth": (C.c_int, [vp, i64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                            C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, i64, vp]),
+        "bnv_depth_sensor": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_uint32, C.c_double, C.c_double,
+                                       C.c_double, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

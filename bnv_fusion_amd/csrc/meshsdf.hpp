@@ -1,0 +1,119 @@
+// The mesh index csrc/meshsdf.hip builds and both it and csrc/meshray.hip read: the header word layout, the carving of
+// the caller's workspace (msdf_layout) and the helpers that decide which cell a coordinate falls into.  One definition,
+// so the builder and every reader agree on it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace bnv {
+namespace {
+
+constexpr int kLevels = 24;               // candidate cell sizes h0 * kLadder^l; the last one is a single cell
+constexpr double kLadder = 1.5;
+constexpr double kCellTarget = 2.0;       // h0 = sqrt(kCellTarget * S / n_faces), S = half the bounding box's surface
+constexpr int64_t kCellsPerFace = 8;      // the grid has at most kCellsPerFace * n_faces + 64 cells
+constexpr int64_t kPairsPerFace = 8;      // ... and at most kPairsPerFace * n_faces + 64 (triangle, cell) pairs
+constexpr int kFineRings = 4;             // rings of the fine grid before a query moves on to the coarse grid
+constexpr int kCoarseShift = 2;           // coarse cell = fine cell >> 2 on every axis
+constexpr double kStopSlack = 1e-5;       // relative slack of the stop test on the distance
+constexpr double kNormalScale = 1099511627776.0;   // 2^40: fixed point of the pseudonormal sums
+constexpr unsigned long long kNoEdge = ~0ull;
+constexpr uint32_t kMagic = 0x4653444du;
+constexpr int kScanThreads = 256, kScanItems = 4, kScanTile = kScanThreads * kScanItems;
+constexpr int64_t kMaxFaces = 1 << 27, kMaxVertices = INT32_MAX;
+
+struct Level {
+  double h, inv_h;
+  int32_t dims[3];
+  int32_t pad;
+};
+
+struct Header {
+  uint32_t bmin[3], bmax[3];   // order-preserving encodings of the finite vertices' bounding box (first: memset)
+  unsigned long long tests;    // byte 24: triangle tests of all queries since the build (BNV_MESHSDF_COUNT_TESTS builds
+                               // only; tools/mesh_sdf_bench.py reads it)
+  uint32_t magic, pad0;
+  int64_t n_vertices, n_faces, bytes;
+  double lo[3], fmin[3], fmax[3];
+  Level level[kLevels];
+  unsigned long long pairs[kLevels];   // (triangle, cell) pairs the grid of every level would hold
+  int32_t chosen, pad1;
+  int32_t n_cells[2];                  // fine, coarse; 0: no valid triangle
+  int32_t dims[2][3];
+  double h, inv_h;                     // the fine grid's
+  double eps_abs;                      // absolute slack of the stop test: 8 ulp of the largest coordinate
+};
+static_assert(offsetof(Header, tests) == 24, "tools/mesh_sdf_bench.py reads the counter at byte 24");
+
+struct Ws {
+  Header* H;
+  float4* tri;                 // [3 F]: (vertex k, bitcast(vertex index)); index -1: a skipped face
+  long long* vacc;             // [3 V] angle-weighted normal sums, fixed point
+  uint32_t* vflag;             // [V] 0x10 boundary, 0x20 non-manifold
+  unsigned long long* ekey;    // [ecap] (lo vertex << 32) | hi vertex, kNoEdge: empty
+  long long* eacc;             // [3 ecap] sums of the incident unit face normals, fixed point
+  uint32_t* ecnt;              // [ecap] incident faces
+  uint32_t* count[2];          // [cellcap + 2]
+  uint32_t* start[2];          // [cellcap + 2]
+  uint32_t* ids[2];            // [paircap]
+  uint64_t* scan_state;        // [2 tiles]
+  uint32_t ecap;
+  int64_t cellcap, paircap, tiles;
+};
+
+__host__ __device__ inline size_t msdf_layout(int64_t nv, int64_t nf, char* base, Ws* w) {
+  uint32_t ecap = 64;
+  while ((int64_t)ecap < 4 * nf) ecap <<= 1;
+  const int64_t cellcap = kCellsPerFace * nf + 64, paircap = kPairsPerFace * nf + 64;
+  const int64_t n_bins = cellcap + 2, tiles = (n_bins + kScanTile - 1) / kScanTile;
+  size_t off = 0;
+  size_t o[14];
+  const size_t bytes[14] = {sizeof(Header), (size_t)nf * 48, (size_t)nv * 24, (size_t)nv * 4, (size_t)ecap * 8,
+                            (size_t)ecap * 24, (size_t)ecap * 4, (size_t)n_bins * 4, (size_t)n_bins * 4,
+                            (size_t)n_bins * 4, (size_t)n_bins * 4, (size_t)paircap * 4, (size_t)paircap * 4,
+                            (size_t)tiles * 2 * 8};
+  for (int k = 0; k < 14; ++k) {
+    o[k] = off;
+    off += (bytes[k] + 255) / 256 * 256;
+  }
+  if (w) {
+    w->H = (Header*)(base + o[0]);
+    w->tri = (float4*)(base + o[1]);
+    w->vacc = (long long*)(base + o[2]);
+    w->vflag = (uint32_t*)(base + o[3]);
+    w->ekey = (unsigned long long*)(base + o[4]);
+    w->eacc = (long long*)(base + o[5]);
+    w->ecnt = (uint32_t*)(base + o[6]);
+    w->count[0] = (uint32_t*)(base + o[7]);
+    w->start[0] = (uint32_t*)(base + o[8]);
+    w->count[1] = (uint32_t*)(base + o[9]);
+    w->start[1] = (uint32_t*)(base + o[10]);
+    w->ids[0] = (uint32_t*)(base + o[11]);
+    w->ids[1] = (uint32_t*)(base + o[12]);
+    w->scan_state = (uint64_t*)(base + o[13]);
+    w->ecap = ecap;
+    w->cellcap = cellcap;
+    w->paircap = paircap;
+    w->tiles = tiles;
+  }
+  return off;
+}
+
+__device__ __forceinline__ uint32_t f2ord(float x) {   // order-preserving float -> uint32
+  const uint32_t b = __builtin_bit_cast(uint32_t, x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t k) {
+  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+__device__ __forceinline__ int cell_axis(float x, double lo, double inv_h, int dim) {
+  double t = floor(((double)x - lo) * inv_h);
+  t = fmin(fmax(t, 0.0), (double)(dim - 1));
+  return (int)t;
+}
+
+}  // namespace
+}  // namespace bnv

@@ -900,6 +900,56 @@ int bnv_mesh_sdf_build(const float* vertices, int64_t n_vertices, const int32_t*
 int bnv_mesh_sdf_query(const void* workspace, int64_t ws_bytes, const float* query, int64_t n_query, float* sdf_out,
                        int32_t* face_out, float* closest_out, uint8_t* feature_out, bnv_stream_t stream);
 
+/* ---- Rays against a triangle mesh and the depth sensor model (bnv_fusion_amd/csrc/meshray.hip;
+ * bnv_fusion_amd/scan.py): scan a mesh into the depth sequence everything else here consumes.  The index is the one
+ * bnv_mesh_sdf_build makes (bnv_mesh_ray_workspace_bytes == bnv_mesh_sdf_workspace_bytes); it is only read.
+ *
+ * bnv_mesh_ray_cast.  origins, dirs fp32 [n_rays, 3] (device; dirs need not be unit) -> per ray the nearest hit
+ * o + t d with t in [t_min, t_max]: t_out fp32 (NaN: none), face_out int32 (-1: none), uv_out fp32 [n_rays, 2] with
+ * hit = (1 - u - v) v0 + u v1 + v v2 (NaN: none), flags_out uint8: BNV_MESH_RAY_HIT, | BNV_MESH_RAY_BACK when the ray
+ * meets the face from behind, d . ((v1 - v0) x (v2 - v0)) > 0.  The optional outputs may be NULL.  One thread per ray
+ * walks the fine grid cell by cell (3D-DDA, after clipping the ray to the grid's box); the ray / triangle test is the
+ * sheared-ray test of Woop, Benthin & Wald (2013) in fp32, one rounding per operation, an exactly zero edge function
+ * redone in float64: a ray through an edge or vertex shared by two faces hits one of them.  Two-sided.  The lowest
+ * face index wins a tie in t; the same inputs give the same bits.  A ray with a NaN / Inf component or a zero
+ * direction, and any ray against an index without a valid face, gets (NaN, -1, NaN, 0).
+ *
+ * bnv_mesh_render_depth.  The camera form, for n_poses <= BNV_MESH_RENDER_MAX_POSES poses in one launch: K_host fp32
+ * [9] row-major, poses_host fp32 [n_poses, 16] row-major camera-to-world (host).  The ray of pixel (u, v) has the
+ * front end's arithmetic: x = (u - cx) / fx, y = (v - cy) / fy, origin T[:3, 3], direction R (x, y, 1) =
+ * (R[a][0] x + R[a][1] y) + R[a][2] in fp32, so t is the z-depth the data sets store.  depth_out fp32 [n_poses, H, W]:
+ * the nearest hit's t in metres, 0 where there is none or it lies outside [near, max_depth) or is not positive;
+ * face_out int32 [n_poses, H, W] (NULL: not written; -1 where depth is 0); normals_out fp32 [n_poses, H, W, 3] (NULL:
+ * not written): the unit geometric normal in world coordinates turned towards the camera (0 where depth is 0); seen
+ * uint32 [n_seen] (NULL: none): += 1 at the face of every pixel with depth > 0 (integer atomics: order-free; faces >=
+ * n_seen are not counted).
+ *
+ * bnv_depth_sensor.  The reference's Simulator.simulate (src/utils/geometry.py:42-72) per output pixel (r, c) of a
+ * clean depth image fp32 [H, W] in metres -> out_mm uint16 [H, W]: x = clamp(rint(c + sigma_px n0)), y = clamp(rint(r
+ * + sigma_px n1)); d = clean[y - y % 2, x - x % 2]; with a table fp32 [80, 80, 5] (NULL: none) d = undistort(x, y, d)
+ * at table cell (y 80 / H, x 80 / W); d == 0 -> 0, else bf 8 / k with k = rint((bf / d + sigma_d n2) 8), k == 0 -> 0;
+ * out = trunc(metres * 1000).  rint is round-half-even.  n0, n1, n2 are standard normals: Philox4x32-10 with key (seed
+ * low word, seed high word) and counter (r W + c, frame, 0, 0) gives words w0 .. w3, uniforms ((w >> 9) + 0.5) 2^-23,
+ * n0 = sqrt(-2 ln u0) cos(2 pi u1), n1 = sqrt(-2 ln u0) sin(2 pi u1), n2 = sqrt(-2 ln u2) cos(2 pi u3) in fp32; the
+ * arithmetic after the draws is float64.  The reference's constants: bf 35.130, sigma_d 0.027778, sigma_px 0.25.
+ *
+ * Null pointers (other than the optional ones), counts and sizes <= 0 or out of range, t_min > t_max, near >
+ * max_depth, more than BNV_MESH_RENDER_MAX_POSES poses and a workspace smaller than an index are
+ * BNV_ERR_INVALID_ARGUMENT before any HIP call. */
+#define BNV_MESH_RAY_HIT 1
+#define BNV_MESH_RAY_BACK 2
+#define BNV_MESH_RENDER_MAX_POSES 8
+int bnv_mesh_ray_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t* bytes);
+int bnv_mesh_ray_cast(const void* workspace, int64_t ws_bytes, const float* origins, const float* dirs, int64_t n_rays,
+                      float t_min, float t_max, float* t_out, int32_t* face_out, float* uv_out, uint8_t* flags_out,
+                      bnv_stream_t stream);
+int bnv_mesh_render_depth(const void* workspace, int64_t ws_bytes, int n_poses, const float* K_host,
+                          const float* poses_host, int height, int width, float near, float max_depth,
+                          float* depth_out, int32_t* face_out, float* normals_out, uint32_t* seen, int64_t n_seen,
+                          bnv_stream_t stream);
+int bnv_depth_sensor(const float* clean, int height, int width, const float* table, uint64_t seed, uint32_t frame,
+                     double bf, double sigma_d, double sigma_px, uint16_t* out_mm, bnv_stream_t stream);
+
 /* ---- Rendering (bnv_fusion_amd/csrc/render.hip): depth and normal images of the map from a camera pose.  The
  * reference has no such entry; these are the semantics SparseVolume.render_depth / TSDFVolume.render_depth expose and
  * the tests replay in float32 (every operation below is one IEEE fp32 rounding, in the order written, sqrt and division
