@@ -34,6 +34,8 @@ from ._lib import BnvError  # noqa: F401
 from . import evaluate  # noqa: F401,E402
 from .evaluate import evaluate_meshes, nearest_neighbors, sample_surface  # noqa: F401,E402
 from .mesh import TriMesh, load_ply  # noqa: F401,E402
+from . import tracking  # noqa: F401,E402
+from .tracking import Tracker, icp_align  # noqa: F401,E402
 
 
 MLP_MODE_FP32_EXACT = 0     # v_mfma_f32_32x32x2_f32

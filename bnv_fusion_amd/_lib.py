@@ -43,6 +43,7 @@ SYMBOLS = [
     "bnv_train_tcnn_forward",
     "bnv_mesh_sdf_workspace_bytes", "bnv_mesh_sdf_build", "bnv_mesh_sdf_query",
     "bnv_mesh_ray_workspace_bytes", "bnv_mesh_ray_cast", "bnv_mesh_render_depth", "bnv_depth_sensor",
+    "bnv_icp_workspace_bytes", "bnv_icp_align",
 ]
 
 
@@ -313,6 +314,11 @@ def load():
                                             C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, i64, vp]),
         "bnv_depth_sensor": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_uint32, C.c_double, C.c_double,
                                        C.c_double, vp, vp]),
+        "bnv_icp_workspace_bytes": (sz, [i32, C.POINTER(i32)]),
+        "bnv_icp_align": (C.c_int, [vp, C.c_int, i32, i32, C.POINTER(C.c_double), C.c_double, vp, vp, i32, i32,
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), i32, C.POINTER(i32), C.c_double, C.c_double, C.c_double, vp,
+                                    sz, vp, vp, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

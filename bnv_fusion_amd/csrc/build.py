@@ -14,7 +14,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["encode.hip", "volume.hip", "decode.hip", "frontend.hip", "tsdf.hip", "mesh.hip", "rays.hip", "io.hip",
            "shard.hip", "pipeline.hip", "probe.hip", "eval.hip",
-           "render.hip", "meshpost.hip", "train.hip", "train_tcnn.hip", "meshsdf.hip", "meshray.hip"]
+           "render.hip", "meshpost.hip", "train.hip", "train_tcnn.hip", "meshsdf.hip", "meshray.hip",
+           "track.hip"]
 HEADERS = ["bnv_common.hpp", "frontend.hpp", "tcnn_mlp.hpp", "meshsdf.hpp", os.path.join("..", "..", "include", "bnv_fusion.h")]
 OUT = os.path.join(HERE, "..", "libbnv_fusion_hip.so")
 STAMP = OUT + ".sha256"

@@ -270,3 +270,18 @@ def depth_errors(pred, gt, threshold=0.025):
         return dict(res, median=float("nan"), mean=float("nan"), rmse=float("nan"), within=float("nan"))
     return dict(res, median=float(e.median()), mean=float(e.mean()), rmse=float(torch.sqrt((e * e).mean())),
                 within=float((e <= threshold).double().mean()))
+
+
+def trajectory_errors(est, gt):
+    """Absolute error of a trajectory against the true one, pose by pose and without any alignment of the two:
+    ``est``, ``gt`` [n, 4, 4] camera-to-world -> {"translation_rmse": metres, "rotation_mean_deg": the mean angle of
+    R_est^T R_gt, "translation_max", "rotation_max_deg", "n"}."""
+    est = np.asarray(est, dtype=np.float64).reshape(-1, 4, 4)
+    gt = np.asarray(gt, dtype=np.float64).reshape(-1, 4, 4)
+    if est.shape != gt.shape or len(est) == 0:
+        raise ValueError(f"trajectory_errors: {est.shape} against {gt.shape}")
+    dt = np.linalg.norm(est[:, :3, 3] - gt[:, :3, 3], axis=1)
+    tr = np.einsum("nij,nij->n", est[:, :3, :3], gt[:, :3, :3])
+    ang = np.degrees(np.arccos(np.clip((tr - 1.0) / 2.0, -1.0, 1.0)))
+    return {"translation_rmse": float(np.sqrt(np.mean(dt * dt))), "rotation_mean_deg": float(ang.mean()),
+            "translation_max": float(dt.max()), "rotation_max_deg": float(ang.max()), "n": int(len(est))}

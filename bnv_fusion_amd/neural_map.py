@@ -375,6 +375,19 @@ class NeuralMap:
         self._drain_pipe()
         return self.tsdf_vol.render_depth(T_wc, intr_mat, H, W, max_depth=self.max_depth, normals=normals)
 
+    def track(self, frame, T_guess=None, source="neural", model_size=None, **icp):
+        """Aligns a depth frame to the map: renders the map at ``T_guess`` (default ``frame['T_wc']``) through
+        ``render`` (``source="neural"``) or ``render_tsdf`` ("tsdf"), ``model_size`` = (H, W) of that view (default
+        the frame's; smaller is cheaper), and runs ``tracking.icp_align`` of the frame against it -> ``TrackResult``
+        (``.T_wc``: the corrected camera-to-world pose, or the guess when ``.status`` is not OK).  Reads the map only;
+        waits for the frames still in the pipeline, as ``render`` does."""
+        from . import tracking
+        if source not in ("neural", "tsdf"):
+            raise ValueError(f"source {source!r}: 'neural' or 'tsdf'")
+        render = self.render if source == "neural" else self.render_tsdf
+        icp.setdefault("max_depth", self.max_depth)
+        return tracking.track_against(render, frame, T_guess, model_size, **icp)
+
     def save(self, working_dir, scan_id="scan"):
         """run_e2e.py:188-194: the TSDF volume as <scan_id>.npy (metres) and the feature volume as
         final_sparse_volume.pth (sparse_volume.py:835-860)."""

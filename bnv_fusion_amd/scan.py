@@ -110,6 +110,18 @@ class MeshScanner:
         out = (depth, face, nrm) if normals else (depth, face)
         return tuple(t[0] for t in out) if single else out
 
+    def track(self, frame, T_guess=None, model_size=None, **icp):
+        """Localises a depth frame against the mesh: renders it at ``T_guess`` (default ``frame['T_wc']``; view of
+        ``model_size`` = (H, W), default the frame's; ``.seen`` is not counted) and aligns the frame to that view
+        (``tracking.icp_align``) -> ``TrackResult``."""
+        from . import tracking
+        max_depth = icp.pop("max_depth", 3.0)
+
+        def render(T, K, H, W):
+            depth, _, nrm = self.render_depth(T, K, H, W, max_depth=max_depth, normals=True, count_seen=False)
+            return depth, nrm
+        return tracking.track_against(render, frame, T_guess, model_size, max_depth=max_depth, **icp)
+
     def visible_mesh(self, min_pixels=1):
         """The faces seen by at least ``min_pixels`` pixels since construction or ``reset_seen`` -> TriMesh (host) with
         the vertices they use: the ground truth for recall."""
@@ -171,6 +183,22 @@ def scan_frames(scanner, poses, K, H, W, noise=None, seed=0, max_depth=math.inf,
             i = s + j
             d = simulate_sensor(depth[j], seed, i, table=table) if noise == "kinect" else to_u16(depth[j], rounding)
             yield {"frame_id": i, "depth": d, "intr_mat": K.copy(), "T_wc": poses[i].copy()}
+
+
+def drift_poses(poses, sigma_t, sigma_r, seed=0):
+    """Odometry that drifts: every relative motion ``T_{i-1}^-1 T_i`` of ``poses`` ([n, 4, 4]) is followed by a small
+    random motion exp((w, v)) in the camera's frame, w ~ N(0, sigma_r^2) radians and v ~ N(0, sigma_t^2) metres per
+    axis, and the perturbed motions are chained from the first pose, which stays exact: a random walk, as a phone's
+    odometry drifts.  ``numpy.random.Generator(PCG64(seed))``: the same seed gives the same poses -> float64
+    [n, 4, 4]."""
+    from .tracking import rigid_inverse, se3_exp
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    out = [poses[0].copy()]
+    for i in range(1, len(poses)):
+        noise = rng.standard_normal(6) * np.array([sigma_r] * 3 + [sigma_t] * 3, dtype=np.float64)
+        out.append(out[-1] @ (rigid_inverse(poses[i - 1]) @ poses[i]) @ se3_exp(noise))
+    return np.stack(out)
 
 
 def look_at_pose(eye, target, down=(0.0, 1.0, 0.0)):

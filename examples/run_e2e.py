@@ -6,6 +6,8 @@ sequence directory, periodic global optimisation, mesh extraction, final artefac
     python examples/run_e2e.py ... --tsdf-mesh --eval-gt GT.ply                            # + the TSDF baseline, both scored
     python examples/run_e2e.py --arkit --data-dir DATA --scan-id room --tiny-cuda           # an iPhone / iPad LiDAR capture
     python examples/run_e2e.py --synthetic-arkit 24 --out /tmp/bnv_arkit                    # writes a synthetic one first
+    python examples/run_e2e.py --sweep 60 --grid 256 --pose-drift 0.005 0.003 --track tsdf --no-optimize --out /tmp/trk
+                                                    # drifting odometry, every frame aligned to the map before it is fused
     python examples/run_e2e.py --sweep 600 --grid 512 --decode-frames --pipelined --no-optimize --out /tmp/sweep
                                                     # a moving-camera room sweep (bnv_fusion_amd/sequence.py), per-frame
                                                     # SDF decode of the touched voxels, two frames in flight
@@ -74,6 +76,17 @@ def main():
     ap.add_argument("--render", metavar="DIR",
                     help="after the run, render the map at every key frame's pose into DIR (16-bit PNGs, millimetres) "
                          "and print the mean depth errors against the observed frames")
+    ap.add_argument("--track", choices=["neural", "tsdf"],
+                    help="align every frame to the map built so far before fusing it (tracking.Tracker: frame-to-model "
+                         "ICP against a render of the neural volume or of the TSDF side volume; the given poses serve "
+                         "as odometry).  Off by default: poses are taken as given")
+    ap.add_argument("--track-view", type=int, nargs=2, metavar=("H", "W"),
+                    help="--track: size of the rendered model view (default: the frame's)")
+    ap.add_argument("--pose-drift", type=float, nargs=2, metavar=("SIGMA_T", "SIGMA_R"),
+                    help="replace the poses by drifting odometry (scan.drift_poses: a random walk of SIGMA_T metres and "
+                         "SIGMA_R radians per frame and axis, seed 0); the frames are held in memory.  With --track the "
+                         "run fuses a second map from the drifted poses as they are and prints trajectory_errors (and, "
+                         "with --eval-gt, the F-score) of both")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     dev = "cuda:0"
@@ -111,6 +124,16 @@ def main():
                        max_depth=data.max_depth)
     t_local = t_global = 0.0
     max_depth = data.max_depth
+    truth = tracker = None
+    if args.pose_drift:
+        from bnv_fusion_amd import scan
+        data = [fr for fr in data if not np.isnan(fr["T_wc"]).any()]
+        truth = np.stack([np.asarray(fr["T_wc"], dtype=np.float64) for fr in data])
+        drifted = scan.drift_poses(truth, args.pose_drift[0], args.pose_drift[1], seed=0)
+        data = [dict(fr, T_wc=T) for fr, T in zip(data, drifted)]
+    if args.track:
+        from bnv_fusion_amd import tracking
+        tracker = tracking.Tracker(nm, source=args.track, model_size=args.track_view)
     if args.decode_frames:
         # the per-frame loop of the benchmark metric: fuse + decode of the touched voxels, synchronous or pipelined
         from bnv_fusion_amd import sequence
@@ -123,7 +146,11 @@ def main():
         t_local = st["seconds"]
     for idx, frame in enumerate(data):                                   # run_e2e.py:243-279
         t0 = time.perf_counter()
-        nm.integrate(frame)
+        if tracker is not None and not np.isnan(frame["T_wc"]).any():
+            tracker.integrate(frame)
+            frame = dict(frame, T_wc=tracker.poses[-1])              # the optimiser's rays start at the corrected pose
+        else:
+            nm.integrate(frame)
         torch.cuda.synchronize()
         t_local += time.perf_counter() - t0
         if np.isnan(frame["T_wc"]).any():
@@ -144,6 +171,11 @@ def main():
             if mesh is not None:                                             # :277-280
                 mesh.export(os.path.join(args.out, f"{idx}.ply"))
     mesh = nm.extract_mesh(os.path.join(args.out, "before_optim.ply"))   # :280-282
+    if tracker is not None:
+        print(f"tracking ({args.track}): {tracker.failures} of {len(tracker.poses)} frames refused by the aligner "
+              "(fused with the predicted pose)")
+    if tracker is not None and truth is not None:
+        compare_given_and_tracked(args, data, truth, tracker, mesh, model, nm, dev)
     steps = int(len(nm.frames) * args.skip_images) * (1 if args.mode == "demo" else 2)   # :283-284
     if not args.no_optimize:
         t0 = time.perf_counter()
@@ -180,6 +212,28 @@ def main():
         render_key_frames(nm, args.render, max_depth)
     print(f"{len(nm.frames)} frames, {nm.volume.num_rows()} voxels, "
           f"{0 if mesh is None else len(mesh.faces)} triangles -> {args.out}")
+
+
+def compare_given_and_tracked(args, frames, truth, tracker, tracked_mesh, model, nm, dev):
+    """--pose-drift with --track: the same frames fused once more with the drifted poses as they are; prints
+    evaluate.trajectory_errors of both trajectories and, with --eval-gt, the F-score of both maps' meshes."""
+    from bnv_fusion_amd import evaluate
+    from bnv_fusion_amd.mesh import load_ply
+    plain = bnv.NeuralMap(nm.dimensions, args.voxel_size, model, capacity=1 << 20, device=dev, tsdf=True,
+                          max_depth=nm.max_depth)
+    for fr in frames:
+        plain.integrate(fr)
+    given = np.stack([fr["T_wc"] for fr in frames])
+    for name, poses in (("given", given), ("tracked", np.stack(tracker.poses))):
+        e = evaluate.trajectory_errors(poses, truth)
+        print(f"trajectory ({name} poses): translation RMSE {e['translation_rmse'] * 1e3:.2f} mm, mean rotation error "
+              f"{e['rotation_mean_deg']:.3f} deg over {e['n']} frames")
+    if args.eval_gt:
+        gt = load_ply(args.eval_gt)
+        for name, m in (("given", plain.extract_mesh()), ("tracked", tracked_mesh)):
+            if m is not None:
+                res = evaluate.evaluate_meshes(m, gt, generator=torch.Generator(device=dev).manual_seed(0), device=dev)
+                print(evaluate.summary_line(res), f"({name} poses, before optimisation)")
 
 
 def render_key_frames(nm, out_dir, max_depth):

@@ -1118,6 +1118,86 @@ int bnv_train_tcnn_forward(const float* params, const float* input_pts, const fl
                            int32_t n, int64_t M, float* feats, float* pred, void* workspace, size_t ws_bytes,
                            bnv_stream_t stream);
 
+/* ---- Tracking (bnv_fusion_amd/csrc/track.hip; bnv_fusion_amd/tracking.py): frame-to-model ICP.  Aligns a depth frame
+ * to a view of the map -- the depth and world normals bnv_render_depth, bnv_tsdf_render_depth or
+ * bnv_mesh_render_depth wrote -- by projective point-to-plane ICP and returns the corrected camera-to-world pose.  The
+ * reference takes every pose as given and has no such entry; tests/track_restatement.py restates what follows in
+ * numpy.  Every operation is one IEEE float64 rounding, in the order written (no contraction); division and sqrt are
+ * correctly rounded.
+ *
+ * Inputs.  depth [H, W] (device): depth_dtype 0 = uint16 millimetres, d = (double)mm / 1000.0; 1 = float32 metres,
+ * d = (double)m (the front end's conversions).  K_host float64 [9] row-major: fx = K[0], cx = K[2], fy = K[4],
+ * cy = K[5].  The model view: model_depth f32 [H_m, W_m] z-depth in metres, 0 = nothing; model_normals f32
+ * [H_m, W_m, 3] world frame, pointing to the free-space side, 0 = none; K_m_host its intrinsics; T_m_host float64 [16]
+ * row-major its camera-to-world pose and T_m_inv_host the inverse [R^T, -R^T t], both from the caller.  T_guess_host:
+ * the frame's camera-to-world pose to start from.  All matrices are host arrays; the images are only read.
+ *
+ * Schedule.  levels_host int32 [n_levels][2] = (stride, iterations), 1 <= n_levels <= BNV_ICP_MAX_LEVELS, stride >= 1,
+ * iterations >= 0, at least one and at most 4096 iterations in all; tracking.DEFAULT_LEVELS is ((4, 4), (2, 5),
+ * (1, 10)).  At stride s the sampled pixels are (u, v) = (s i, s j), i < ceil(W / s), j < ceil(H / s), numbered
+ * j ceil(W / s) + i; association always goes into the full model view.  No filtered pyramid, no early termination:
+ * n_iter = the sum of the iterations is fixed.
+ *
+ * A pair.  At the current estimate T = [R | t], sampled pixel (u, v) with depth d:
+ *   valid iff 0 < d <= max_depth;  x = (u - cx) / fx,  y = (v - cy) / fy,  p_c = (x d, y d, d);
+ *   p_w_a = ((R[a][0] p_c0 + R[a][1] p_c1) + R[a][2] p_c2) + t_a;   p_m = T_m_inv p_w in the same form;
+ *   reject unless p_m2 > 0;   u' = rint(fx_m p_m0 / p_m2 + cx_m),  v' = rint(fy_m p_m1 / p_m2 + cy_m)  (half to even);
+ *   reject unless 0 <= u' <= W_m - 1 and 0 <= v' <= H_m - 1;   d_m = model_depth(v', u'): reject unless d_m > 0 and
+ *   finite;   n = model_normals(v', u'): reject when all three components are 0;
+ *   q = T_m ((u' - cx_m) / fx_m d_m, (v' - cy_m) / fy_m d_m, d_m) in the form of p_w;   e = q - p_w;
+ *   gates: (e0 e0 + e1 e1) + e2 e2 <= dist dist, and (n0 (t0 - q0) + n1 (t1 - q1)) + n2 (t2 - q2) > 0: the model's
+ *   surface faces the frame's camera.  No robust weights: the gates are the outlier rule.
+ *   r = (n0 e0 + n1 e1) + n2 e2 (a pair whose r is not finite is rejected),  J = [p_w x n, n] with
+ *   (p_w x n)_0 = p_w1 n2 - p_w2 n1 and cyclic.  The twist xi = (w, v) multiplies on the left: T <- exp(xi^) T.
+ * Sums.  BNV_ICP_SUMS = 29 float64 sums over the pairs: J_a J_b for a <= b row by row (21), J_a r (6), r r, 1.
+ * A grid of BNV_ICP_BLOCKS blocks of 256 threads whatever the image; thread g takes the sampled pixels g, g + G, ...
+ * (G = 256 BNV_ICP_BLOCKS) in that order; lanes are added by s += shfl_down(s, o) for o = 32, 16, ..., 1, the block's
+ * four waves in wave order, the blocks in ascending order.  No float atomics: the same inputs give the same bits.
+ *
+ * Solve (a one-block launch per iteration).  pairs = the last sum, rmse = sqrt(sum r r / pairs) (0 without pairs).
+ *   BNV_ICP_LOST        pairs == 0 or pairs < min_pair_share (sampled pixels of the level);
+ *   BNV_ICP_DEGENERATE  spread < min_spread, spread = the smallest eigenvalue of A[3:, 3:] / pairs = (1 / pairs) sum
+ *                       n n^T (six sweeps of cyclic Jacobi over (0,1), (0,2), (1,2)): the normals span too few
+ *                       directions to hold the translation; or a pivot of the factorisation <= 0;
+ *   BNV_ICP_JUMP        |w| > BNV_ICP_MAX_ROTATION or |v| > BNV_ICP_MAX_TRANSLATION;
+ * tested in this order.  A xi = b by LDL^T without pivoting, column by column: D_j = A_jj - sum_k<j (L_jk L_jk) D_k,
+ * L_ij = (A_ij - sum_k<j (L_ik L_jk) D_k) / D_j (k ascending), then L z = b, z_i / D_i, L^T xi = z.  exp(xi^) by
+ * Rodrigues: th = |w|, K = [w]x, R = (I + a K) + b K K, V = (I + b K) + c K K, a = sin th / th, b = (1 - cos th) / th^2,
+ * c = (th - sin th) / (th^2 th); below th < 1e-8 a = 1 - th^2 / 6, b = 0.5 - th^2 / 24, c = 1 / 6 - th^2 / 120.
+ * T <- [R R_T | (R t_T) + V v], in device memory.
+ * A status other than BNV_ICP_OK is sticky: the launch that finds it writes the status and sets pose_out back to
+ * T_guess, bit for bit, and every later launch of the call returns right after reading the status.  Nothing is read
+ * by the host between the first and the last launch, nothing is allocated or synchronised: the call can be captured
+ * into a graph.
+ *
+ * Outputs (device).  pose_out f64 [16]; poses_out f64 [n_iter + 1, 16] or NULL: the estimate before every iteration
+ * and the final one (rows the call did not reach hold T_guess); stats_out f64 [n_iter, 5] = pairs, rmse, |w|, |v|,
+ * spread per iteration (0 for what was not computed; rows after a stop are 0); status_out int32 [1].
+ * Workspace: bnv_icp_workspace_bytes(n_levels, levels_host) bytes (0 for an invalid schedule): the blocks' partial
+ * rows f64 [BNV_ICP_BLOCKS, 29], then one record f64 [BNV_ICP_RECORD_DOUBLES] per iteration = the 29 sums, xi[6] and
+ * a pad, for tests and diagnosis.
+ * Null pointers (poses_out excepted), sizes <= 0 or > 32768, an invalid schedule, depth_dtype other than 0 / 1,
+ * non-finite matrices, a zero focal length, max_depth or dist not positive and finite and negative or non-finite
+ * thresholds are BNV_ERR_INVALID_ARGUMENT before any HIP call; a workspace below bnv_icp_workspace_bytes is
+ * BNV_ERR_WORKSPACE_TOO_SMALL. */
+#define BNV_ICP_OK 0
+#define BNV_ICP_LOST 1
+#define BNV_ICP_DEGENERATE 2
+#define BNV_ICP_JUMP 3
+#define BNV_ICP_MAX_LEVELS 8
+#define BNV_ICP_BLOCKS 256
+#define BNV_ICP_SUMS 29
+#define BNV_ICP_RECORD_DOUBLES 36
+#define BNV_ICP_MAX_ROTATION 0.1      /* radians per iteration */
+#define BNV_ICP_MAX_TRANSLATION 0.2   /* metres per iteration */
+size_t bnv_icp_workspace_bytes(int32_t n_levels, const int32_t* levels_host);
+int bnv_icp_align(const void* depth, int depth_dtype, int32_t H, int32_t W, const double K_host[9], double max_depth,
+                  const float* model_depth, const float* model_normals, int32_t H_m, int32_t W_m,
+                  const double K_m_host[9], const double T_m_host[16], const double T_m_inv_host[16],
+                  const double T_guess_host[16], int32_t n_levels, const int32_t* levels_host, double dist,
+                  double min_pair_share, double min_spread, void* workspace, size_t ws_bytes, double* pose_out,
+                  double* poses_out, double* stats_out, int32_t* status_out, bnv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
