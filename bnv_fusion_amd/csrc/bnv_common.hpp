@@ -105,6 +105,9 @@ struct ProfScope {
 
 #define BNV_LAUNCH_CHECK() BNV_HIP_CHECK(hipGetLastError())
 
+// size of a workspace piece: every piece starts on a 256-byte boundary
+__host__ __device__ inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+
 // Corner order of get_neighbors (modules.py:590-655): bit0 = x uses ceil, bit1 = y, bit2 = z.
 __device__ __constant__ const unsigned char kCornerCeilBits[8] = {0, 1, 2, 4, 3, 5, 6, 7};
 

@@ -7,15 +7,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
 #include <atomic>
 
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
+#include "cell_grid.hpp"
 
 namespace bnv {
-
-static inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 // =====================================================================================================================
 // Surface sampling (trimesh.sample.sample_surface)
@@ -185,16 +183,13 @@ __global__ __launch_bounds__(256) void k_sample_surface(const float* __restrict_
 // =====================================================================================================================
 // Exact nearest neighbour on a uniform grid
 // =====================================================================================================================
-// Cell size rule.  The inputs are surface samples: n points on an area A occupy ~A / h^2 cells of edge h, so
-// h = sqrt(kCellTarget * A / n) puts ~kCellTarget points in an occupied cell.  A is estimated by half the bounding
-// box's surface, Lx Ly + Ly Lz + Lz Lx (a height field: ~its area; a closed room: half of it).  A set with no area
-// (a line: h = kCellTarget * L / n; a point: h = 1) and volumetric sets (the estimate asks for far more cells than
-// points) are covered by the cap: h grows by 5/4 until the grid has at most max(n_ref, 1) cells.
+// Cell size (cell_grid.hpp: grid_cell_edge): the inputs are surface samples, ~kCellTarget of them in an occupied cell.
+// Volumetric sets (the area estimate asks for far more cells than points) are covered by the cap: h grows by 5/4 until
+// the grid has at most max(n_ref, 1) cells.
 constexpr double kCellTarget = 4.0;
 constexpr double kStopSlack = 1e-5;    // relative slack of the stop test (fp32 d^2 carries ~4 ulp of rounding)
 constexpr int kFineRings = 8;          // rings of the fine grid before a query moves on to the coarse grid
 constexpr double kCoarse = 4.0;        // coarse cell edge / fine cell edge
-constexpr int kScanThreads = 256, kScanItems = 4, kScanTile = kScanThreads * kScanItems;
 constexpr uint32_t kNoCell = 0xffffffffu;
 
 struct NnParams {
@@ -204,6 +199,7 @@ struct NnParams {
   double lo[3], fmin[3], fmax[3];
   double h, inv_h;
 };
+static_assert(offsetof(NnParams, bmin) == 0 && offsetof(NnParams, bmax) == 12, "grid_bbox writes the first six words");
 
 struct NnWs {
   NnParams* P;           // [2]: the fine grid, the coarse grid
@@ -270,58 +266,6 @@ static size_t nn_ws_layout(int64_t n_ref, int64_t n_query, char* base, NnWs* w) 
   return off;
 }
 
-__device__ __forceinline__ uint32_t f2ord(float x) {   // order-preserving float -> uint32
-  const uint32_t b = __builtin_bit_cast(uint32_t, x);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t k) {
-  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  return isfinite(x) && isfinite(y) && isfinite(z);
-}
-
-// bounding box of the finite reference points: a wave reduction, the block's waves through LDS, one integer-encoded
-// atomic min / max per component per block
-__global__ __launch_bounds__(256) void k_nn_bbox(const float* __restrict__ R, int64_t n, NnParams* __restrict__ P) {
-  uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float x = R[i * 3], y = R[i * 3 + 1], z = R[i * 3 + 2];
-    if (!finite3(x, y, z)) continue;
-    const uint32_t k[3] = {f2ord(x), f2ord(y), f2ord(z)};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      mn[d] = min(mn[d], k[d]);
-      mx[d] = max(mx[d], k[d]);
-    }
-  }
-#pragma unroll
-  for (int d = 0; d < 3; ++d)
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-      mn[d] = min(mn[d], (uint32_t)__shfl_xor((int)mn[d], s, 64));
-      mx[d] = max(mx[d], (uint32_t)__shfl_xor((int)mx[d], s, 64));
-    }
-  __shared__ uint32_t s_mn[4][3], s_mx[4][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-    for (int d = 0; d < 3; ++d) {
-      s_mn[wave][d] = mn[d];
-      s_mx[wave][d] = mx[d];
-    }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int d = threadIdx.x;
-    uint32_t a = s_mn[0][d], b = s_mx[0][d];
-    for (int w = 1; w < 4; ++w) {
-      a = min(a, s_mn[w][d]);
-      b = max(b, s_mx[w][d]);
-    }
-    atomicMin(&P->bmin[d], a);
-    atomicMax(&P->bmax[d], b);
-  }
-}
-
 // the grid of cell size h (grown by 5/4 until it has at most `cap` cells) over the bounding box in P
 __device__ void nn_grid(NnParams* __restrict__ P, const double L[3], double h, double cap) {
   double dims[3];
@@ -356,13 +300,8 @@ __global__ void k_nn_params(NnParams* __restrict__ P, int64_t n_ref) {
     P->fmax[d] = (double)ord2f(P->bmax[d]);
     L[d] = P->fmax[d] - P->fmin[d];
   }
-  const double n = (double)n_ref;
-  const double S = L[0] * L[1] + L[1] * L[2] + L[2] * L[0];
-  const double Lmax = fmax(L[0], fmax(L[1], L[2]));
-  double h = S > 0.0 ? sqrt(kCellTarget * S / n) : (Lmax > 0.0 ? kCellTarget * Lmax / n : 1.0);
-  if (!(h > 0.0) || !isfinite(h)) h = Lmax > 0.0 && isfinite(Lmax) ? Lmax : 1.0;
-  const double cap = fmax(n, 1.0);
-  nn_grid(P, L, h, cap);
+  const double cap = fmax((double)n_ref, 1.0);
+  nn_grid(P, L, grid_cell_edge(L, n_ref, kCellTarget), cap);
   for (int d = 0; d < 3; ++d) {
     P[1].bmin[d] = P->bmin[d];
     P[1].bmax[d] = P->bmax[d];
@@ -371,12 +310,6 @@ __global__ void k_nn_params(NnParams* __restrict__ P, int64_t n_ref) {
     P[1].fmax[d] = P->fmax[d];
   }
   nn_grid(P + 1, L, P->h * kCoarse, cap);
-}
-
-__device__ __forceinline__ int cell_axis(float x, double lo, double inv_h, int dim) {
-  double t = floor(((double)x - lo) * inv_h);
-  t = fmin(fmax(t, 0.0), (double)(dim - 1));
-  return (int)t;
 }
 
 // cell of every point (query: the clamped cell; non-finite: the extra bucket n_cells) and its slot in the cell.  The
@@ -398,34 +331,6 @@ __global__ __launch_bounds__(256) void k_nn_count(const float* __restrict__ X, i
   }
   cell_of[i] = c;
   if (c != kNoCell) slot_of[i] = atomicAdd(&count[c], 1u);
-}
-
-// exclusive scan of count[0 .. n_bins) -> start (bnv_common.hpp's uint32 block scan + decoupled look-back)
-__global__ __launch_bounds__(kScanThreads) void k_nn_scan(const uint32_t* __restrict__ count, int64_t n_bins,
-                                                          uint32_t* __restrict__ start, uint64_t* __restrict__ state,
-                                                          uint32_t epoch) {
-  __shared__ uint32_t wave_tot[kScanThreads / 64];
-  __shared__ uint32_t s_excl;
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  uint32_t v[kScanItems], s = 0;
-#pragma unroll
-  for (int e = 0; e < kScanItems; ++e) {
-    v[e] = base + e < n_bins ? count[base + e] : 0u;
-    s += v[e];
-  }
-  uint32_t total;
-  uint32_t run = block_exclusive_scan<kScanThreads>(s, wave_tot, &total);
-  if (threadIdx.x < 64) {
-    const uint32_t excl = lookback_exclusive(state, (int)blockIdx.x, total, epoch);
-    if (threadIdx.x == 0) s_excl = excl;
-  }
-  __syncthreads();
-  run += s_excl;
-#pragma unroll
-  for (int e = 0; e < kScanItems; ++e) {
-    if (base + e < n_bins) start[base + e] = run;
-    run += v[e];
-  }
 }
 
 __global__ __launch_bounds__(256) void k_nn_scatter(const float* __restrict__ X, int64_t n,
@@ -452,35 +357,12 @@ __device__ __forceinline__ float nn_d2(float qx, float qy, float qz, const float
   return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
-// Can the search stop after ring r?  A point of an unvisited cell lies beyond one face of the box of visited cells on
-// some axis a (by at least the query's distance to that face, minus a slack for the rounding of the cell assignment)
-// and inside the reference bounding box on the other axes.  Stop when that lower bound on the real d^2 exceeds the best
-// fp32 d^2 by the relative slack (continue while it is <=), or when the ring covers the grid.
+// Can the search stop after ring r?  When the ring covers the grid, or when the lower bound on the real d^2 to every
+// unvisited point (cell_grid.hpp: grid_ring_bound) exceeds the best fp32 d^2 by the relative slack (continue while it
+// is <=).
 __device__ __forceinline__ bool nn_can_stop(const NnParams& P, const int c[3], int r, const double q[3], float best) {
-  double gd2[3], base = 0.0;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const double g = fmax(fmax(P.fmin[d] - q[d], q[d] - P.fmax[d]), 0.0);
-    gd2[d] = g * g;
-    base += gd2[d];
-  }
-  double lb = INFINITY;
-  bool open = false;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const double slack = 1e-12 * (fabs(q[d]) + fabs(P.lo[d]) + (double)P.dims[d] * P.h) + 1e-9 * P.h;
-    if (c[d] - r > 0) {
-      open = true;
-      const double f = fmax(q[d] - (P.lo[d] + (double)(c[d] - r) * P.h) - slack, 0.0);
-      lb = fmin(lb, f * f + (base - gd2[d]));
-    }
-    if (c[d] + r < P.dims[d] - 1) {
-      open = true;
-      const double f = fmax((P.lo[d] + (double)(c[d] + r + 1) * P.h) - q[d] - slack, 0.0);
-      lb = fmin(lb, f * f + (base - gd2[d]));
-    }
-  }
-  if (!open) return true;
+  double lb;
+  if (!grid_ring_bound(P.lo, P.fmin, P.fmax, P.dims, P.h, c, r, q, lb)) return true;
   return lb > (double)best * (1.0 + kStopSlack) + 1e-30;
 }
 
@@ -492,31 +374,12 @@ __device__ __forceinline__ bool nn_rings(const NnParams& P, const uint32_t* __re
   const int c[3] = {cell_axis(qv.x, P.lo[0], P.inv_h, P.dims[0]), cell_axis(qv.y, P.lo[1], P.inv_h, P.dims[1]),
                     cell_axis(qv.z, P.lo[2], P.inv_h, P.dims[2])};
   for (int r = 0; r <= rmax; ++r) {
-    const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, P.dims[0] - 1);
-    const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, P.dims[1] - 1);
-    const int zl = c[2] - r, zh = c[2] + r;
-    for (int x = x0; x <= x1; ++x)
-      for (int y = y0; y <= y1; ++y) {
-        const bool shell = x == c[0] - r || x == c[0] + r || y == c[1] - r || y == c[1] + r;
-        // the ring's cells of this (x, y) column: a contiguous z-run on the shell, else its two ends
-        for (int part = 0; part < (shell ? 1 : 2); ++part) {
-          int za, zb;
-          if (shell) {
-            za = max(zl, 0);
-            zb = min(zh, P.dims[2] - 1);
-          } else {
-            za = zb = part == 0 ? zl : zh;
-            if (za < 0 || za >= P.dims[2]) continue;
-          }
-          if (za > zb) continue;
-          const int64_t col = ((int64_t)x * P.dims[1] + y) * P.dims[2];
-          const uint32_t e = rstart[col + zb + 1];
-          for (uint32_t k = rstart[col + za]; k < e; ++k) {
-            const float4 rv = Rs[k];
-            nn_take(nn_d2(qv.x, qv.y, qv.z, rv), __builtin_bit_cast(int32_t, rv.w), best, bi);
-          }
-        }
+    grid_ring(c, r, P.dims, rstart, [&](uint32_t k0, uint32_t k1) {
+      for (uint32_t k = k0; k < k1; ++k) {
+        const float4 rv = Rs[k];
+        nn_take(nn_d2(qv.x, qv.y, qv.z, rv), __builtin_bit_cast(int32_t, rv.w), best, bi);
       }
+    });
     if (nn_can_stop(P, c, r, q, best)) return true;
   }
   return false;
@@ -611,17 +474,13 @@ int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_
   const int64_t n_bins = n_ref + 2;
   const int64_t tiles = (n_bins + kScanTile - 1) / kScanTile;
   // everything the build accumulates into starts from a known state on every call (also when replayed from a graph):
-  // the bounding box, the counts, the look-back words (0 = an epoch next_epoch never hands out)
-  BNV_HIP_CHECK(hipMemsetAsync(w.P, 0, 2 * sizeof(NnParams), s));
-  BNV_HIP_CHECK(hipMemsetAsync(w.P, 0xff, 3 * sizeof(uint32_t), s));   // bmin (first member) = the largest key
+  // the counts, the look-back words (0 = an epoch next_epoch never hands out), the bounding box (grid_bbox)
   BNV_HIP_CHECK(hipMemsetAsync(w.ref_count, 0, (size_t)n_bins * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(w.q_count, 0, (size_t)n_bins * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(w.rc_count, 0, (size_t)n_bins * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(w.scan_state, 0, (size_t)tiles * 3 * 8, s));
-  const unsigned bbox_blocks = (unsigned)std::min<int64_t>((n_ref + 255) / 256, 2048);
   const dim3 ref_blocks((unsigned)((n_ref + 255) / 256)), q_blocks((unsigned)((n_query + 255) / 256));
-  hipLaunchKernelGGL(k_nn_bbox, dim3(bbox_blocks), dim3(256), 0, s, ref, n_ref, w.P);
-  BNV_LAUNCH_CHECK();
+  if (const int e = grid_bbox(ref, n_ref, w.P, 2 * sizeof(NnParams), s)) return e;
   hipLaunchKernelGGL(k_nn_params, dim3(1), dim3(64), 0, s, w.P, n_ref);
   BNV_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_nn_count, ref_blocks, dim3(256), 0, s, ref, n_ref, w.P, 0, w.ref_count, w.ref_cell, w.ref_slot);
@@ -633,7 +492,7 @@ int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_
   uint32_t* counts[3] = {w.ref_count, w.rc_count, w.q_count};
   uint32_t* starts[3] = {w.ref_start, w.rc_start, w.q_start};
   for (int k = 0; k < 3; ++k) {
-    hipLaunchKernelGGL(k_nn_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, counts[k], n_bins, starts[k],
+    hipLaunchKernelGGL(k_grid_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, counts[k], n_bins, starts[k],
                        w.scan_state + k * tiles, next_epoch());
     BNV_LAUNCH_CHECK();
   }

@@ -31,8 +31,6 @@ struct PostHdr {
   int32_t n_unique, n_clusters, n_vout, n_fout, error, pad[3];
 };
 
-static inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 static inline uint64_t hash_slots(int64_t T) {
   uint64_t h = 64;
   while (h < 2 * (uint64_t)T) h <<= 1;

@@ -16,8 +16,6 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
 #include "meshsdf.hpp"
@@ -34,46 +32,6 @@ __device__ __forceinline__ unsigned long long edge_key(int32_t a, int32_t b) {
 // =====================================================================================================================
 // Index build
 // =====================================================================================================================
-// bounding box of the finite vertices (eval.hip's k_nn_bbox: wave reduction, LDS, one integer atomic per block)
-__global__ __launch_bounds__(256) void k_msdf_bbox(const float* __restrict__ V, int64_t n, Header* __restrict__ H) {
-  uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float x = V[i * 3], y = V[i * 3 + 1], z = V[i * 3 + 2];
-    if (!finite3(x, y, z)) continue;
-    const uint32_t k[3] = {f2ord(x), f2ord(y), f2ord(z)};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      mn[d] = min(mn[d], k[d]);
-      mx[d] = max(mx[d], k[d]);
-    }
-  }
-#pragma unroll
-  for (int d = 0; d < 3; ++d)
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-      mn[d] = min(mn[d], (uint32_t)__shfl_xor((int)mn[d], s, 64));
-      mx[d] = max(mx[d], (uint32_t)__shfl_xor((int)mx[d], s, 64));
-    }
-  __shared__ uint32_t s_mn[4][3], s_mx[4][3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-    for (int d = 0; d < 3; ++d) {
-      s_mn[wave][d] = mn[d];
-      s_mx[wave][d] = mx[d];
-    }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int d = threadIdx.x;
-    uint32_t a = s_mn[0][d], b = s_mx[0][d];
-    for (int w = 1; w < 4; ++w) {
-      a = min(a, s_mn[w][d]);
-      b = max(b, s_mx[w][d]);
-    }
-    atomicMin(&H->bmin[d], a);
-    atomicMax(&H->bmax[d], b);
-  }
-}
-
 // The ladder of candidate grids over the bounding box.  Which level is used is decided once the (triangle, cell) pairs
 // of every level are counted (k_msdf_pick): the workspace is a function of the two counts alone, so the grid adapts to
 // it, not the other way round.
@@ -90,11 +48,8 @@ __global__ void k_msdf_levels(Header* __restrict__ H, int64_t n_vertices, int64_
       L[d] = H->fmax[d] - H->fmin[d];
     }
   }
-  const double n = (double)n_faces;
-  const double S = L[0] * L[1] + L[1] * L[2] + L[2] * L[0];
   const double Lmax = fmax(L[0], fmax(L[1], L[2]));
-  double h = S > 0.0 ? sqrt(kCellTarget * S / n) : (Lmax > 0.0 ? kCellTarget * Lmax / n : 1.0);
-  if (!(h > 0.0) || !isfinite(h)) h = Lmax > 0.0 && isfinite(Lmax) ? Lmax : 1.0;
+  double h = grid_cell_edge(L, n_faces, kCellTarget);
   for (int l = 0; l < kLevels; ++l) {
     if (l == kLevels - 1) h = fmax(h, 2.0 * Lmax + 1.0);   // one cell
     H->level[l].h = h;
@@ -300,34 +255,6 @@ __global__ __launch_bounds__(256) void k_msdf_cells(Ws W, int g) {
       }
 }
 
-// exclusive scan of count[0 .. n_bins) -> start (bnv_common.hpp's uint32 block scan + decoupled look-back)
-__global__ __launch_bounds__(kScanThreads) void k_msdf_scan(const uint32_t* __restrict__ count, int64_t n_bins,
-                                                            uint32_t* __restrict__ start, uint64_t* __restrict__ state,
-                                                            uint32_t epoch) {
-  __shared__ uint32_t wave_tot[kScanThreads / 64];
-  __shared__ uint32_t s_excl;
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  uint32_t v[kScanItems], s = 0;
-#pragma unroll
-  for (int e = 0; e < kScanItems; ++e) {
-    v[e] = base + e < n_bins ? count[base + e] : 0u;
-    s += v[e];
-  }
-  uint32_t total;
-  uint32_t run = block_exclusive_scan<kScanThreads>(s, wave_tot, &total);
-  if (threadIdx.x < 64) {
-    const uint32_t excl = lookback_exclusive(state, (int)blockIdx.x, total, epoch);
-    if (threadIdx.x == 0) s_excl = excl;
-  }
-  __syncthreads();
-  run += s_excl;
-#pragma unroll
-  for (int e = 0; e < kScanItems; ++e) {
-    if (base + e < n_bins) start[base + e] = run;
-    run += v[e];
-  }
-}
-
 // =====================================================================================================================
 // Query
 // =====================================================================================================================
@@ -403,38 +330,14 @@ __device__ __forceinline__ void tri_test(const float q[3], const float4 A, const
   }
 }
 
-// Can the search stop after ring r of grid g (cell edge hh)?  A point of a triangle lies in a cell the triangle is
-// listed in.  If that cell was visited, the triangle was tested as a whole; otherwise the point lies beyond one face
-// of the box of visited cells on some axis and inside the bounding box on the others (eval.hip: nn_can_stop).  Stop
-// when that lower bound on the distance exceeds the best fp32 distance by the relative and the absolute slack (the
-// fp32 closest point carries a few ulp of the largest coordinate), or when the ring covers the grid.
+// Can the search stop after ring r of grid g (cell edge hh)?  When the ring covers the grid, or when the lower bound on
+// the distance to every triangle not yet tested (cell_grid.hpp: grid_ring_bound; a point of a triangle lies in a cell
+// the triangle is listed in) exceeds the best fp32 distance by the relative and the absolute slack (the fp32 closest
+// point carries a few ulp of the largest coordinate).
 __device__ __forceinline__ bool can_stop(const Header& H, int g, double hh, const int c[3], int r, const double q[3],
                                          float best_d2) {
-  double gd2[3], base = 0.0;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const double gap = fmax(fmax(H.fmin[d] - q[d], q[d] - H.fmax[d]), 0.0);
-    gd2[d] = gap * gap;
-    base += gd2[d];
-  }
-  double lb = INFINITY;
-  bool open = false;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const int dim = H.dims[g][d];
-    const double slack = 1e-12 * (fabs(q[d]) + fabs(H.lo[d]) + (double)dim * hh) + 1e-9 * hh;
-    if (c[d] - r > 0) {
-      open = true;
-      const double f = fmax(q[d] - (H.lo[d] + (double)(c[d] - r) * hh) - slack, 0.0);
-      lb = fmin(lb, f * f + (base - gd2[d]));
-    }
-    if (c[d] + r < dim - 1) {
-      open = true;
-      const double f = fmax((H.lo[d] + (double)(c[d] + r + 1) * hh) - q[d] - slack, 0.0);
-      lb = fmin(lb, f * f + (base - gd2[d]));
-    }
-  }
-  if (!open) return true;
+  double lb;
+  if (!grid_ring_bound(H.lo, H.fmin, H.fmax, H.dims[g], hh, c, r, q, lb)) return true;
   const double bd = sqrt((double)best_d2) * (1.0 + kStopSlack) + H.eps_abs;
   return lb > bd * bd;
 }
@@ -447,37 +350,17 @@ __device__ __forceinline__ bool rings(const Header& H, const Ws& W, int g, const
   const int c[3] = {cell_axis(qf[0], H.lo[0], H.inv_h, H.dims[0][0]) >> sh,
                     cell_axis(qf[1], H.lo[1], H.inv_h, H.dims[0][1]) >> sh,
                     cell_axis(qf[2], H.lo[2], H.inv_h, H.dims[0][2]) >> sh};
-  const int D0 = H.dims[g][0], D1 = H.dims[g][1], D2 = H.dims[g][2];
-  const uint32_t* __restrict__ start = W.start[g];
+  const int dims[3] = {H.dims[g][0], H.dims[g][1], H.dims[g][2]};
   const uint32_t* __restrict__ ids = W.ids[g];
   const float4* __restrict__ tri = W.tri;
   for (int r = 0; r <= rmax; ++r) {
-    const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, D0 - 1);
-    const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, D1 - 1);
-    const int zl = c[2] - r, zh = c[2] + r;
-    for (int x = x0; x <= x1; ++x)
-      for (int y = y0; y <= y1; ++y) {
-        const bool shell = x == c[0] - r || x == c[0] + r || y == c[1] - r || y == c[1] + r;
-        // the ring's cells of this (x, y) column: a contiguous z-run on the shell, else its two ends
-        for (int part = 0; part < (shell ? 1 : 2); ++part) {
-          int za, zb;
-          if (shell) {
-            za = max(zl, 0);
-            zb = min(zh, D2 - 1);
-          } else {
-            za = zb = part == 0 ? zl : zh;
-            if (za < 0 || za >= D2) continue;
-          }
-          if (za > zb) continue;
-          const int64_t col = ((int64_t)x * D1 + y) * D2;
-          const uint32_t e = start[col + zb + 1];
-          for (uint32_t k = start[col + za]; k < e; ++k) {
-            const uint32_t f = ids[k];
-            tri_test(qf, tri[(int64_t)f * 3], tri[(int64_t)f * 3 + 1], tri[(int64_t)f * 3 + 2], (int32_t)f, best);
-            ++tests;
-          }
-        }
+    grid_ring(c, r, dims, W.start[g], [&](uint32_t k0, uint32_t k1) {
+      for (uint32_t k = k0; k < k1; ++k) {
+        const uint32_t f = ids[k];
+        tri_test(qf, tri[(int64_t)f * 3], tri[(int64_t)f * 3 + 1], tri[(int64_t)f * 3 + 2], (int32_t)f, best);
+        ++tests;
       }
+    });
     if (can_stop(H, g, hh, c, r, q, best.d2)) return true;
   }
   return false;
@@ -596,8 +479,6 @@ int bnv_mesh_sdf_build(const float* vertices, int64_t n_vertices, const int32_t*
   msdf_layout(n_vertices, n_faces, (char*)workspace, &W);
   const int64_t n_bins = W.cellcap + 2;
   // everything the build accumulates into starts from a known state on every call
-  BNV_HIP_CHECK(hipMemsetAsync(W.H, 0, sizeof(Header), s));
-  BNV_HIP_CHECK(hipMemsetAsync(W.H, 0xff, 3 * sizeof(uint32_t), s));   // bmin (first member) = the largest key
   BNV_HIP_CHECK(hipMemsetAsync(W.vacc, 0, (size_t)n_vertices * 24, s));
   BNV_HIP_CHECK(hipMemsetAsync(W.vflag, 0, (size_t)n_vertices * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(W.ekey, 0xff, (size_t)W.ecap * 8, s));
@@ -606,10 +487,8 @@ int bnv_mesh_sdf_build(const float* vertices, int64_t n_vertices, const int32_t*
   BNV_HIP_CHECK(hipMemsetAsync(W.count[0], 0, (size_t)n_bins * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(W.count[1], 0, (size_t)n_bins * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(W.scan_state, 0, (size_t)W.tiles * 2 * 8, s));
-  const unsigned bbox_blocks = (unsigned)std::min<int64_t>((n_vertices + 255) / 256, 2048);
   const dim3 face_blocks((unsigned)((n_faces + 255) / 256));
-  hipLaunchKernelGGL(k_msdf_bbox, dim3(bbox_blocks), dim3(256), 0, s, vertices, n_vertices, W.H);
-  BNV_LAUNCH_CHECK();
+  if (const int e = grid_bbox(vertices, n_vertices, W.H, sizeof(Header), s)) return e;   // clears the header
   hipLaunchKernelGGL(k_msdf_levels, dim3(1), dim3(64), 0, s, W.H, n_vertices, n_faces, need);
   BNV_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_msdf_faces, face_blocks, dim3(256), 0, s, vertices, n_vertices, faces, n_faces, W);
@@ -621,7 +500,7 @@ int bnv_mesh_sdf_build(const float* vertices, int64_t n_vertices, const int32_t*
   for (int g = 0; g < 2; ++g) {
     hipLaunchKernelGGL(k_msdf_cells<false>, face_blocks, dim3(256), 0, s, W, g);
     BNV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_msdf_scan, dim3((unsigned)W.tiles), dim3(kScanThreads), 0, s, W.count[g], n_bins, W.start[g],
+    hipLaunchKernelGGL(k_grid_scan, dim3((unsigned)W.tiles), dim3(kScanThreads), 0, s, W.count[g], n_bins, W.start[g],
                        W.scan_state + g * W.tiles, next_epoch());
     BNV_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_msdf_cells<true>, face_blocks, dim3(256), 0, s, W, g);

@@ -1,10 +1,12 @@
 // The mesh index csrc/meshsdf.hip builds and both it and csrc/meshray.hip read: the header word layout, the carving of
-// the caller's workspace (msdf_layout) and the helpers that decide which cell a coordinate falls into.  One definition,
-// so the builder and every reader agree on it.
+// the caller's workspace (msdf_layout).  One definition, so the builder and every reader agree on it; which cell a
+// coordinate falls into is csrc/cell_grid.hpp's rule.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "cell_grid.hpp"
 
 namespace bnv {
 namespace {
@@ -20,7 +22,6 @@ constexpr double kStopSlack = 1e-5;       // relative slack of the stop test on 
 constexpr double kNormalScale = 1099511627776.0;   // 2^40: fixed point of the pseudonormal sums
 constexpr unsigned long long kNoEdge = ~0ull;
 constexpr uint32_t kMagic = 0x4653444du;
-constexpr int kScanThreads = 256, kScanItems = 4, kScanTile = kScanThreads * kScanItems;
 constexpr int64_t kMaxFaces = 1 << 27, kMaxVertices = INT32_MAX;
 
 struct Level {
@@ -44,6 +45,7 @@ struct Header {
   double h, inv_h;                     // the fine grid's
   double eps_abs;                      // absolute slack of the stop test: 8 ulp of the largest coordinate
 };
+static_assert(offsetof(Header, bmin) == 0 && offsetof(Header, bmax) == 12, "grid_bbox writes the first six words");
 static_assert(offsetof(Header, tests) == 24, "tools/mesh_sdf_bench.py reads the counter at byte 24");
 
 struct Ws {
@@ -75,7 +77,7 @@ __host__ __device__ inline size_t msdf_layout(int64_t nv, int64_t nf, char* base
                             (size_t)tiles * 2 * 8};
   for (int k = 0; k < 14; ++k) {
     o[k] = off;
-    off += (bytes[k] + 255) / 256 * 256;
+    off += align256(bytes[k]);
   }
   if (w) {
     w->H = (Header*)(base + o[0]);
@@ -98,21 +100,6 @@ __host__ __device__ inline size_t msdf_layout(int64_t nv, int64_t nf, char* base
     w->tiles = tiles;
   }
   return off;
-}
-
-__device__ __forceinline__ uint32_t f2ord(float x) {   // order-preserving float -> uint32
-  const uint32_t b = __builtin_bit_cast(uint32_t, x);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t k) {
-  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-__device__ __forceinline__ int cell_axis(float x, double lo, double inv_h, int dim) {
-  double t = floor(((double)x - lo) * inv_h);
-  t = fmin(fmax(t, 0.0), (double)(dim - 1));
-  return (int)t;
 }
 
 }  // namespace

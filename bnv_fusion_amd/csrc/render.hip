@@ -143,7 +143,7 @@ static size_t render_ws_layout(int64_t n, int k, char* base, RenderWs* w) {
   const int64_t m = k + 1 > 6 ? k + 1 : 6;
   auto take = [&](size_t bytes) {
     char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
+    off += align256(bytes);
     return p;
   };
   RenderWs t;
