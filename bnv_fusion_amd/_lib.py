@@ -35,6 +35,7 @@ SYMBOLS = [
     "bnv_tsdf_mesh_workspace_bytes", "bnv_tsdf_mesh_count", "bnv_tsdf_mesh_emit",
     "bnv_render_workspace_bytes", "bnv_render_depth", "bnv_tsdf_render_depth",
     "bnv_mesh_post_workspace_bytes", "bnv_mesh_post_process",
+    "bnv_mesh_components_workspace_bytes", "bnv_mesh_components", "bnv_mesh_filter_components",
     "bnv_depth_to_points_gated", "bnv_depth_to_points_padded_gated", "bnv_encode_begin_depth_gated",
     "bnv_frame_begin_depth_gated",
     "bnv_train_param_floats", "bnv_train_running_floats", "bnv_train_workspace_bytes", "bnv_train_step",
@@ -293,6 +294,9 @@ def load():
                                             C.c_float, vp, vp, vp]),
         "bnv_mesh_post_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
         "bnv_mesh_post_process": (C.c_int, [vp, i64, vp, i64, C.c_double, vp, i64, vp, vp, vp, vp]),
+        "bnv_mesh_components_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+        "bnv_mesh_components": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+        "bnv_mesh_filter_components": (C.c_int, [vp, i64, vp, i64, C.c_double, i64, i64, vp, i64, vp, vp, vp, vp]),
         "bnv_train_param_floats": (i64, []),
         "bnv_train_running_floats": (i64, []),
         "bnv_train_workspace_bytes": (sz, [i64, i32, i64]),

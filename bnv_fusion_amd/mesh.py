@@ -138,7 +138,7 @@ def marching_cubes_lattice_indexed(sdf, origins, voxel_size, min_coords, level=0
     return verts, faces, nv, nt
 
 
-def post_process_mesh(mesh, vertex_threshold=0.005):
+def post_process_mesh(mesh, vertex_threshold=0.005, surface_threshold=None):
     """``o3d_helper.post_process_mesh`` (src/utils/o3d_helper.py:220-241; called at run_e2e.py:278, 293 with
     ``vertex_threshold = voxel_size / 4``): merge close vertices, drop degenerate and duplicated triangles and
     unreferenced / duplicated vertices, one pass of simple Laplacian smoothing.  A one-off at the end of a run, on the
@@ -152,7 +152,17 @@ def post_process_mesh(mesh, vertex_threshold=0.005):
     ``remove_unreferenced_vertices`` call is commented out, o3d_helper.py:230) but hands the result to
     ``trimesh.Trimesh(vertices, faces)`` with the default ``process=True``, whose vertex merge keeps referenced vertices
     only [from memory of trimesh 3.x] -- so they are dropped here; against Open3D's intermediate mesh the vertex count and
-    the face indices can therefore differ (same surface).  -> a new TriMesh."""
+    the face indices can therefore differ (same surface).
+
+    ``surface_threshold``: None, or an area -- connected components whose surface is below it are then removed after
+    the smoothing pass, and the vertices only they reference go with them (the reference's commented block,
+    o3d_helper.py:232-236).  Areas are taken on this function's own float32 output: the call equals
+    ``remove_small_components(post_process_mesh(mesh, eps), min_area=surface_threshold)`` bit for bit.  The default is
+    None because the reference's live code does not filter, and its 0.1 m^2 was never validated by anyone.
+    -> a new TriMesh."""
+    if surface_threshold is not None:
+        _check_filter_args("post_process_mesh", surface_threshold, 0, None)
+        return remove_small_components(post_process_mesh(mesh, vertex_threshold), min_area=surface_threshold)
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components
     from scipy.spatial import cKDTree
@@ -193,28 +203,26 @@ def post_process_mesh(mesh, vertex_threshold=0.005):
 _POST_EXTENT_LIMIT = 2.0 ** 29   # |x| / eps below it: the device neighbour grid is exact (bnv_fusion.h: 2^30 on u)
 
 
-def post_process_mesh_tensors(vertices, faces, vertex_threshold=0.005):
+def post_process_mesh_tensors(vertices, faces, vertex_threshold=0.005, surface_threshold=None):
     """``post_process_mesh`` on the device (csrc/meshpost.hip; include/bnv_fusion.h, "Mesh post-processing"):
     vertices [V, 3] float32 and faces [T, 3] int64 on the GPU -> (vertices [V', 3] float32, faces [T', 3] int64) on the
     same device, bit for bit what the host function returns.  The only host reads: one for the input checks, one for
-    the two output counts.  Raises ValueError on CPU tensors, wrong shapes or dtypes, face indices outside [0, V),
-    non-finite vertices, a negative or non-finite threshold, or coordinates beyond 2^29 thresholds."""
-    for name, t, dt in (("vertices", vertices, torch.float32), ("faces", faces, torch.int64)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"post_process_mesh_tensors: {name} must be a GPU tensor (there is no CPU path; the host "
-                             "function is mesh.post_process_mesh)")
-        if t.dim() != 2 or t.shape[1] != 3 or t.dtype != dt:
-            raise ValueError(f"post_process_mesh_tensors: {name} must be [N, 3] {dt} (got {list(t.shape)} {t.dtype})")
-    if vertices.device != faces.device:
-        raise ValueError("post_process_mesh_tensors: vertices and faces are on different devices")
+    the two output counts (with ``surface_threshold`` a third: the filter's two counts; its input is this function's
+    own output, whose size the kernels need on the host).  Raises ValueError on CPU tensors, wrong shapes or dtypes, face indices outside [0, V),
+    non-finite vertices, a negative or non-finite threshold, or coordinates beyond 2^29 thresholds.
+    ``surface_threshold``: None (the default: the reference's live code does not filter, and its 0.1 m^2 was never
+    validated by anyone), or the area below which connected components of the result are removed
+    (the device filter of remove_small_components_tensors on this function's own output)."""
+    who = "post_process_mesh_tensors"
+    if surface_threshold is not None:
+        min_area, _, _ = _check_filter_args(who, surface_threshold, 0, None)
+        v_out, f_out = post_process_mesh_tensors(vertices, faces, vertex_threshold)
+        return _filter_components(who, v_out, f_out, min_area, 0, 0)
+    vertices, faces, V, T = _check_mesh_tensors(who, vertices, faces, "post_process_mesh")
     eps = float(vertex_threshold)
     if not (np.isfinite(eps) and eps >= 0.0):
         raise ValueError(f"post_process_mesh_tensors: vertex_threshold must be finite and >= 0 (got {eps})")
-    V, T = int(vertices.shape[0]), int(faces.shape[0])
-    if V >= 2 ** 31 - 1 or T >= 2 ** 31 - 1:
-        raise ValueError(f"post_process_mesh_tensors: {V} vertices / {T} faces: indices are int32 on the device")
     dev = vertices.device
-    vertices, faces = vertices.detach().contiguous(), faces.detach().contiguous()
     if V == 0 and T == 0:
         return vertices.clone(), faces.clone()
     # one host read for every check: finite, face index range, extent against the neighbour grid
@@ -248,12 +256,215 @@ def post_process_mesh_tensors(vertices, faces, vertex_threshold=0.005):
     return v_out[:nv], f_out[:nf]
 
 
-def post_process_mesh_gpu(mesh, vertex_threshold=0.005, device="cuda:0"):
+def post_process_mesh_gpu(mesh, vertex_threshold=0.005, device="cuda:0", surface_threshold=None):
     """``post_process_mesh`` of a TriMesh on the GPU: the same TriMesh, bit for bit, through one upload and
     ``to_host``.  Same errors as post_process_mesh_tensors."""
     v = torch.from_numpy(np.ascontiguousarray(mesh.vertices, dtype=np.float32)).to(device)
     f = torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int64)).to(device)
-    vs, fs = post_process_mesh_tensors(v, f, vertex_threshold)
+    vs, fs = post_process_mesh_tensors(v, f, vertex_threshold, surface_threshold=surface_threshold)
+    return TriMesh(*to_host(vs, fs))
+
+
+# ---- connected components (include/bnv_fusion.h, "Mesh components") -------------------------------------------------
+_AREA_SCALE = 2.0 ** 50          # areas are summed as integers in units of 2^-50
+_AREA_LIMIT = 2.0 ** 12          # total area below it: the integer sums stay below 2^62
+
+
+def _check_filter_args(who, min_area, min_faces, keep_largest):
+    a = float(min_area)
+    if not (np.isfinite(a) and a >= 0.0):
+        raise ValueError(f"{who}: the area threshold must be finite and >= 0 (got {a})")
+    if int(min_faces) != min_faces or int(min_faces) < 0:
+        raise ValueError(f"{who}: min_faces must be an integer >= 0 (got {min_faces})")
+    if keep_largest is not None and (int(keep_largest) != keep_largest or int(keep_largest) < 1):
+        raise ValueError(f"{who}: keep_largest must be None or an integer >= 1 (got {keep_largest})")
+    return a, int(min_faces), 0 if keep_largest is None else int(keep_largest)
+
+
+def _face_area_units(v, f):
+    """q [T] int64 = rint(area * 2^50) per face, in float64 from the float32 coordinates, one rounding per operation."""
+    p = v.astype(np.float64)
+    a, b, c = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
+    e1, e2 = b - a, c - a
+    cx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    cy = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    cz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    area = 0.5 * np.sqrt((cx * cx + cy * cy) + cz * cz)
+    if (area >= _AREA_LIMIT).any():
+        raise ValueError("connected_components: the mesh's total area reaches 2^12 square units")
+    q = np.rint(area * _AREA_SCALE).astype(np.int64)
+    if int((q >> 31).sum()) * 2 ** 31 + int((q & (2 ** 31 - 1)).sum()) >= 2 ** 62:
+        raise ValueError("connected_components: the mesh's total area reaches 2^12 square units")
+    return q
+
+
+def connected_components(mesh):
+    """Connected components of a mesh's faces over shared edges (two faces are adjacent when they have an edge with the
+    same two vertex indices), the block the reference keeps commented out in o3d_helper.post_process_mesh
+    (src/utils/o3d_helper.py:232-236, ``cluster_connected_triangles``).  -> (labels [T] int32, numbered in ascending
+    order of every component's smallest face; n_faces [C] int64; areas [C] float64: per-face areas in units of 2^-50
+    summed as integers, so any order gives the same bits).  On the host, with numpy + scipy.
+
+    PARITY UNPINNED: Open3D is not in the image; its clustering rule is restated from memory [Open3D 0.14].  Raises
+    ValueError on a non-finite vertex, a face index outside [0, V), or a total area of 2^12 square units or more."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components as cc
+    v = np.asarray(mesh.vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
+    V, T = len(v), len(f)
+    if not np.isfinite(v).all():
+        raise ValueError("connected_components: vertices must be finite")
+    if T and (V == 0 or f.min() < 0 or f.max() >= V):
+        raise ValueError(f"connected_components: a face indexes a vertex outside [0, {V})")
+    if T == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0, np.float64)
+    q = _face_area_units(v, f)
+    ends = np.stack([f, np.roll(f, -1, axis=1)], -1).reshape(-1, 2)                  # [3T, 2]: (f0,f1), (f1,f2), (f2,f0)
+    face = np.repeat(np.arange(T), 3)
+    real = ends[:, 0] != ends[:, 1]
+    key = (ends.min(1) << 32 | ends.max(1))[real]
+    face = face[real]
+    order = np.argsort(key, kind="stable")
+    key, face = key[order], face[order]
+    same = key[1:] == key[:-1]
+    i, j = face[:-1][same], face[1:][same]
+    g = coo_matrix((np.ones(len(i), dtype=np.int8), (i, j)), shape=(T, T))
+    n_c, lab = cc(g, directed=False)
+    first = np.full(n_c, T, dtype=np.int64)                                          # scipy numbers components in order
+    np.minimum.at(first, lab, np.arange(T))                                          # of their smallest member already;
+    lab = np.argsort(np.argsort(first, kind="stable"), kind="stable")[lab]           # make it hold whatever it does
+    by = np.argsort(lab, kind="stable")
+    starts = np.searchsorted(lab[by], np.arange(n_c))
+    sums = np.add.reduceat(q[by], starts)
+    return lab.astype(np.int32), np.bincount(lab, minlength=n_c).astype(np.int64), sums.astype(np.float64) / _AREA_SCALE
+
+
+def _kept_components(n_faces, areas, min_area, min_faces, keep_largest):
+    keep = (areas >= min_area) & (n_faces >= min_faces)
+    if keep_largest:
+        order = np.lexsort((np.arange(len(areas)), -areas))                          # area descending, label ascending
+        top = np.zeros(len(areas), dtype=bool)
+        top[order[:keep_largest]] = True
+        keep &= top
+    return keep
+
+
+def remove_small_components(mesh, min_area=0.0, min_faces=0, keep_largest=None):
+    """Drops the connected components (``connected_components``) that fail any of: area >= ``min_area`` (equality
+    keeps; the reference's block removes ``component_surfaces < surface_threshold``), face count >= ``min_faces``,
+    among the ``keep_largest`` largest by area over all components (None: no such test; ties go to the smaller label).
+    Kept faces and the vertices they reference keep their order and their bits; every other vertex is dropped and the
+    faces are renumbered.  Nothing kept, or no faces, gives an empty mesh.  -> a new TriMesh.  Host function; the device
+    versions are remove_small_components_tensors / remove_small_components_gpu."""
+    min_area, min_faces, k = _check_filter_args("remove_small_components", min_area, min_faces, keep_largest)
+    labels, n_faces, areas = connected_components(mesh)
+    v = np.asarray(mesh.vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
+    if len(f) == 0:
+        return TriMesh(v[:0], f)
+    f = f[_kept_components(n_faces, areas, min_area, min_faces, k)[labels]]
+    used = np.unique(f)
+    remap = np.full(len(v), -1, dtype=np.int64)
+    remap[used] = np.arange(len(used))
+    return TriMesh(v[used], remap[f])
+
+
+def _check_mesh_tensors(who, vertices, faces, host_name):
+    """The checks the device mesh functions share -> (vertices, faces, V, T) contiguous and detached."""
+    for name, t, dt in (("vertices", vertices, torch.float32), ("faces", faces, torch.int64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{who}: {name} must be a GPU tensor (there is no CPU path; the host function is "
+                             f"mesh.{host_name})")
+        if t.dim() != 2 or t.shape[1] != 3 or t.dtype != dt:
+            raise ValueError(f"{who}: {name} must be [N, 3] {dt} (got {list(t.shape)} {t.dtype})")
+    if vertices.device != faces.device:
+        raise ValueError(f"{who}: vertices and faces are on different devices")
+    V, T = int(vertices.shape[0]), int(faces.shape[0])
+    if V >= 2 ** 31 - 1 or T >= 2 ** 31 - 1:
+        raise ValueError(f"{who}: {V} vertices / {T} faces: indices are int32 on the device")
+    return vertices.detach().contiguous(), faces.detach().contiguous(), V, T
+
+
+def _refused_component_input(who, vertices, faces, V, T):
+    """The device refused the input (a count of -1): the ValueError that names why.  The kernels check finite vertices,
+    the face index range and the total area themselves and report one word, so valid input pays for no check here."""
+    got = [torch.isfinite(vertices).all()] + ([faces.min() < 0, faces.max() >= V] if T else [])
+    got = torch.stack(got).tolist()
+    if not got[0]:
+        return ValueError(f"{who}: vertices must be finite")
+    if T and (V == 0 or got[1] or got[2]):
+        return ValueError(f"{who}: a face indexes a vertex outside [0, {V})")
+    return ValueError(f"{who}: the mesh's total area reaches 2^12 square units")      # the one check left
+
+
+def _components_workspace(lib, V, T, dev):
+    need = C.c_int64()
+    _lib.check(lib.bnv_mesh_components_workspace_bytes(V, T, C.byref(need)), "bnv_mesh_components_workspace_bytes")
+    return torch.empty(int(need.value), dtype=torch.uint8, device=dev), int(need.value)
+
+
+def connected_components_tensors(vertices, faces):
+    """``connected_components`` on the device (csrc/meshpost.hip; include/bnv_fusion.h, "Mesh components"): vertices
+    [V, 3] float32 and faces [T, 3] int64 on the GPU -> (labels [T] int32, n_faces [C] int64, areas [C] float64) on the
+    same device, bit for bit what the host function returns.  One host read: C, which is -1 when the device's input
+    checks refuse the mesh (a second read then finds which check to name).  Raises ValueError on CPU tensors, wrong shapes or dtypes, non-finite vertices, face indices outside [0, V), or a
+    total area of 2^12 square units or more."""
+    who = "connected_components_tensors"
+    vertices, faces, V, T = _check_mesh_tensors(who, vertices, faces, "connected_components")
+    dev = vertices.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws, need = _components_workspace(lib, V, T, dev)
+        labels = torch.empty(T, dtype=torch.int32, device=dev)
+        n_faces = torch.empty(T, dtype=torch.int64, device=dev)
+        areas = torch.empty(T, dtype=torch.float64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(lib.bnv_mesh_components(_lib.ptr(vertices), V, _lib.ptr(faces), T, _lib.ptr(ws), need,
+                                           _lib.ptr(labels), _lib.ptr(n_faces), _lib.ptr(areas), _lib.ptr(count),
+                                           _lib.stream_ptr()), "bnv_mesh_components")
+        n_c = int(count.item())                    # the one host read of the result: the number of components
+    if n_c < 0:
+        raise _refused_component_input(who, vertices, faces, V, T)
+    return labels, n_faces[:n_c], areas[:n_c]
+
+
+def _filter_components(who, vertices, faces, min_area, min_faces, k):
+    """bnv_mesh_filter_components on checked tensors (_check_mesh_tensors) and arguments (_check_filter_args)."""
+    V, T = int(vertices.shape[0]), int(faces.shape[0])
+    dev = vertices.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws, need = _components_workspace(lib, V, T, dev)
+        v_out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        f_out = torch.empty((T, 3), dtype=torch.int64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(lib.bnv_mesh_filter_components(_lib.ptr(vertices), V, _lib.ptr(faces), T, C.c_double(min_area),
+                                                  min_faces, k, _lib.ptr(ws), need, _lib.ptr(v_out), _lib.ptr(f_out),
+                                                  _lib.ptr(counts), _lib.stream_ptr()), "bnv_mesh_filter_components")
+        nv, nf = counts.tolist()                   # the one host read of the result: the mesh's size
+    if nv < 0:
+        raise _refused_component_input(who, vertices, faces, V, T)
+    return v_out[:nv], f_out[:nf]
+
+
+def remove_small_components_tensors(vertices, faces, min_area=0.0, min_faces=0, keep_largest=None):
+    """``remove_small_components`` on the device: vertices [V, 3] float32 and faces [T, 3] int64 on the GPU ->
+    (vertices [V', 3] float32, faces [T', 3] int64) on the same device, bit for bit what the host function returns.
+    One host read: the two output counts, which are -1 when the device's input checks refuse the mesh (a second read
+    then finds which check to name).  Raises ValueError like connected_components_tensors, and on a negative or
+    non-finite ``min_area``, a negative ``min_faces`` or a ``keep_largest`` below 1."""
+    who = "remove_small_components_tensors"
+    min_area, min_faces, k = _check_filter_args(who, min_area, min_faces, keep_largest)
+    vertices, faces, _, _ = _check_mesh_tensors(who, vertices, faces, "remove_small_components")
+    return _filter_components(who, vertices, faces, min_area, min_faces, k)
+
+
+def remove_small_components_gpu(mesh, min_area=0.0, min_faces=0, keep_largest=None, device="cuda:0"):
+    """``remove_small_components`` of a TriMesh on the GPU: the same TriMesh, bit for bit, through one upload and
+    ``to_host``.  Same errors as remove_small_components_tensors."""
+    v = torch.from_numpy(np.ascontiguousarray(mesh.vertices, dtype=np.float32)).to(device)
+    f = torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int64)).to(device)
+    vs, fs = remove_small_components_tensors(v, f, min_area, min_faces, keep_largest)
     return TriMesh(*to_host(vs, fs))
 
 

@@ -348,14 +348,20 @@ class NeuralMap:
         delta = self.prepare_tsdf_volume() if self.tsdf_vol is not None else self.sdf_delta
         return self.volume.meshlize_sdf(self.pointnet.nerf, delta)
 
-    def extract_mesh(self, path=None, post_process=None):
+    def extract_mesh(self, path=None, post_process=None, min_component_area=None):
         """run_e2e.py:164-167: mesh of the whole volume (TSDF prior included when enabled) -> TriMesh or None.
         ``post_process``: None, or a vertex threshold (run_e2e.py:293 uses voxel_size / 4) -- the mesh is then
-        post-processed on the device, the same as mesh.post_process_mesh(extract_mesh(), post_process)."""
+        post-processed on the device, the same as mesh.post_process_mesh(extract_mesh(), post_process).
+        ``min_component_area``: None, or an area -- connected components of the post-processed mesh below it are
+        removed on the device (mesh.remove_small_components); ValueError without ``post_process``."""
+        if min_component_area is not None and post_process is None:
+            raise ValueError("extract_mesh: min_component_area needs post_process (a vertex threshold): the unwelded "
+                             "per-voxel mesh has one component per voxel patch")
         self._drain_pipe()
         delta = self.prepare_tsdf_volume() if self.tsdf_vol is not None else self.sdf_delta
         self.volume.to_tensor()
-        out = self.volume.meshlize(self.pointnet.nerf, delta, path, post_process=post_process)
+        out = self.volume.meshlize(self.pointnet.nerf, delta, path, post_process=post_process,
+                                   min_component_area=min_component_area)
         return None if out is None else out[1]
 
     def render(self, T_wc, intr_mat, H, W, normals=True):

@@ -631,14 +631,19 @@ class SparseVolume:
         off = int(self._lib.bnv_decode_lattice_count_offset(self._row_capacity))
         return self._lattice_last[off + 4: off + 8].view(torch.int32)
 
-    def meshlize(self, nerf, sdf_delta=None, path=None, post_process=None):
+    def meshlize(self, nerf, sdf_delta=None, path=None, post_process=None, min_component_area=None):
         """sparse_volume.py:697-766: decode the 3x3x3 lattice of every active voxel and run per-voxel
         marching cubes -- both on the GPU.  Returns (active_pts, mesh) like the reference (None when no
         voxel straddles the surface); ``mesh`` is a bnv_fusion_amd.mesh.TriMesh (vertices / faces /
         export), standing in for trimesh.Trimesh(process=False).  ``post_process``: None, or a vertex threshold --
         the mesh is then mesh.post_process_mesh'ed on the device (post_process_mesh_tensors, bit for bit the host
-        result) before it leaves it."""
+        result) before it leaves it.  ``min_component_area``: None, or an area -- connected components of the
+        post-processed mesh below it are removed on the device too (mesh.remove_small_components); it needs
+        ``post_process``, because in the unwelded per-voxel concatenation every voxel's patch is its own component."""
         from .mesh import TriMesh, marching_cubes_lattice_indexed, post_process_mesh_tensors, to_host
+        if min_component_area is not None and post_process is None:
+            raise ValueError("meshlize: min_component_area needs post_process (a vertex threshold): the unwelded "
+                             "per-voxel mesh has one component per voxel patch")
         assert self.active_coordinates is not None, "call self.to_tensor() first."
         active_pts = self.active_coordinates * self.voxel_size + self.min_coords
         sdf = self.decode_lattice(self.active_coordinates, nerf, sdf_delta, query_tensor=True)
@@ -648,7 +653,8 @@ class SparseVolume:
         if faces.shape[0] == 0:
             return None
         if post_process is not None:
-            verts, faces = post_process_mesh_tensors(verts, faces, float(post_process))
+            verts, faces = post_process_mesh_tensors(verts, faces, float(post_process),
+                                                     surface_threshold=min_component_area)
         v_host, f_host, pts_host = to_host(verts, faces, active_pts)
         mesh = TriMesh(v_host, f_host)
         if path is not None:

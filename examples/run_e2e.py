@@ -31,7 +31,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import bnv_fusion_amd as bnv                                   # noqa: E402
 bnv.configure_runtime()                                       # optional: the package's hardware queue count
 from bnv_fusion_amd import datasets, synthetic                # noqa: E402
-from bnv_fusion_amd.mesh import post_process_mesh, to_host    # noqa: E402
+from bnv_fusion_amd.mesh import (TriMesh, connected_components, connected_components_tensors,          # noqa: E402
+                                 post_process_mesh, remove_small_components, remove_small_components_tensors, to_host)
 
 
 def main():
@@ -66,6 +67,10 @@ def main():
     ap.add_argument("--post-process", default="host", choices=["host", "gpu"],
                     help="where the written meshes are post-processed (merge close vertices, clean, smooth): the host "
                          "function or its device version (same output bit for bit)")
+    ap.add_argument("--min-component-area", type=float, metavar="A",
+                    help="remove connected components of the post-processed meshes whose surface is below A square "
+                         "metres (the block the reference keeps commented out in o3d_helper.post_process_mesh, there "
+                         "with 0.1), on either --post-process route; prints what the final mesh lost")
     ap.add_argument("--arkit", action="store_true",
                     help="read --data-dir/--scan-id as an iPhone / iPad LiDAR capture (3D Scanner app, 'All Data')")
     ap.add_argument("--confidence-level", type=int, default=2,
@@ -164,10 +169,10 @@ def main():
             torch.cuda.synchronize()
             t_global += time.perf_counter() - t0
             if args.post_process == "gpu":
-                mesh = nm.extract_mesh(post_process=0.005)
+                mesh = nm.extract_mesh(post_process=0.005, min_component_area=args.min_component_area)
             else:
                 mesh = nm.extract_mesh()
-                mesh = None if mesh is None else post_process_mesh(mesh)
+                mesh = None if mesh is None else post_process_mesh(mesh, surface_threshold=args.min_component_area)
             if mesh is not None:                                             # :277-280
                 mesh.export(os.path.join(args.out, f"{idx}.ply"))
     mesh = nm.extract_mesh(os.path.join(args.out, "before_optim.ply"))   # :280-282
@@ -189,6 +194,22 @@ def main():
     else:
         mesh = nm.extract_mesh()
         mesh = None if mesh is None else post_process_mesh(mesh, vertex_threshold=nm.voxel_size / 4)
+    if mesh is not None and args.min_component_area is not None:
+        # the same as extract_mesh(post_process=..., min_component_area=A) / post_process_mesh(surface_threshold=A),
+        # in two steps: the figures below are about the components of the unfiltered mesh
+        n_before = len(mesh.faces)
+        if args.post_process == "gpu":                                   # one upload serves the statistics and the filter
+            gv, gf = torch.from_numpy(mesh.vertices).to(dev), torch.from_numpy(mesh.faces).to(dev)
+            areas = to_host(connected_components_tensors(gv, gf)[2])[0]
+            mesh = TriMesh(*to_host(*remove_small_components_tensors(gv, gf, min_area=args.min_component_area)))
+        else:
+            _, _, areas = connected_components(mesh)
+            mesh = remove_small_components(mesh, min_area=args.min_component_area)
+        gone = areas < args.min_component_area
+        share = f"{areas.max() / areas.sum():.4%}" if len(areas) and areas.sum() > 0 else "n/a"
+        print(f"components: {len(areas)}, the largest holds {share} of the area; below "
+              f"{args.min_component_area:g} m^2: {int(gone.sum())} components, {n_before - len(mesh.faces)} faces, "
+              f"{areas[gone].sum():.6f} m^2 removed")
     if mesh is not None:
         mesh.export(os.path.join(args.out, "final.ply"))
     nm.save(args.out, scan_id=args.scan_id.split("/")[-1])

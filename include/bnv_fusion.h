@@ -1040,6 +1040,48 @@ int bnv_mesh_post_process(const float* vertices, int64_t n_vertices, const int64
                           double vertex_threshold, void* workspace, int64_t ws_bytes, float* vertices_out,
                           int64_t* faces_out, int64_t* counts, bnv_stream_t stream);
 
+/* ---- Mesh components (bnv_fusion_amd/csrc/meshpost.hip): connected components of a mesh's faces, their face counts and
+ * areas, and the filter that removes the small ones -- mesh.connected_components / mesh.remove_small_components on the
+ * device with the same output bit for bit.  This is the block the reference's o3d_helper.post_process_mesh documents
+ * ("merge close vertices and remove small connected components") and keeps commented out (src/utils/o3d_helper.py:
+ * 232-236: cluster_connected_triangles, drop components below surface_threshold, remove unreferenced vertices).
+ * PARITY UNPINNED: Open3D's clustering rule is restated from memory.
+ *
+ * Input: vertices f32 [V, 3], faces i64 [T, 3], V, T < 2^31 - 1.
+ * 1. Adjacency.  Face t has the undirected edges {f0, f1}, {f1, f2}, {f2, f0}; an edge whose two ends are the same
+ *    index joins nothing.  Two faces are adjacent when they have an edge with the same two vertex INDICES (positions do
+ *    not count: an unwelded soup has T components).  Winding does not matter, three or more faces on one edge are all
+ *    adjacent, faces that share only a vertex are not.
+ * 2. Components: the connected components of that adjacency, numbered 0..C-1 in ascending order of their smallest face
+ *    index (scipy's labelling).  labels i32 [T].
+ * 3. Areas, order-free and exact.  Per face in float64 from the float32 coordinates, one rounding per operation in the
+ *    order written, no contraction: e1 = b - a, e2 = c - a; cx = e1y*e2z - e1z*e2y, cy = e1z*e2x - e1x*e2z,
+ *    cz = e1x*e2y - e1y*e2x; area = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz) with a correctly rounded sqrt;
+ *    q = rint(area * 2^50) as int64, ties to even.  A component's area is (sum of q) / 2^50 with the sum taken in
+ *    integers (any summation order gives the same bits) and converted to float64 once, to nearest even; its face count
+ *    comes with it.  The input is refused when a vertex is non-finite, a face index is outside [0, V), or the mesh's
+ *    total area reaches 2^12 square units (sum of q >= 2^62): the sums then cannot overflow.
+ * 4. Filter (min_area finite >= 0, min_faces >= 0, keep_largest >= 0).  A component is kept iff area >= min_area
+ *    (equality keeps; the reference removes component_surfaces < surface_threshold), n_faces >= min_faces, and
+ *    keep_largest == 0 or the component is among the keep_largest largest by area over ALL components, ties going to
+ *    the smaller label.  Kept faces keep their order; vertices referenced by a kept face keep their order and their
+ *    bits, all others are dropped; faces are renumbered.  Nothing kept, or T = 0, gives V' = T' = 0.
+ *
+ * Workspace: bnv_mesh_components_workspace_bytes (148 B per face + 8 B per vertex; one workspace serves both entries;
+ * V, T out of range: BNV_ERR_INVALID_ARGUMENT).  bnv_mesh_components writes labels i32 [T], n_faces_out i64 [T] and
+ * areas_out f64 [T] (capacities of T: C <= T; entries past C are unspecified) and the device int64 count = C, or -1 for
+ * input the device finds invalid.  bnv_mesh_filter_components writes vertices_out f32 [V, 3] and faces_out i64 [T, 3]
+ * (capacities of the input's size) and the device int64[2] counts = {V', T'}, {-1, -1} for invalid input; rows past
+ * the counts are unspecified.  No allocation, synchronisation or host read: the caller reads the counts. */
+int bnv_mesh_components_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t* bytes);
+int bnv_mesh_components(const float* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces,
+                        void* workspace, int64_t ws_bytes, int32_t* labels, int64_t* n_faces_out, double* areas_out,
+                        int64_t* count, bnv_stream_t stream);
+int bnv_mesh_filter_components(const float* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces,
+                               double min_area, int64_t min_faces, int64_t keep_largest, void* workspace,
+                               int64_t ws_bytes, float* vertices_out, int64_t* faces_out, int64_t* counts,
+                               bnv_stream_t stream);
+
 /* ---- Training of the local shape embedding (bnv_fusion_amd/csrc/train.hip): the reference's
  * LitFusionPointNet.training_step with training_global=False (local_point_fusion.py:381-460), in exact fp32.
  *
