@@ -105,6 +105,13 @@ struct ProfScope {
 
 #define BNV_LAUNCH_CHECK() BNV_HIP_CHECK(hipGetLastError())
 
+// passes a failed step's code on to the caller
+#define BNV_TRY(expr)              \
+  do {                             \
+    const int _rc = (expr);        \
+    if (_rc != BNV_OK) return _rc; \
+  } while (0)
+
 // size of a workspace piece: every piece starts on a 256-byte boundary
 __host__ __device__ inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
@@ -292,7 +299,7 @@ struct ShardRec {   // 48 bytes, 16-byte aligned: three dwordx4
 static_assert(sizeof(ShardRec) == BNV_SHARD_RECORD_BYTES, "record size");
 // header record of a block: x = number of records, y = sender rank, z = 1 if the block overflowed its capacity
 
-// workspace words of the lattice decode that kernels of other files touch (decode.hip: lattice_ws_layout)
+// workspace words of the lattice decode that kernels of other files touch (decode_host.hpp: lattice_ws_layout; lattice.hip)
 void lattice_ws_frame_words(void* ws, int64_t row_capacity, int32_t** origin_stamp, int32_t** ctl);
 
 // ---- packed volume keys -------------------------------------------------------------------

@@ -10,7 +10,7 @@
 //                   by distance (rank counting), world points; per sample the L1 target (signed distance to the nearest valid
 //                   neighbouring surface point, truncated) and its weight (valid x ray mask);
 //   k_count_optim_pts  weights[row] += 1 once per distinct corner row of the samples (count_optim, :602-622);
-//   (decode_pts forward: csrc/decode.hip)
+//   (decode_pts forward: csrc/decode_pts.hip)
 //   k_ray_loss      loss = sum w |pred - target| / n_valid and d loss / d pred;
 //   (decode_pts backward).
 // The uniforms of the stratified draws are an INPUT (the caller's generator), so the reference's random

@@ -4,8 +4,8 @@
 // kernel stores them.  Encoder 16 | 64 | 64 | 64 | 16 (NK0 = 1 input K-step), SDF decoder 32 | 64 | 64 | 64 | 16
 // (NK0 = 2); inputs are padded with 1.0 (the pad columns act as biases).
 //
-// This is the only place the tile is written.  Every kernel that runs these networks (decode.hip: sdf_mlp_tile_t,
-// k_decode_pts_bwd_t, k_lattice_table_t; encode.hip: k_pointnet_scatter_t, k_pointnet_scatter_tb; train_tcnn.hip:
+// This is the only place the tile is written.  Every kernel that runs these networks (sdf_mlp.hpp: sdf_mlp_tile_t;
+// decode_pts.hip: k_decode_pts_bwd_t; decode.hip: k_lattice_table_t; encode.hip: k_pointnet_scatter_t, k_pointnet_scatter_tb; train_tcnn.hip:
 // k_tcnn_tile) brings its own inputs and takes the outputs where it needs them; the operands and the MFMA order
 // per accumulator (mb outer, K-step inner, accumulate in place) are the ones below, so the kernels agree bit for bit.
 //

@@ -418,12 +418,6 @@ static int colsum(hipStream_t s, const float* X, const float* Y, int64_t R, int 
   return BNV_OK;
 }
 
-#define BNV_TRY(expr)             \
-  do {                            \
-    const int _rc = (expr);       \
-    if (_rc != BNV_OK) return _rc; \
-  } while (0)
-
 // forward through encoder and decoder; loss into loss_out; train: batch statistics (+ running update), dpred
 static int forward(hipStream_t s, const Layout& L, const float* params, float* running, const float* input_pts,
                    const float* training_pts, const float* gt, int64_t B, int n, int64_t M, int train, Ws& w,

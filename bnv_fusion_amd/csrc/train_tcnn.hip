@@ -7,7 +7,7 @@
 // [out, in] matrices in layer order:  encoder 16 | 64 | 64 | 64 | 16 (10,240 weights), decoder 32 | 64 | 64 | 64 | 16
 // (11,264).  The input is padded with 1.0 to 16 / 32 columns (the pad columns act as biases).
 //
-// Forward = the mode-2 arithmetic of the inference kernels (encode.hip k_pointnet_scatter_tb, decode.hip
+// Forward = the mode-2 arithmetic of the inference kernels (encode.hip k_pointnet_scatter_tb, sdf_mlp.hpp
 // sdf_mlp_tile_t), from the same code (tcnn_mlp.hpp): inputs and weights rounded to f16, every layer an f16 MFMA with
 // fp32 accumulation, ReLU after the hidden layers, every layer output rounded to f16.
 //
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void k_tcnn_tile(TileArgs a) {
 #pragma unroll
       for (int c = 0; c < 6; ++c) in[c] = src[c];
     } else {
-      // the encoding NeuralMap's mode-2 decode stages (decode.hip: stage_input_t)
+      // the encoding NeuralMap's mode-2 decode stages (sdf_mlp.hpp: stage_input_t)
       b = row / a.M;
       const float* p = a.xyz + row * 3;
       const float loc[3] = {p[0], p[1], p[2]};
@@ -594,12 +594,6 @@ static int encode(hipStream_t s, const float* params, const float* input_pts, in
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
-
-#define BNV_TRY(expr)              \
-  do {                             \
-    const int _rc = (expr);        \
-    if (_rc != BNV_OK) return _rc; \
-  } while (0)
 
 }  // namespace train_tcnn
 }  // namespace bnv

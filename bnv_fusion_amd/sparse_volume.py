@@ -1,7 +1,7 @@
 """SparseVolume -- drop-in for the reference class of the same name
 (src/models/sparse_volume.py:484-892), backed by the HIP hash volume (csrc/volume.hip) and the
-HIP decode kernels (csrc/decode.hip).  Same constructor, attributes and method names; tensors
-live on the GPU; torch only owns the memory.
+HIP decode kernels (csrc/decode.hip, csrc/decode_pts.hip, csrc/lattice.hip).  Same constructor, attributes and
+method names; tensors live on the GPU; torch only owns the memory.
 """
 import ctypes as C
 

@@ -1,5 +1,5 @@
 """Weights of the fp32 point encoder / SDF decoder: loading, BatchNorm folding and the
-pre-permuted MFMA operand layouts the kernels read (csrc/encode.hip, csrc/decode.hip).
+pre-permuted MFMA operand layouts the kernels read (csrc/encode.hip, csrc/sdf_mlp.hpp, csrc/decode.hip, csrc/decode_pts.hip).
 
 State-dict key names are the reference's, so either the converted
 ``weights/pointnet_fp32.npz`` or a ``torch.load(ckpt)['state_dict']`` can be passed in.
@@ -212,7 +212,7 @@ def _pack_split16(W, n_steps, first_layer=False):
 
 
 def pack_sdf_mlp_bwd(sd):
-    """Transposed layers for bnv_decode_pts_backward -> float32 [204800] (SB_* layout of csrc/decode.hip):
+    """Transposed layers for bnv_decode_pts_backward -> float32 [204800] (SB_* layout of csrc/decode_pts.hip):
     W3^T, W2^T, W1^T as 256x256 split packs, then W0^T (17 x 256, rows padded to 32)."""
     Ws = [_np(sd[f"nerf.geo_layer{i}.weight"]).astype(np.float32) for i in range(4)]
     halves = np.concatenate([_pack_split(Ws[3].T, 16), _pack_split(Ws[2].T, 16), _pack_split(Ws[1].T, 16),
@@ -222,7 +222,7 @@ def pack_sdf_mlp_bwd(sd):
 
 
 def pack_sdf_mlp(sd):
-    """-> float32 [SD_TOTAL] in the SD_* layout of csrc/decode.hip.
+    """-> float32 [SD_TOTAL] in the SD_* layout of csrc/sdf_mlp.hpp.
     Wp[w][kb][l][i] = W[32 w + (l & 31)][8 kb + 4 (l >> 5) + i]; layer 0 has K = 17 padded to 24."""
     lane = np.arange(64)
     n, h = lane & 31, lane >> 5
@@ -315,7 +315,7 @@ def pack_sdf_tcnn(params):
 
 def pack_sdf_tcnn_bwd(params):
     """Transposed layers of the tcnn SDF decoder for bnv_decode_pts_backward in MLP mode 2 -> float32 [5184]
-    (TB_* layout of csrc/decode.hip): W2^T, W1^T as hidden-layer packs, W0^T as an output-layer pack (32 rows =
+    (TB_* layout of csrc/decode_pts.hip): W2^T, W1^T as hidden-layer packs, W0^T as an output-layer pack (32 rows =
     the padded inputs), then row 0 of the output layer as 64 floats."""
     W0, W1, W2, W3 = _split_tcnn(params, 32)
     h16 = lambda W: W.astype(np.float16).astype(np.float32)     # the forward multiplies fp16 weights

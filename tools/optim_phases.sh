@@ -5,10 +5,10 @@
 # (tools/optimize_profile.py: "ray_batch_step ... synchronised ms").
 set -u
 cd "$(dirname "$0")/.."
-SRC="encode volume decode frontend tsdf mesh rays io shard pipeline probe"
+SRC=$(python3 -c "import os, sys; sys.path.insert(0, 'bnv_fusion_amd/csrc'); import build as b; print(' '.join(os.path.join(b.HERE, s) for s in b.SOURCES))")   # the library's own source list
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fno-fast-math -Wno-unused-function -w"
 for P in 1 2 3 4; do
-  [ -f tools/libbnv_optim_phase$P.so ] || /opt/rocm/bin/hipcc $FL -DBNV_OPTIM_PHASES=$P $(for f in $SRC; do echo bnv_fusion_amd/csrc/$f.hip; done) -o tools/libbnv_optim_phase$P.so
+  [ -f tools/libbnv_optim_phase$P.so ] || /opt/rocm/bin/hipcc $FL -DBNV_OPTIM_PHASES=$P $SRC -o tools/libbnv_optim_phase$P.so
 done
 for P in 0 1 2 3 4; do
   L=""; [ $P -gt 0 ] && L=$PWD/tools/libbnv_optim_phase$P.so

@@ -1,7 +1,8 @@
 """Phase breakdown of the lattice-table decode kernel (development tool).
-Build the instrumented library first:
+Build the instrumented library first (the sources are csrc/build.py's SOURCES):
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fno-fast-math -DBNV_PHASE_PROF \
-        bnv_fusion_amd/csrc/{encode,volume,decode,frontend,tsdf}.hip -o tools/libbnv_phase_prof.so
+        $(python -c "import os, sys; sys.path.insert(0, 'bnv_fusion_amd/csrc'); import build as b; print(' '.join(os.path.join(b.HERE, s) for s in b.SOURCES))") \
+        -o tools/libbnv_phase_prof.so
 then:  BNV_FUSION_LIB=tools/libbnv_phase_prof.so python tools/phase_prof.py
 Thread 0 of every workgroup accumulates shader-clock deltas between phase marks."""
 import ctypes as C
