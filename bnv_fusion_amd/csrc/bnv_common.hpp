@@ -14,7 +14,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kWave = 64;
-extern int g_num_cus;
+extern int g_num_cus;   // (these words: runtime.hip)
 extern int g_last_hip_error;
 // process-wide defaults / A-B switches: relaxed atomic words, read once per launch (bnv_set_mlp_mode, bnv_set_option)
 extern std::atomic<int> g_mlp_mode;
@@ -145,7 +145,7 @@ __device__ __forceinline__ uint32_t mix64(uint64_t k) {
   return (uint32_t)k;
 }
 
-// ---- first-touch ownership (bnv_grid_t::shard_state; encode.hip: k_shard_assign) ------------------------------------
+// ---- first-touch ownership (bnv_grid_t::shard_state; shard.hip: k_shard_assign) -------------------------------------
 // [header 1024 B: uint64 load[64] | int32 any_new | ...][owner table: 1 byte per block][block weights u32][new list u32]
 constexpr size_t kShardHdrBytes = 1024;
 constexpr uint8_t kOwnRank = 0x3f, kOwnAssigned = 0x40, kOwnTouched = 0x80;

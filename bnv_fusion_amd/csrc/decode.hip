@@ -594,7 +594,7 @@ __global__ __launch_bounds__(512, 2) void k_lattice_table_x(DecodeArgs A) {
     ring.hi[2] = load_frag(rs, voff, O1 + (w * 16) * 2048);
     if (NPROD == 3) ring.lo[2] = load_frag(rs, voff, O1 + (w * 16) * 2048 + 1024);
   }
-  // LDS byte addresses of this lane (opaque to the optimiser: base + 16-bit immediates, encode.hip: EncLds)
+  // LDS byte addresses of this lane (opaque to the optimiser: base + 16-bit immediates, encode_mlp.hip: EncLdsX)
   uint32_t act_hi, act_lo, park_hi, park_lo, st_hi, st_lo;
   {
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)lds;

@@ -1,5 +1,5 @@
 // pipeline.hip -- one frame of the hot path behind a handful of C calls (host-side orchestration only; the kernels
-// live in encode.hip / volume.hip / shard.hip / decode.hip / lattice.hip / tsdf.hip).
+// live in encode*.hip / volume.hip / shard.hip / decode.hip / lattice.hip / tsdf.hip).
 //
 // What NeuralMap.integrate (run_e2e.py:78-109) + the per-frame lattice decode (sparse_volume.py:697-738) cost the
 // host when every stage is a Python call of its own: ~15 kernel launches through ~8 ctypes calls, a dozen tensor

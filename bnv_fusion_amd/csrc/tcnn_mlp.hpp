@@ -5,7 +5,7 @@
 // (NK0 = 2); inputs are padded with 1.0 (the pad columns act as biases).
 //
 // This is the only place the tile is written.  Every kernel that runs these networks (sdf_mlp.hpp: sdf_mlp_tile_t;
-// decode_pts.hip: k_decode_pts_bwd_t; decode.hip: k_lattice_table_t; encode.hip: k_pointnet_scatter_t, k_pointnet_scatter_tb; train_tcnn.hip:
+// decode_pts.hip: k_decode_pts_bwd_t; decode.hip: k_lattice_table_t; encode_tcnn.hip: k_pointnet_scatter_t, k_pointnet_scatter_tb; train_tcnn.hip:
 // k_tcnn_tile) brings its own inputs and takes the outputs where it needs them; the operands and the MFMA order
 // per accumulator (mb outer, K-step inner, accumulate in place) are the ones below, so the kernels agree bit for bit.
 //

@@ -7,7 +7,7 @@
 // [out, in] matrices in layer order:  encoder 16 | 64 | 64 | 64 | 16 (10,240 weights), decoder 32 | 64 | 64 | 64 | 16
 // (11,264).  The input is padded with 1.0 to 16 / 32 columns (the pad columns act as biases).
 //
-// Forward = the mode-2 arithmetic of the inference kernels (encode.hip k_pointnet_scatter_tb, sdf_mlp.hpp
+// Forward = the mode-2 arithmetic of the inference kernels (encode_tcnn.hip k_pointnet_scatter_tb, sdf_mlp.hpp
 // sdf_mlp_tile_t), from the same code (tcnn_mlp.hpp): inputs and weights rounded to f16, every layer an f16 MFMA with
 // fp32 accumulation, ReLU after the hidden layers, every layer output rounded to f16.
 //

@@ -154,7 +154,7 @@ def walk_key(b, nb, axis):
 
 
 class OwnershipModel:
-    """Host restatement of the ownership rules of a spatially sharded volume (csrc/encode.hip: k_rank, k_shard_assign;
+    """Host restatement of the ownership rules of a spatially sharded volume (csrc/encode.hip: k_rank; csrc/shard.hip: k_shard_assign;
     csrc/bnv_common.hpp: voxel_owner, shard_is_boundary, shard_adjacent_to): fed the touched voxels of every frame in
     order, it holds the owner table every rank's device table must equal -- the specification the GPU tests compare
     with, and what tools/shard_model.py prices rules with.

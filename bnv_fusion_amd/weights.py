@@ -1,5 +1,5 @@
 """Weights of the fp32 point encoder / SDF decoder: loading, BatchNorm folding and the
-pre-permuted MFMA operand layouts the kernels read (csrc/encode.hip, csrc/sdf_mlp.hpp, csrc/decode.hip, csrc/decode_pts.hip).
+pre-permuted MFMA operand layouts the kernels read (csrc/encode.hpp, csrc/sdf_mlp.hpp, csrc/decode.hip, csrc/decode_pts.hip).
 
 State-dict key names are the reference's, so either the converted
 ``weights/pointnet_fp32.npz`` or a ``torch.load(ckpt)['state_dict']`` can be passed in.
@@ -87,7 +87,7 @@ def sdf_feature_bound(sd):
 
 
 def pack_pointnet(sd):
-    """-> float32 [34952 + split pack + 4] in the PN_* / PX_* layouts of csrc/encode.hip; the trailing 4 floats hold the
+    """-> float32 [34952 + split pack + 4] in the PN_* / PX_* layouts of csrc/encode.hpp; the trailing 4 floats hold the
     certified bound on |normal| of the split modes (pointnet_normal_bound) and padding.
 
     MFMA tile: lane l = (n = l & 31, h = l >> 5).  A K-step that consumes D register r of input
@@ -138,7 +138,7 @@ def _slot_feature(jj, h):
 
 
 def _pack_pointnet_split16(W1, W2, W3, W4):
-    """Split-operand layout PX_* of csrc/encode.hip (k_pointnet_scatter_x, v_mfma_f32_16x16x32_f16), as float32 words.
+    """Split-operand layout PX_* of csrc/encode.hpp (csrc/encode_mlp.hip: k_pointnet_scatter_x, v_mfma_f32_16x16x32_f16), as float32 words.
     A fragments: lane (m = l & 15, g = l >> 4), slot jj.  Layer 1: [8 rb][hi/lo][64][8] = W1[16 rb + m][8 g + jj]
     (6 inputs, the other 26 K slots zero).  Layers 2, 3: [4 s][8 rb][hi/lo][64][8] = W[16 rb + m][32 s + 16 (jj >> 2) +
     4 g + (jj & 3)] -- K-step s consumes what accumulator row blocks 2 s and 2 s + 1 of the previous layer hold.

@@ -106,14 +106,11 @@ def test_encode_empty_and_ragged(bnv, model):
         assert out[0] is None or out[2].shape[0] == out[0].shape[0]
 
 
-@pytest.mark.parametrize("pattern", ["one_voxel", "alternating", "runs_with_gaps", "run_across_tiles"])
-def test_encode_scatter_run_patterns_vs_oracle(bnv, model, orc, sd, pattern):
-    """The tile scatter sums RUNS of equal voxels inside 32-pair tiles (a prefix sum over the lanes and differences at
-    the run ends, csrc/encode.hip: scatter_tile): run shapes the golden frames do not pin -- one run filling every
-    tile, runs of length 1, invalid rows (NaN / out of bounds) cutting runs, runs crossing tile and half-tile
-    boundaries -- against the oracle's scatter_mean: counts bit-exact, features to the encoder tolerance."""
-    z = np.load(os.path.join(GOLDEN, "encode_64.npz"))
-    vol = _vol(bnv, z)
+RUN_PATTERNS = ["one_voxel", "alternating", "runs_with_gaps", "run_across_tiles"]
+
+
+def _run_pattern_pts(pattern):
+    """input_pts [1, 4096 + 19, 6] whose (point, corner) pairs form the named run pattern in the 32-pair tiles."""
     rng = np.random.default_rng(7)
     n = 4096 + 19                                               # ragged last tile
     a = np.array([0.113, -0.207, 0.051], np.float32)            # two points well inside different voxels
@@ -136,7 +133,18 @@ def test_encode_scatter_run_patterns_vs_oracle(bnv, model, orc, sd, pattern):
         xyz[:] = np.where((seg % 2 == 0)[:, None], a, b) + rng.uniform(-1e-3, 1e-3, (n, 3)).astype(np.float32)
     nrm = rng.normal(size=(n, 3)).astype(np.float32)
     nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
-    pts = torch.from_numpy(np.concatenate([xyz, nrm], 1)[None])
+    return torch.from_numpy(np.concatenate([xyz, nrm], 1)[None])
+
+
+@pytest.mark.parametrize("pattern", RUN_PATTERNS)
+def test_encode_scatter_run_patterns_vs_oracle(bnv, model, orc, sd, pattern):
+    """The tile scatter sums RUNS of equal voxels inside 32-pair tiles (a prefix sum over the lanes and differences at
+    the run ends, csrc/encode.hpp: tile_run_sums): run shapes the golden frames do not pin -- one run filling every
+    tile, runs of length 1, invalid rows (NaN / out of bounds) cutting runs, runs crossing tile and half-tile
+    boundaries -- against the oracle's scatter_mean: counts bit-exact, features to the encoder tolerance."""
+    z = np.load(os.path.join(GOLDEN, "encode_64.npz"))
+    vol = _vol(bnv, z)
+    pts = _run_pattern_pts(pattern)
     f, c, ids, g, navg = _encode(model, vol, pts)
     fo, co, io, go, no = orc.encode_pointcloud(sd, pts, vol.n_xyz.cpu(), vol.min_coords.cpu(), vol.max_coords.cpu(),
                                                vol.voxel_size)
@@ -837,6 +845,43 @@ def test_tcnn_checkpoint_encode_decode_vs_oracle(bnv, orc):
     a = m32.encode_pointcloud(torch.from_numpy(z["frames"][0]).to(DEV), nm.volume.n_xyz, nm.volume.min_coords,
                               nm.volume.max_coords, voxel, return_dense=False)
     assert bnv.get_mlp_mode() in (0, 1) and a[0].shape[1] == 8
+
+
+@pytest.mark.parametrize("pattern", RUN_PATTERNS)
+def test_tcnn_encode_scatter_run_patterns_vs_oracle(bnv, orc, pattern):
+    """The run patterns of test_encode_scatter_run_patterns_vs_oracle through the tiny-cuda-nn checkpoint: its tile
+    encoder and both forms of its block encoder sum runs with the same tile_run_sums / run_to_global (csrc/encode.hpp)
+    as the fp32 encoders.  Under the three (tcnn_block_encoder, tcnn_shared_table) settings: ids and counts bit-exact
+    against the oracle's fp16 restatement, features within the 3e-3 of the checkpoint test, and the three settings
+    bit-identical to each other (the sums are integers)."""
+    from conftest import WEIGHTS_TCNN
+    from bnv_fusion_amd import _lib
+    enc = orc.tcnn_point_encoder(orc.load_weights(WEIGHTS_TCNN)["pointnet_backbone.model.params"])
+    z = np.load(os.path.join(GOLDEN, "encode_64.npz"))
+    vol = _vol(bnv, z)
+    model = bnv.load_pretrained(device=DEV, voxel_size=float(z["voxel_size"]), tiny_cuda=True)
+    pts = _run_pattern_pts(pattern)
+    fo, co, io, go, no = orc.encode_pointcloud(None, pts, vol.n_xyz.cpu(), vol.min_coords.cpu(), vol.max_coords.cpu(),
+                                               vol.voxel_size, encoder=enc)
+    lib = _lib.load()
+    outs = []
+    try:
+        for opt, shared in ((1, 1), (1, 0), (0, 1)):
+            assert lib.bnv_set_option(b"tcnn_block_encoder", opt) == 0
+            assert lib.bnv_set_option(b"tcnn_shared_table", shared) == 0
+            f, c, ids, g, navg = _encode(model, vol, pts)
+            assert torch.equal(ids.cpu(), io) and torch.equal(c.cpu(), co) and torch.equal(g.cpu(), go), (opt, shared)
+            assert float(navg) == float(no)
+            err = float((f.cpu() - fo).abs().max())
+            print(f"tcnn run pattern {pattern} block_encoder={opt} shared_table={shared}: max feature err {err:.3e}")
+            assert err <= 3e-3, (opt, shared, err)
+            outs.append((f, c, ids, g))
+    finally:
+        lib.bnv_set_option(b"tcnn_block_encoder", 1)
+        lib.bnv_set_option(b"tcnn_shared_table", 1)
+    for other in outs[1:]:
+        for a, b in zip(outs[0], other):
+            assert torch.equal(a, b)
 
 
 def test_volume_list_wrapper(bnv, model, golden_volume):

@@ -1,6 +1,6 @@
 """CPU emulation of the v_mfma_f32_32x32x2_f32 lane/register layout, used to check that the
 host-side weight packing (bnv_fusion_amd/weights.py) matches the index arithmetic of the kernels
-(csrc/encode.hip k_pointnet_scatter, csrc/sdf_mlp.hpp sdf_mlp_tile) without a GPU.
+(csrc/encode_mlp.hip k_pointnet_scatter, csrc/sdf_mlp.hpp sdf_mlp_tile) without a GPU.
 
 Layout (cdna_hip_programming.md section 3): A lane l holds A[i = l & 31][k = l >> 5]; B lane l holds
 B[k = l >> 5][j = l & 31]; D lane l register r holds D[i = (r & 3) + 8 (r >> 2) + 4 (l >> 5)][j = l & 31].

@@ -14,7 +14,7 @@ tests/test_gpu_multiprocess.py):
 * the decode of an emitted voxel: 27 lattice points at {-.5, 0, .5}^3; a point is LIVE when all 8 corner voxels carry
   weight >= min_pts (sparse_volume.py:768-833); a live point reads 8 table entries (corner voxel, local offset);
   the table kernel evaluates every DISTINCT entry live points of the rank's own voxels read;
-* ownership rules (distributed.py / csrc/encode.hip): block hash, round 4's greedy first touch + lattice pin, round 5's
+* ownership rules (distributed.py / csrc/shard.hip): block hash, round 4's greedy first touch + lattice pin, round 5's
   region-growing first touch.
 
 Reported per evaluated frame and as means: evaluations per rank, their sum over the single-volume count (duplicated
