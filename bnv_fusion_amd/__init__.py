@@ -36,6 +36,7 @@ from .evaluate import evaluate_meshes, nearest_neighbors, sample_surface  # noqa
 from .mesh import TriMesh, load_ply  # noqa: F401,E402
 from . import tracking  # noqa: F401,E402
 from .tracking import Tracker, icp_align  # noqa: F401,E402
+from .frontend import DepthFilter, filter_depth  # noqa: F401,E402
 
 
 MLP_MODE_FP32_EXACT = 0     # v_mfma_f32_32x32x2_f32

@@ -45,6 +45,7 @@ SYMBOLS = [
     "bnv_mesh_sdf_workspace_bytes", "bnv_mesh_sdf_build", "bnv_mesh_sdf_query",
     "bnv_mesh_ray_workspace_bytes", "bnv_mesh_ray_cast", "bnv_mesh_render_depth", "bnv_depth_sensor",
     "bnv_icp_workspace_bytes", "bnv_icp_align",
+    "bnv_depth_filter",
 ]
 
 
@@ -323,6 +324,8 @@ def load():
                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), i32, C.POINTER(i32), C.c_double, C.c_double, C.c_double, vp,
                                     sz, vp, vp, vp, vp, vp]),
+        "bnv_depth_filter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, vp,
+                                       C.c_int, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

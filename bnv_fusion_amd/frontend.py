@@ -4,6 +4,7 @@ Replaces the float64 numpy/kornia code of FusionInferenceAbstractDataset.__getit
 (src/datasets/fusion_inference_dataset.py:40-90) that the reference runs on DataLoader workers and
 then uploads (7.4 MB/frame): here the 0.6 MB uint16 depth image is what crosses PCIe.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -61,3 +62,64 @@ def depth_to_input_pts(depth, intr_mat, T_wc, max_depth=10.0, compact=True, conf
     if not compact:
         return out.unsqueeze(0), n
     return out[: int(n.item())].unsqueeze(0)
+
+
+# ---- depth filter (csrc/depth_filter.hip; include/bnv_fusion.h, "Depth filter") ---------------------------------------
+
+DEFAULT_SIGMA_DEPTH = 2.0 / (8 * 35.130)    # two disparity steps of the reference's sensor model at 1 m (geometry.py:54-69)
+
+
+def filter_depth(depth, max_depth=3.0, radius=3, sigma_depth=DEFAULT_SIGMA_DEPTH, range_cut=3.0, conf=None,
+                 conf_level=0):
+    """Edge-preserving smoothing of a depth image on the GPU, for the front end's normals and the tracker: a bilateral
+    filter with Tukey biweight kernels, ``radius`` 1..8 pixels, whose range width is ``sigma_depth * z^2`` metres (the
+    sensor's disparity noise grows with z^2) and which ignores taps further than ``range_cut`` widths from the centre
+    pixel's depth.  depth [H, W] or [1, H, W] on the GPU: uint16/int16 millimetres or float32/float64 metres.  Pixels
+    outside (0, max_depth), non-finite ones and, with ``conf`` ([H, W] uint8), those below ``conf_level`` are neither
+    smoothed nor used: they come back as 0.  Returns float32 metres [H, W]; float64 arithmetic in a fixed order, the
+    same bits on every call (tests/depth_filter_restatement.py is the definition in numpy).  GPU only."""
+    if not (torch.is_tensor(depth) and depth.is_cuda):
+        raise _lib.BnvError("filter_depth runs on the GPU only: depth must be a device tensor (no CPU fallback)")
+    if depth.dtype not in DEPTH_DTYPES:
+        raise _lib.BnvError(f"filter_depth: depth must be uint16 millimetres or float32 / float64 metres, got "
+                            f"{depth.dtype}")
+    d = depth[0] if depth.dim() == 3 and depth.shape[0] == 1 else depth
+    if d.dim() != 2 or d.numel() == 0:
+        raise _lib.BnvError(f"filter_depth: expected a non-empty [H, W] image, got {tuple(depth.shape)}")
+    lib = _lib.require_device(d.device.index or 0)
+    d = d.contiguous()
+    H, W = int(d.shape[0]), int(d.shape[1])
+    c, c_ptr, level = conf_arg(conf, conf_level, (H, W), d.device, "filter_depth")
+    with torch.cuda.device(d.device):
+        out = torch.empty((H, W), dtype=torch.float32, device=d.device)
+        _lib.check(lib.bnv_depth_filter(_lib.ptr(d), DEPTH_DTYPES[d.dtype], H, W, float(max_depth), int(radius),
+                                        float(sigma_depth), float(range_cut), c_ptr, level, _lib.ptr(out),
+                                        _lib.stream_ptr()), "bnv_depth_filter")
+    return out
+
+
+class DepthFilter(collections.namedtuple("DepthFilter", "radius sigma_depth range_cut",
+                                         defaults=(3, DEFAULT_SIGMA_DEPTH, 3.0))):
+    """The settings of ``filter_depth`` as one immutable object (``NeuralMap(..., depth_filter=DepthFilter())``)."""
+    __slots__ = ()
+
+    def apply(self, frame, max_depth):
+        """A shallow copy of the frame dict whose ``depth`` is the filtered image (float32 metres) and whose
+        ``depth_filtered`` is True (``depth_ready``: an event behind the filter kernel on the current stream); the
+        frame's ``conf`` / ``conf_level`` gate the filter and stay in the frame.  A
+        frame that already carries ``depth_filtered``, and one with ``input_pts`` and no ``depth``, is returned as it
+        is."""
+        if frame.get("depth_filtered") or frame.get("depth") is None:
+            return frame
+        gate = {}
+        if frame.get("conf") is not None:
+            gate = {"conf": frame["conf"], "conf_level": int(frame.get("conf_level", 0))}
+        out = dict(frame)
+        out["depth"] = filter_depth(frame["depth"], max_depth=max_depth, radius=self.radius,
+                                    sigma_depth=self.sigma_depth, range_cut=self.range_cut, **gate)
+        out["depth_filtered"] = True
+        # behind the filter kernel on the stream that runs it: NeuralMap.fuse_and_decode_async does not treat the
+        # frame as resident (inputs_resident) before this event has completed
+        out["depth_ready"] = torch.cuda.Event()
+        out["depth_ready"].record()
+        return out

@@ -5,6 +5,7 @@
                                   section 8d): integrate + the 3x3x3 meshing lattice of every voxel the frame's
                                   encode returned; the async form never synchronises with the host;
 * ``optimize``                    run_e2e.py:111-162: the global optimiser over ``self.frames``;
+* ``prepare_frame``               the optional depth filter (frontend.DepthFilter) in front of all of the above;
 * ``extract_mesh`` / ``save``     run_e2e.py:164-194.
 """
 import ctypes as C
@@ -106,8 +107,11 @@ class PipeHandle:
 class NeuralMap:
     def __init__(self, dimensions, voxel_size, pointnet, min_pts_in_grid=8, feature_vector_size=8,
                  capacity=100000, device="cuda:0", tsdf=False, truncated_units=10, sdf_delta_weight=0.1,
-                 max_depth=3.0):
+                 max_depth=3.0, depth_filter=None):
         self.pointnet = pointnet
+        # None, or a frontend.DepthFilter: every depth frame is smoothed once (prepare_frame) before the front end,
+        # the TSDF side fusion and the tracker read it.  None changes nothing.
+        self.depth_filter = depth_filter
         # depth cut-off of the reference's loader (model.ray_tracer.ray_max_dist, fusion_pointnet_model.yaml:43 ->
         # fusion_inference_dataset.py:28 -> common.py:110-113): applies to input_pts AND to the TSDF side fusion,
         # both of which see ``depth * mask`` in the reference (run_e2e.py:100-109 reads frame['rgbd'])
@@ -134,7 +138,9 @@ class NeuralMap:
         self._pipe = None
         self._pipe_open = []
         # True: the caller guarantees that a frame's tensors are complete in device memory when it is passed in
-        # (uploaded / produced and synchronised earlier), so the encode stream need not wait for the caller's stream
+        # (uploaded / produced and synchronised earlier), so the encode stream need not wait for the caller's stream.
+        # A depth image the depth filter made (prepare_frame, here or by the caller) is resident only once its
+        # ``depth_ready`` event has completed; until then the encode stream waits for the caller's stream regardless.
         self.inputs_resident = False
         self._vol_ev = None            # behind the last TSDF update a synchronous integrate() enqueued (main stream)
         self.sdf_delta_weight = sdf_delta_weight                          # fusion_pointnet_model.yaml:44,47
@@ -144,6 +150,20 @@ class NeuralMap:
             from .tsdf import TSDFVolume
             mn, mx, _ = get_world_range(dimensions, self.tsdf_voxel_size)
             self.tsdf_vol = TSDFVolume(np.stack([mn, mx], 1), self.tsdf_voxel_size, device=device)
+
+    def prepare_frame(self, frame):
+        """The frame as ``integrate``, ``fuse_and_decode[_async]`` and ``track`` read it: with a ``depth_filter`` set, a
+        shallow copy whose ``depth`` is the filtered image (float32 metres, produced on the current stream) and whose
+        ``depth_filtered`` is True; a frame that carries that mark already, a frame without ``depth`` and every frame
+        of a map without a filter come back as they are.  Those calls do this themselves; call it to filter a frame
+        once for several of them (``tracking.Tracker.integrate`` does), or to keep the filtered image: ``optimize``
+        reads ``self.frames``, which the caller fills, so key frames appended after ``prepare_frame`` are optimised
+        on the filtered depth and raw ones on the raw depth.  The copy also carries ``depth_ready``, an event behind the
+        filter kernel on the stream that ran it: ``fuse_and_decode_async`` takes a prepared frame as resident
+        (``inputs_resident``) only once that event has completed, so a frame prepared a moment ago is safe to pass."""
+        if self.depth_filter is None:
+            return frame
+        return self.depth_filter.apply(frame, self.max_depth)
 
     def prepare_tsdf_volume(self):
         """run_e2e.py:169-186 -> sdf_delta [1, 1, X, Y, Z] for decode_pts / meshlize."""
@@ -165,7 +185,7 @@ class NeuralMap:
             if h.pending:
                 h.result()
 
-    def _pipe_frame(self, frame, decode):
+    def _pipe_frame(self, frame, decode, resident):
         from .pipeline import FramePipe
         n = int(frame["input_pts"].shape[1]) if "input_pts" in frame else int(frame["depth"].shape[-2] * frame["depth"].shape[-1])
         if self._pipe is None or self._pipe.max_points < n or self._pipe.pointnet is not self.pointnet \
@@ -174,7 +194,7 @@ class NeuralMap:
             self._pipe = FramePipe(self.volume, self.pointnet, n, n_slots=4, tsdf_vol=self.tsdf_vol,
                                    max_depth=self.max_depth)
         pipe = self._pipe
-        pipe.inputs_resident, pipe.sdf_delta = self.inputs_resident, self.sdf_delta
+        pipe.inputs_resident, pipe.sdf_delta = resident, self.sdf_delta
         self._pipe_open = [h for h in self._pipe_open if h.pending]
         while pipe.free_slot() is None:                 # every slot holds an uncollected frame: collect the oldest
             self._pipe_open.pop(0).result()
@@ -193,6 +213,7 @@ class NeuralMap:
         """run_e2e.py:78-98.  frame['input_pts'] : [1, N, 6] float32 on the GPU (or a depth frame, see
         frame_input_pts).
         Returns the voxel coordinates the frame touched ([U', 3] int64) or None."""
+        frame = self.prepare_frame(frame)
         self._drain_pipe()
         input_pts = frame_input_pts(frame, self.max_depth)
         if len(input_pts) == 0:
@@ -219,7 +240,7 @@ class NeuralMap:
     def fuse_and_decode(self, frame):
         """One benchmark work unit: integrate + SDF lattice [U', 27] of the touched voxels (live
         volume values, i.e. decode_pts(..., is_coords=True, query_tensor=False))."""
-        coords = self.integrate(frame)
+        coords = self.integrate(frame)               # (filters the frame's depth when a depth_filter is set)
         if coords is None:
             return None, None
         sdf = self.volume.decode_lattice(coords, self.pointnet.nerf, self.sdf_delta, query_tensor=False)
@@ -243,9 +264,16 @@ class NeuralMap:
         queued before frame t + 1's upsert / decode front end runs (+5 % frames/s, bench.py) -- to keep the GPU busy
         (``result()`` also settles the frame's row reservation and raises on a device-side upsert error).  Any number
         of uncollected frames gives the synchronous results bit for bit."""
+        frame = self.prepare_frame(frame)
+        # a depth image filtered just now is still being produced on the caller's stream: the encode stream waits for
+        # that stream for this frame, whatever inputs_resident promises about the caller's own tensors
+        # -- and the same holds for a frame the caller prepared (prepare_frame) a moment ago: the event the filter left
+        # in the frame tells (a host-side query, no wait)
+        ready = frame.get("depth_ready")
+        resident = self.inputs_resident and (ready is None or ready.query())
         if self.frame_pipe and self.overlap_encode and not self.pointnet.dense_volume and not (
                 "input_pts" not in frame and frame["depth"].dtype == torch.float64 and self.tsdf_vol is not None):
-            return self._pipe_frame(frame, decode)
+            return self._pipe_frame(frame, decode, resident)
         self._drain_pipe()
         with torch.no_grad():
             v = self.volume
@@ -255,7 +283,7 @@ class NeuralMap:
                     from .streams import concurrent_stream
                     self._enc_stream = concurrent_stream(v._dev, main)     # one that really runs beside `main`
                 enc = self._enc_stream
-                if self.inputs_resident:
+                if resident:
                     # only a synchronous integrate() on the caller's stream can still hold the TSDF volume
                     if self._vol_ev is not None:
                         enc.wait_event(self._vol_ev)
@@ -386,10 +414,12 @@ class NeuralMap:
         ``render`` (``source="neural"``) or ``render_tsdf`` ("tsdf"), ``model_size`` = (H, W) of that view (default
         the frame's; smaller is cheaper), and runs ``tracking.icp_align`` of the frame against it -> ``TrackResult``
         (``.T_wc``: the corrected camera-to-world pose, or the guess when ``.status`` is not OK).  Reads the map only;
-        waits for the frames still in the pipeline, as ``render`` does."""
+        waits for the frames still in the pipeline, as ``render`` does.  With a ``depth_filter`` the frame is aligned on
+        its filtered depth (``prepare_frame``)."""
         from . import tracking
         if source not in ("neural", "tsdf"):
             raise ValueError(f"source {source!r}: 'neural' or 'tsdf'")
+        frame = self.prepare_frame(frame)
         render = self.render if source == "neural" else self.render_tsdf
         icp.setdefault("max_depth", self.max_depth)
         return tracking.track_against(render, frame, T_guess, model_size, **icp)

@@ -171,6 +171,7 @@ class Tracker:
         self._prev_given = self._prev_tracked = None
 
     def integrate(self, frame):
+        frame = self.nm.prepare_frame(frame)      # the map's depth filter, once: tracking and fusion read one image
         given = np.asarray(frame["T_wc"], dtype=np.float64).reshape(4, 4)
         if len(self.poses) < self.warmup or self._prev_given is None:
             T, status = given, -1

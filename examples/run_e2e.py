@@ -8,6 +8,7 @@ sequence directory, periodic global optimisation, mesh extraction, final artefac
     python examples/run_e2e.py --synthetic-arkit 24 --out /tmp/bnv_arkit                    # writes a synthetic one first
     python examples/run_e2e.py --sweep 60 --grid 256 --pose-drift 0.005 0.003 --track tsdf --no-optimize --out /tmp/trk
                                                     # drifting odometry, every frame aligned to the map before it is fused
+    python examples/run_e2e.py ... --depth-filter                                           # smooth every depth image first
     python examples/run_e2e.py --sweep 600 --grid 512 --decode-frames --pipelined --no-optimize --out /tmp/sweep
                                                     # a moving-camera room sweep (bnv_fusion_amd/sequence.py), per-frame
                                                     # SDF decode of the touched voxels, two frames in flight
@@ -92,7 +93,20 @@ def main():
                          "SIGMA_R radians per frame and axis, seed 0); the frames are held in memory.  With --track the "
                          "run fuses a second map from the drifted poses as they are and prints trajectory_errors (and, "
                          "with --eval-gt, the F-score) of both")
+    ap.add_argument("--depth-filter", type=float, nargs="*", metavar="RADIUS SIGMA_DEPTH",
+                    help="smooth every depth image on the GPU before fusion, tracking and optimisation "
+                         "(frontend.DepthFilter: edge-preserving, range width SIGMA_DEPTH * z^2 metres).  Bare: radius 3 "
+                         "and two disparity steps of the Kinect model at 1 m; or give both values.  Off by default")
     args = ap.parse_args()
+    depth_filter = None
+    if args.depth_filter is not None:
+        from bnv_fusion_amd import frontend
+        if len(args.depth_filter) not in (0, 2):
+            ap.error("--depth-filter takes no value or RADIUS SIGMA_DEPTH")
+        if args.depth_filter and not (args.depth_filter[0].is_integer() and 1 <= args.depth_filter[0] <= 8):
+            ap.error(f"--depth-filter: RADIUS must be an integer from 1 to 8, got {args.depth_filter[0]:g}")
+        depth_filter = frontend.DepthFilter(*((int(args.depth_filter[0]), args.depth_filter[1])
+                                              if args.depth_filter else ()))
     os.makedirs(args.out, exist_ok=True)
     dev = "cuda:0"
 
@@ -126,7 +140,7 @@ def main():
         data = datasets.FusionInferenceDataset(args.data_dir, args.scan_id, skip_images=args.skip_images, device=dev)
     model = bnv.load_pretrained(device=dev, voxel_size=args.voxel_size, tiny_cuda=args.tiny_cuda, path=args.weights)
     nm = bnv.NeuralMap(data.dimensions, args.voxel_size, model, capacity=1 << 20, device=dev, tsdf=True,
-                       max_depth=data.max_depth)
+                       max_depth=data.max_depth, depth_filter=depth_filter)
     t_local = t_global = 0.0
     max_depth = data.max_depth
     truth = tracker = None
@@ -143,7 +157,8 @@ def main():
         # the per-frame loop of the benchmark metric: fuse + decode of the touched voxels, synchronous or pipelined
         from bnv_fusion_amd import sequence
         nm.volume.reset(100000)                  # the reference's initial capacity: the tables grow on demand
-        st = sequence.run(nm, data, pipelined=args.pipelined, in_flight=2, checksums=False,
+        # (prepare_frame: the key frames the optimiser reads later hold the filtered depth; the raw frame without one)
+        st = sequence.run(nm, (nm.prepare_frame(fr) for fr in data), pipelined=args.pipelined, in_flight=2, checksums=False,
                           on_frame=lambda k, fr, c, s: nm.frames.append(fr))
         print(f"fused + decoded {st['frames']} frames ({st['empty_frames']} without a point inside the volume) at "
               f"{st['frames'] / st['seconds']:.1f} frames/s incl. file reading; {nm.volume.num_rows()} voxels")
@@ -151,6 +166,7 @@ def main():
         t_local = st["seconds"]
     for idx, frame in enumerate(data):                                   # run_e2e.py:243-279
         t0 = time.perf_counter()
+        frame = nm.prepare_frame(frame)             # --depth-filter: filtered once, for tracking, fusion and nm.frames
         if tracker is not None and not np.isnan(frame["T_wc"]).any():
             tracker.integrate(frame)
             frame = dict(frame, T_wc=tracker.poses[-1])              # the optimiser's rays start at the corrected pose
@@ -241,7 +257,7 @@ def compare_given_and_tracked(args, frames, truth, tracker, tracked_mesh, model,
     from bnv_fusion_amd import evaluate
     from bnv_fusion_amd.mesh import load_ply
     plain = bnv.NeuralMap(nm.dimensions, args.voxel_size, model, capacity=1 << 20, device=dev, tsdf=True,
-                          max_depth=nm.max_depth)
+                          max_depth=nm.max_depth, depth_filter=nm.depth_filter)
     for fr in frames:
         plain.integrate(fr)
     given = np.stack([fr["T_wc"] for fr in frames])

@@ -1240,6 +1240,30 @@ int bnv_icp_align(const void* depth, int depth_dtype, int32_t H, int32_t W, cons
                   double min_pair_share, double min_spread, void* workspace, size_t ws_bytes, double* pose_out,
                   double* poses_out, double* stats_out, int32_t* status_out, bnv_stream_t stream);
 
+/* ---- Depth filter (bnv_fusion_amd/csrc/depth_filter.hip; bnv_fusion_amd/frontend.py: filter_depth): edge-preserving
+ * smoothing of a depth image in front of the front end and the tracker.  Sensor depth is disparity-quantised (one
+ * step of the reference's Kinect model is z^2 / (8 * 35.130): 3.6 mm at 1 m, 32 mm at 3 m) and the front end's 3x3
+ * Sobel makes poor normals of such a staircase.  A bilateral filter whose spatial and range kernels are Tukey
+ * biweights: float64 arithmetic in the order below, no transcendental function, one rounding to float32 at the end.
+ *
+ * depth [H, W] / depth_dtype / max_depth / conf / conf_level as for bnv_depth_to_points_gated.  z(q) is the depth of
+ * pixel q in metres as a double (uint16: (double)u / 1000.0); q is valid when 0 < z(q) < max_depth (NaN and inf are
+ * not) and, with a confidence map, conf[q] >= conf_level.  Spatial weight of the offset (dy, dx), r = radius:
+ * a = 1.0 - (double)(dy dy + dx dx) / (double)((r + 1) (r + 1)), wa = a a; taps with a <= 0 are skipped.  For a valid
+ * centre p: s = sigma_depth z_p z_p, c = range_cut s, ic = 1.0 / c; over the taps in row-major order (dy = -r..r outer,
+ * dx = -r..r inner) that lie inside the image (no padding), are valid and have |z_q - z_p| < c:
+ *     t = (z_q - z_p) ic,  b = 1.0 - t t,  w = wa (b b),  num += w z_q,  den += w;
+ * out[p] = (float)(num / den) (the centre tap always counts, with w = 1).  An invalid centre gives 0.0f.  out is
+ * float32 metres [H, W], device memory.  The range width grows with z^2 as the sensor's noise does: sigma_depth is
+ * the width in metres at 1 m.  Deterministic: the same input gives the same bits.
+ * A null depth or out, out overlapping depth, H or W <= 0 or > 32768, depth_dtype other than 0 / 1 / 2, a radius
+ * outside 1..BNV_DEPTH_FILTER_MAX_RADIUS, a max_depth, sigma_depth or range_cut that is not positive and finite, and
+ * a confidence level without a map are BNV_ERR_INVALID_ARGUMENT before any HIP call. */
+#define BNV_DEPTH_FILTER_MAX_RADIUS 8
+int bnv_depth_filter(const void* depth, int depth_dtype, int H, int W, double max_depth, int radius,
+                     double sigma_depth, double range_cut, const uint8_t* conf, int conf_level, float* out,
+                     bnv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
