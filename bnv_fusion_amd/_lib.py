@@ -46,6 +46,8 @@ SYMBOLS = [
     "bnv_mesh_ray_workspace_bytes", "bnv_mesh_ray_cast", "bnv_mesh_render_depth", "bnv_depth_sensor",
     "bnv_icp_workspace_bytes", "bnv_icp_align",
     "bnv_depth_filter",
+    "bnv_mesh_normals_workspace_bytes", "bnv_mesh_vertex_normals", "bnv_mesh_color_workspace_bytes",
+    "bnv_mesh_color_begin", "bnv_mesh_color_accumulate", "bnv_mesh_color_resolve",
 ]
 
 
@@ -97,6 +99,13 @@ class FramePipeConfig(C.Structure):
                 ("n_slots", C.c_int32), ("slots", FrameSlot * 8), ("encode_stream", C.c_void_p),
                 ("main_stream", C.c_void_p), ("enc_ws2", C.c_void_p), ("front_stream", C.c_void_p),
                 ("blend_stream", C.c_void_p), ("encoder_workgroups", C.c_int32)]
+
+
+class MeshColorFrame(C.Structure):      # bnv_mesh_color_frame_t
+    _fields_ = [("depth", C.c_void_p), ("conf", C.c_void_p), ("rgb", C.c_void_p), ("depth_dtype", C.c_int32),
+                ("conf_level", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("color_height", C.c_int32),
+                ("color_width", C.c_int32), ("K", C.c_double * 4), ("K_color", C.c_double * 4),
+                ("T_cw", C.c_double * 12), ("center", C.c_double * 3)]
 
 
 class BnvError(RuntimeError):
@@ -326,6 +335,13 @@ def load():
                                     sz, vp, vp, vp, vp, vp]),
         "bnv_depth_filter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, vp,
                                        C.c_int, vp, vp]),
+        "bnv_mesh_normals_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
+        "bnv_mesh_vertex_normals": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+        "bnv_mesh_color_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
+        "bnv_mesh_color_begin": (C.c_int, [vp, i64, i64, vp]),
+        "bnv_mesh_color_accumulate": (C.c_int, [vp, vp, i64, C.POINTER(MeshColorFrame), i32, C.c_double, C.c_double,
+                                                C.c_double, C.c_double, vp, i64, vp]),
+        "bnv_mesh_color_resolve": (C.c_int, [vp, i64, i64, C.POINTER(C.c_uint8), vp, vp, vp, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

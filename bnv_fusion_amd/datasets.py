@@ -5,13 +5,14 @@
     <data_dir>/<scan_id>/pose/T_wc_<i>.txt      16 numbers on one line: camera-to-world, row-major
     <data_dir>/<scan_id>/pose/intr_mat_<i>.txt  9 (or 16) numbers on one line
     <data_dir>/<scan_id>/pose/dimensions.txt    3 numbers: the metric extent of the volume
-    <data_dir>/<scan_id>/image/<i>.jpg          colour (only counted, never decoded on this path)
+    <data_dir>/<scan_id>/image/<i>.jpg          colour (decoded only on request: ``load_rgb=True``, for mesh colouring)
 
 ``ARKitDataset`` reads the other layout the reference offers (``FusionInferenceDatasetARKit``,
 fusion_inference_dataset.py:242-306): an iPhone / iPad LiDAR capture exported by the *3D Scanner* app ("All Data"),
 
     <data_dir>/<scan_id>/depth_<n>.png    16-bit greyscale, millimetres (256x192 on current devices)
     <data_dir>/<scan_id>/conf_<n>.png     8-bit greyscale, ARKit depth confidence 0 / 1 / 2
+    <data_dir>/<scan_id>/frame_<n>.jpg    colour, 1920x1440 (decoded only on request: ``load_rgb=True``)
     <data_dir>/<scan_id>/frame_<n>.json   cameraPoseARFrame (4x4, row-major, ARKit camera axes), intrinsics (3x3,
                                           row-major, of the 1920x1440 colour image)
     <data_dir>/<scan_id>/export.obj       the app's rough mesh: its bounds place the volume
@@ -137,11 +138,38 @@ def _read_matrix(path):
     return vals.reshape(n, n).astype(np.float32)
 
 
+def read_rgb(path):
+    """A colour image file -> uint8 [H, W, 3] (red, green, blue) on the host, decoded by Pillow, which is imported here
+    and only here: nothing else in the package needs it."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError(f"load_rgb=True needs Pillow to decode {path} (import PIL failed: {e}); the depth path "
+                          "does not") from None
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{path}: missing -- the colour image of the frame (load_rgb=True)")
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
+
+
+def _scaled_intrinsics(intr, sy, sx):
+    """Intrinsics of the same view resampled by (sy, sx), integer pixel coordinates being pixel centres:
+    u' = (u + 0.5) s - 0.5."""
+    out = np.asarray(intr, dtype=np.float64).copy()
+    out[0, 0], out[0, 2] = out[0, 0] * sx, (out[0, 2] + 0.5) * sx - 0.5
+    out[1, 1], out[1, 2] = out[1, 1] * sy, (out[1, 2] + 0.5) * sy - 0.5
+    return out
+
+
 class FusionInferenceDataset:
-    """fusion_inference_dataset.py:105-146 for the per-frame path: ``dimensions`` and frames in order."""
+    """fusion_inference_dataset.py:105-146 for the per-frame path: ``dimensions`` and frames in order.  ``load_rgb``:
+    every frame also carries ``rgb`` (uint8 [Hc, Wc, 3] on the host, ``image/<i>.jpg``) for
+    mesh.VertexColorer, and ``rgb_intr_mat`` when the colour image is not of the depth image's size (the same view is
+    assumed: the depth intrinsics rescaled)."""
 
     def __init__(self, data_dir, scan_id, skip_images=1, downsample_scale=1.0, max_depth=3.0, device="cuda:0",
-                 num_images=None):
+                 num_images=None, load_rgb=False):
+        self.load_rgb = bool(load_rgb)
         # max_depth: cfg.model.ray_tracer.ray_max_dist (fusion_inference_dataset.py:28; 3 m in
         # fusion_pointnet_model.yaml:43).  The frames carry the raw depth image; the cut-off is applied by the
         # kernels (NeuralMap(max_depth=dataset.max_depth)), where the reference's load_depth zeroes the image.
@@ -168,13 +196,19 @@ class FusionInferenceDataset:
             # load_depth's dense mode (common.py:96-103): nearest-neighbour resize, intrinsics scaled (:135)
             depth = _resize_nearest(depth, self.downsample_scale)
             intr[:2, :3] *= self.downsample_scale
-        return {
+        frame = {
             "frame_id": i, "scene_id": self.scan_id, "max_depth": self.max_depth,
             "depth": torch.from_numpy(depth).to(self.device),
             "depth_path": os.path.join(self.root, "depth", f"{i}.png"),
             "intr_mat": intr.astype(np.float64),
             "T_wc": _read_matrix(os.path.join(self.root, "pose", f"T_wc_{i}.txt")).astype(np.float64),
         }
+        if self.load_rgb:
+            frame["rgb"] = read_rgb(os.path.join(self.root, "image", f"{i}.jpg"))
+            if frame["rgb"].shape[:2] != depth.shape:
+                frame["rgb_intr_mat"] = _scaled_intrinsics(intr, frame["rgb"].shape[0] / depth.shape[0],
+                                                           frame["rgb"].shape[1] / depth.shape[1])
+        return frame
 
     def __iter__(self):
         for k in range(len(self)):
@@ -218,10 +252,12 @@ class ARKitDataset:
     ...) and also carries the confidence map (``conf`` uint8 on the device) and ``conf_level``: NeuralMap keeps the
     pixels with ``0 < depth < max_depth`` and ``conf >= conf_level`` as points and as training rays; the normals and the
     TSDF side fusion see the range-masked depth, as in the reference.  ``skip_images`` (the reference ignores it for
-    this layout) keeps every k-th frame; the default keeps all."""
+    this layout) keeps every k-th frame; the default keeps all.  ``load_rgb``: every frame also carries ``rgb``
+    (``frame_<n>.jpg``, uint8 [1440, 1920, 3] on the host) and ``rgb_intr_mat``, the file's own intrinsics."""
 
     def __init__(self, data_dir, scan_id, confidence_level=2, max_depth=3.0, downsample_scale=1.0,
-                 intr_scale=ARKIT_INTR_SCALE, skip_images=1, device="cuda:0"):
+                 intr_scale=ARKIT_INTR_SCALE, skip_images=1, device="cuda:0", load_rgb=False):
+        self.load_rgb = bool(load_rgb)
         self.root = os.path.join(data_dir, scan_id)
         self.scan_id = scan_id
         self.device = device
@@ -255,17 +291,22 @@ class ARKitDataset:
             cam = json.load(fh)
         T_wc = self.axis_align_mat @ np.asarray(cam["cameraPoseARFrame"], dtype=np.float64).reshape(4, 4) @ _ARKIT_FLIP
         intr = np.asarray(cam["intrinsics"], dtype=np.float64).reshape(3, 3)      # (a fresh array: scaled in place)
+        color_intr = intr.copy()
         intr[:2, :3] *= self.intr_scale * self.downsample_scale
         if self.downsample_scale != 1.0:
             depth = _resize_nearest(depth, self.downsample_scale)
             conf = _resize_nearest(conf, self.downsample_scale)
-        return {
+        frame = {
             "frame_id": k, "scene_id": self.scan_id, "max_depth": self.max_depth,
             "depth": torch.from_numpy(depth).to(self.device),
             "conf": torch.from_numpy(conf).to(self.device), "conf_level": self.confidence_level,
             "depth_path": depth_path, "conf_path": conf_path,
             "intr_mat": intr, "T_wc": T_wc,
         }
+        if self.load_rgb:
+            frame["rgb"] = read_rgb(os.path.join(self.root, f"frame_{n}.jpg"))
+            frame["rgb_intr_mat"] = color_intr
+        return frame
 
     def __iter__(self):
         for k in range(len(self)):

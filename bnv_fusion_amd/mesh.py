@@ -47,28 +47,55 @@ def to_host(*tensors):
 
 
 class TriMesh:
+    """``vertices`` [V, 3] float32, ``faces`` [T, 3] int64.  Optional per-vertex attributes, None unless set:
+    ``vertex_normals`` [V, 3] float32 and ``vertex_colors`` [V, 3] uint8 (red, green, blue), computed on the final mesh
+    (``vertex_normals`` / ``color_vertices``; ``extract_mesh(normals=..., color=...)``) and written by ``export``."""
+
     def __init__(self, vertices, faces):
         self.vertices = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
         self.faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+        self.vertex_normals = None
+        self.vertex_colors = None
 
     def export(self, path):
-        """Binary little-endian PLY (what trimesh writes for a ``.ply`` path)."""
+        """Binary little-endian PLY (what trimesh writes for a ``.ply`` path); with attributes set, the vertex element
+        also carries ``float nx ny nz`` and / or ``uchar red green blue``."""
         v, f = self.vertices, self.faces
+        props, fields = "property float x\nproperty float y\nproperty float z\n", [("p", "<f4", 3)]
+        if self.vertex_normals is not None:
+            props += "property float nx\nproperty float ny\nproperty float nz\n"
+            fields.append(("n", "<f4", 3))
+        if self.vertex_colors is not None:
+            props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+            fields.append(("c", "u1", 3))
         header = ("ply\nformat binary_little_endian 1.0\n"
-                  f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+                  f"element vertex {len(v)}\n{props}"
                   f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
+        vrec = np.empty(len(v), dtype=fields)          # (a packed record: x y z [nx ny nz] [red green blue])
+        vrec["p"] = v.astype("<f4")
+        for key, name, attr, dt in (("n", "vertex_normals", self.vertex_normals, np.float32),
+                                    ("c", "vertex_colors", self.vertex_colors, np.uint8)):
+            if attr is not None:
+                a = np.asarray(attr)
+                if a.shape != (len(v), 3):
+                    raise ValueError(f"TriMesh.export: {name} must be [{len(v)}, 3] (got {list(a.shape)})")
+                vrec[key] = a.astype(dt)
         rec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", 3)])
         rec["n"] = 3
         rec["i"] = f.astype(np.int32)
         with open(path, "wb") as fh:
             fh.write(header.encode("ascii"))
-            fh.write(v.astype("<f4").tobytes())
+            fh.write(vrec.tobytes())
             fh.write(rec.tobytes())
         return path
 
     def merge_vertices(self):
         """Weld coincident vertices (trimesh's ``merge_vertices``): meshlize shares vertices inside a voxel only,
-        neighbouring voxels repeat the vertices on their common lattice edges."""
+        neighbouring voxels repeat the vertices on their common lattice edges.  A mesh that carries vertex attributes
+        is refused: they are computed on the final mesh and are not carried through welding."""
+        if self.vertex_normals is not None or self.vertex_colors is not None:
+            raise ValueError("TriMesh.merge_vertices: the mesh carries vertex_normals / vertex_colors; weld first and "
+                             "compute the attributes on the final mesh")
         u, inv = np.unique(np.ascontiguousarray(self.vertices).view([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]).reshape(-1),
                            return_inverse=True)
         self.vertices = u.view(np.float32).reshape(-1, 3).copy()
@@ -468,6 +495,250 @@ def remove_small_components_gpu(mesh, min_area=0.0, min_faces=0, keep_largest=No
     return TriMesh(*to_host(vs, fs))
 
 
+# ---- vertex normals and colours (include/bnv_fusion.h, "Mesh normals and colours"; csrc/meshcolor.hip) --------------
+_NORMAL_SCALE = 2.0 ** 48        # cross products are summed as integers in units of 2^-48
+COLOR_MAX_FRAMES = 8             # BNV_MESH_COLOR_MAX_FRAMES
+DEFAULT_FILL = (128, 128, 128)
+
+
+def vertex_normals(mesh):
+    """Area-weighted vertex normals of a TriMesh on the host -> float32 [V, 3], unit length, or (0, 0, 0) for a vertex
+    no face references, that only degenerate faces touch, or whose faces cancel.  Per face the cross product
+    (b - a) x (c - a) in float64 from the float32 coordinates (the operation order of ``_face_area_units``), quantised
+    to rint(x * 2^48) and summed per vertex as int64: the order of the faces does not matter.  The same bits as
+    ``vertex_normals_tensors``.  Raises ValueError on a non-finite vertex, a face index outside [0, V) or a total area
+    of 2^12 square units or more."""
+    v = np.asarray(mesh.vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
+    V, T = len(v), len(f)
+    if not np.isfinite(v).all():
+        raise ValueError("vertex_normals: vertices must be finite")
+    if T and (V == 0 or f.min() < 0 or f.max() >= V):
+        raise ValueError(f"vertex_normals: a face indexes a vertex outside [0, {V})")
+    out = np.zeros((V, 3), dtype=np.float32)
+    if T == 0:
+        return out
+    try:
+        _face_area_units(v, f)
+    except ValueError:
+        raise ValueError("vertex_normals: the mesh's total area reaches 2^12 square units") from None
+    p = v.astype(np.float64)
+    a, b, c = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
+    e1, e2 = b - a, c - a
+    cross = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                      e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], axis=1)
+    q = np.rint(cross * _NORMAL_SCALE).astype(np.int64)
+    sums = np.zeros((V, 3), dtype=np.int64)
+    for k in range(3):
+        np.add.at(sums, f[:, k], q)
+    some = (sums != 0).any(axis=1)
+    s = sums[some].astype(np.float64)
+    length = np.sqrt((s[:, 0] * s[:, 0] + s[:, 1] * s[:, 1]) + s[:, 2] * s[:, 2])
+    out[some] = (s / length[:, None]).astype(np.float32)
+    return out
+
+
+def vertex_normals_tensors(vertices, faces):
+    """``vertex_normals`` on the device: vertices [V, 3] float32 and faces [T, 3] int64 on the GPU -> normals [V, 3]
+    float32 on the same device, bit for bit what the host function returns.  One host read: the status word, -1 when
+    the device's input checks refuse the mesh (a second read then finds which check to name).  Raises ValueError like
+    connected_components_tensors."""
+    who = "vertex_normals_tensors"
+    vertices, faces, V, T = _check_mesh_tensors(who, vertices, faces, "vertex_normals")
+    dev = vertices.device
+    if V == 0:
+        if T:
+            raise ValueError(f"{who}: a face indexes a vertex outside [0, 0)")
+        return torch.zeros((0, 3), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    need = C.c_int64()
+    _lib.check(lib.bnv_mesh_normals_workspace_bytes(V, C.byref(need)), "bnv_mesh_normals_workspace_bytes")
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
+        out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.bnv_mesh_vertex_normals(_lib.ptr(vertices), V, _lib.ptr(faces), T, _lib.ptr(ws),
+                                               int(need.value), _lib.ptr(out), _lib.ptr(status), _lib.stream_ptr()),
+                   "bnv_mesh_vertex_normals")
+        refused = int(status.item()) < 0           # the one host read of the result
+    if refused:
+        raise _refused_component_input(who, vertices, faces, V, T)
+    return out
+
+
+def _host_matrix(x, shape, what):
+    m = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    m = np.asarray(m, dtype=np.float64)
+    if m.size != shape[0] * shape[1]:
+        raise ValueError(f"{what} must be {shape[0]}x{shape[1]} (got {list(m.shape)})")
+    return m.reshape(shape)
+
+
+def world_to_camera(T_wc):
+    """The world-to-camera matrix of a camera-to-world pose, inverted in float64 on the host -> float64 [4, 4]: what
+    ``VertexColorer`` hands to bnv_mesh_color_accumulate (and tests/mesh_color_restatement.py restates with)."""
+    return np.linalg.inv(_host_matrix(T_wc, (4, 4), "T_wc"))
+
+
+class VertexColorer:
+    """Colours the vertices of a mesh from RGB-D frames on the device (csrc/meshcolor.hip; include/bnv_fusion.h, "Mesh
+    normals and colours"): every vertex is projected into every frame, tested against the frame's own depth image
+    (``depth_tol``: background pixels at a silhouette and frames in which the vertex is hidden contribute nothing),
+    weighted by ``cos / z^2`` of the view (``cos_min`` drops back-facing and grazing views) and sampled bilinearly from
+    the full-resolution colour image.
+
+    ``vertices`` [V, 3] float32 and ``faces`` [T, 3] int64 on the GPU; ``normals`` [V, 3] float32 (default:
+    ``vertex_normals_tensors``).  ``add(frames)`` may be called any number of times -- key frames can be streamed from
+    disk -- and the result does not depend on how the frames are split over calls."""
+
+    def __init__(self, vertices, faces, normals=None, depth_tol=0.02, cos_min=0.2, near=0.0, max_depth=3.0):
+        who = "VertexColorer"
+        vertices, faces, V, _ = _check_mesh_tensors(who, vertices, faces, "vertex_normals")
+        if V == 0:
+            raise ValueError(f"{who}: the mesh has no vertices")
+        self.depth_tol, self.cos_min, self.near, self.max_depth = (float(depth_tol), float(cos_min), float(near),
+                                                                   float(max_depth))
+        if not (np.isfinite(self.depth_tol) and self.depth_tol >= 0.0):
+            raise ValueError(f"{who}: depth_tol must be finite and >= 0 (got {depth_tol})")
+        if not 0.0 <= self.cos_min < 1.0:
+            raise ValueError(f"{who}: cos_min must lie in [0, 1) (got {cos_min})")
+        if not (np.isfinite(self.near) and self.near >= 0.0 and np.isfinite(self.max_depth)
+                and self.max_depth > self.near):
+            raise ValueError(f"{who}: need 0 <= near < max_depth, both finite (got {near}, {max_depth})")
+        if normals is None:
+            normals = vertex_normals_tensors(vertices, faces)
+        elif not (torch.is_tensor(normals) and normals.device == vertices.device and normals.dtype == torch.float32
+                  and tuple(normals.shape) == (V, 3)):
+            raise ValueError(f"{who}: normals must be [{V}, 3] float32 on {vertices.device}")
+        self.vertices, self.faces, self.normals = vertices, faces, normals.detach().contiguous()
+        self.device, self.n_vertices, self.n_frames = vertices.device, V, 0
+        self._lib = _lib.load()
+        need = C.c_int64()
+        _lib.check(self._lib.bnv_mesh_color_workspace_bytes(V, C.byref(need)), "bnv_mesh_color_workspace_bytes")
+        self._ws_bytes = int(need.value)
+        with torch.cuda.device(self.device):
+            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+            _lib.check(self._lib.bnv_mesh_color_begin(_lib.ptr(self._ws), self._ws_bytes, V, _lib.stream_ptr()),
+                       "bnv_mesh_color_begin")
+
+    def _image(self, x, what):
+        if torch.is_tensor(x):
+            return x.detach().to(self.device).contiguous(), what
+        x = np.ascontiguousarray(x)
+        if x.dtype == np.uint16:                       # (uploaded as int32: from_numpy takes no uint16 everywhere)
+            return torch.from_numpy(x.astype(np.int32)).to(self.device).to(torch.uint16), what
+        return torch.from_numpy(x).to(self.device), what
+
+    def _frame(self, frame):
+        """A frame dict -> (bnv_mesh_color_frame_t, the tensors it points into)."""
+        who = f"VertexColorer.add: frame {frame.get('frame_id')!r}"
+        if frame.get("rgb") is None:
+            raise ValueError(f"{who} has no 'rgb'")
+        depth, _ = self._image(frame["depth"], "depth")
+        if depth.dtype in (torch.uint16, torch.int16):
+            dtype = 0
+        elif depth.dtype == torch.float32:
+            dtype = 1
+        else:
+            raise ValueError(f"{who}: depth must be uint16 millimetres or float32 metres (got {depth.dtype})")
+        if depth.dim() < 2 or depth.numel() != depth.shape[-2] * depth.shape[-1] or depth.numel() == 0:
+            raise ValueError(f"{who}: depth must be one [H, W] image (got {list(depth.shape)})")
+        H, W = int(depth.shape[-2]), int(depth.shape[-1])
+        rgb, _ = self._image(frame["rgb"], "rgb")
+        if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3 or rgb.numel() == 0:
+            raise ValueError(f"{who}: rgb must be uint8 [H, W, 3] (got {rgb.dtype} {list(rgb.shape)})")
+        Hc, Wc = int(rgb.shape[0]), int(rgb.shape[1])
+        K = _host_matrix(frame["intr_mat"], (3, 3), "intr_mat")
+        if frame.get("rgb_intr_mat") is not None:
+            Kc = _host_matrix(frame["rgb_intr_mat"], (3, 3), "rgb_intr_mat")
+        elif (Hc, Wc) == (H, W):
+            Kc = K
+        else:
+            raise ValueError(f"{who}: rgb is {Hc}x{Wc}, depth {H}x{W}: a colour image of its own size needs "
+                             "'rgb_intr_mat'")
+        T_wc = _host_matrix(frame["T_wc"], (4, 4), "T_wc")
+        T_cw = world_to_camera(T_wc)
+        keep = [depth, rgb]
+        conf_ptr, level = None, 0
+        if frame.get("conf") is not None:
+            conf, _ = self._image(frame["conf"], "conf")
+            if conf.dtype != torch.uint8 or conf.numel() != H * W:
+                raise ValueError(f"{who}: conf must be uint8 [{H}, {W}] (got {conf.dtype} {list(conf.shape)})")
+            keep.append(conf)
+            conf_ptr, level = conf.data_ptr(), int(frame.get("conf_level", 0))
+        f = _lib.MeshColorFrame()
+        f.depth, f.conf, f.rgb = depth.data_ptr(), conf_ptr, rgb.data_ptr()
+        f.depth_dtype, f.conf_level = dtype, level
+        f.height, f.width, f.color_height, f.color_width = H, W, Hc, Wc
+        f.K[:] = [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
+        f.K_color[:] = [Kc[0, 0], Kc[1, 1], Kc[0, 2], Kc[1, 2]]
+        f.T_cw[:] = T_cw[:3].reshape(-1).tolist()
+        f.center[:] = T_wc[:3, 3].tolist()
+        return f, keep
+
+    def _launch(self, batch):
+        frames = (_lib.MeshColorFrame * len(batch))(*[f for f, _ in batch])
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.bnv_mesh_color_accumulate(
+                _lib.ptr(self.vertices), _lib.ptr(self.normals), self.n_vertices, frames, len(batch), self.depth_tol,
+                self.cos_min, self.near, self.max_depth, _lib.ptr(self._ws), self._ws_bytes, _lib.stream_ptr()),
+                "bnv_mesh_color_accumulate")
+        self.n_frames += len(batch)
+
+    def add(self, frames):
+        """Adds frames (an iterable of the dicts ``NeuralMap`` takes -- ``depth`` uint16 millimetres or float32 metres,
+        ``intr_mat``, ``T_wc`` -- plus ``rgb`` uint8 [Hc, Wc, 3]; optional ``rgb_intr_mat`` for a colour image of its
+        own size, ``conf`` / ``conf_level``), ``COLOR_MAX_FRAMES`` per launch.  A frame without ``rgb`` raises
+        ValueError naming its ``frame_id``.  -> self"""
+        if isinstance(frames, dict):
+            frames = [frames]
+        batch = []
+        for frame in frames:
+            batch.append(self._frame(frame))
+            if len(batch) == COLOR_MAX_FRAMES:
+                self._launch(batch)
+                batch = []
+        if batch:
+            self._launch(batch)
+        return self
+
+    def result(self, fill=DEFAULT_FILL, return_weights=False):
+        """-> (colors uint8 [V, 3], observed bool [V][, sum_w float64 [V], count int32 [V]]) on the device: the weighted
+        mean of the samples, rounded half to even; vertices no frame contributed to get ``fill``."""
+        fill = [int(c) for c in fill]
+        if len(fill) != 3 or not all(0 <= c <= 255 for c in fill):
+            raise ValueError(f"VertexColorer.result: fill must be three values in [0, 255] (got {fill})")
+        V = self.n_vertices
+        with torch.cuda.device(self.device):
+            colors = torch.empty((V, 3), dtype=torch.uint8, device=self.device)
+            observed = torch.empty(V, dtype=torch.uint8, device=self.device)
+            sum_w = torch.empty(V, dtype=torch.float64, device=self.device) if return_weights else None
+            count = torch.empty(V, dtype=torch.int32, device=self.device) if return_weights else None
+            _lib.check(self._lib.bnv_mesh_color_resolve(_lib.ptr(self._ws), self._ws_bytes, V, (C.c_uint8 * 3)(*fill),
+                                                        _lib.ptr(colors), _lib.ptr(observed), _lib.ptr(sum_w),
+                                                        _lib.ptr(count), _lib.stream_ptr()), "bnv_mesh_color_resolve")
+        observed = observed.bool()
+        return (colors, observed, sum_w, count) if return_weights else (colors, observed)
+
+
+def color_vertices(mesh_or_tensors, frames, fill=DEFAULT_FILL, return_weights=False, device="cuda:0", **kw):
+    """``VertexColorer`` in one call.  ``mesh_or_tensors``: (vertices, faces) device tensors -> what
+    ``VertexColorer.result`` returns; or a TriMesh (uploaded to ``device``) -> the same TriMesh with ``vertex_normals``
+    and ``vertex_colors`` set, and ``(mesh, observed[, sum_w, count])`` as host arrays.  ``kw``: ``normals``,
+    ``depth_tol``, ``cos_min``, ``near``, ``max_depth``."""
+    if isinstance(mesh_or_tensors, TriMesh):
+        m = mesh_or_tensors
+        v = torch.from_numpy(np.ascontiguousarray(m.vertices, dtype=np.float32)).to(device)
+        f = torch.from_numpy(np.ascontiguousarray(m.faces, dtype=np.int64)).to(device)
+        colorer = VertexColorer(v, f, **kw).add(frames)
+        out = colorer.result(fill, return_weights)
+        host = to_host(colorer.normals, out[0], out[1].to(torch.uint8), *out[2:])
+        m.vertex_normals, m.vertex_colors = host[0], host[1]
+        return (m, host[2].astype(bool)) + tuple(host[3:])
+    vertices, faces = mesh_or_tensors
+    return VertexColorer(vertices, faces, **kw).add(frames).result(fill, return_weights)
+
+
 _PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
                 "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
                 "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
@@ -488,8 +759,8 @@ def _fan(polys):
 
 def load_ply(path):
     """PLY -> TriMesh: ASCII or binary little-endian, as ``TriMesh.export`` and most ground-truth meshes are written.
-    Vertices: ``float`` / ``double`` x, y, z, possibly with further scalar properties (normals, ``uchar`` colours ...),
-    which are read past.  Faces: ``property list uchar|uint8 int|uint|int32|uint32 vertex_indices`` (or
+    Vertices: ``float`` / ``double`` x, y, z, possibly with further scalar properties, which are read past -- except
+    ``nx ny nz`` and ``uchar red green blue``, which become ``vertex_normals`` / ``vertex_colors`` of the result.  Faces: ``property list uchar|uint8 int|uint|int32|uint32 vertex_indices`` (or
     ``vertex_index``); quads and larger polygons are triangulated as fans.  Anything else -- big-endian data, list
     properties on vertices, extra face properties, other elements with data -- fails with a ValueError naming it."""
     with open(path, "rb") as fh:
@@ -523,6 +794,7 @@ def load_ply(path):
     if fmt not in ("ascii", "binary_little_endian"):
         raise ValueError(f"{path}: PLY format {fmt!r} is not supported (ascii and binary_little_endian are)")
     verts, faces = None, np.zeros((0, 3), dtype=np.int64)
+    normals = colors = None
     pos = 0                                           # binary: byte offset into body
     lines = body.decode("ascii").split("\n") if fmt == "ascii" else None
     li = 0                                            # ascii: next line
@@ -537,11 +809,17 @@ def load_ply(path):
                 rows = [ln.split() for ln in lines[li:li + count]]
                 li += count
                 verts = np.array([[float(r[0]), float(r[1]), float(r[2])] for r in rows], dtype=np.float64).reshape(-1, 3)
+                cols = {n: np.array([float(r[k]) for r in rows], dtype=np.float64) for k, n in enumerate(names)}
             else:
                 dt = np.dtype([(n, "<" + _PLY_SCALARS[t]) for n, t in props])
                 rec = np.frombuffer(body, dtype=dt, count=count, offset=pos)
                 pos += dt.itemsize * count
                 verts = np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float64)
+                cols = {n: rec[n] for n in names}
+            if all(n in names for n in ("nx", "ny", "nz")):
+                normals = np.stack([cols["nx"], cols["ny"], cols["nz"]], axis=1).astype(np.float32).reshape(-1, 3)
+            if all(n in names and dict(props)[n] in ("uchar", "uint8") for n in ("red", "green", "blue")):
+                colors = np.stack([cols["red"], cols["green"], cols["blue"]], axis=1).astype(np.uint8).reshape(-1, 3)
         elif name == "face":
             if len(props) != 1 or not isinstance(props[0][1], tuple) or props[0][0] not in ("vertex_indices",
                                                                                              "vertex_index"):
@@ -584,7 +862,9 @@ def load_ply(path):
         raise ValueError(f"{path}: no vertex element")
     if len(faces) and (faces.min() < 0 or faces.max() >= len(verts)):
         raise ValueError(f"{path}: a face indexes a vertex that does not exist")
-    return TriMesh(verts.astype(np.float32), faces)
+    out = TriMesh(verts.astype(np.float32), faces)
+    out.vertex_normals, out.vertex_colors = normals, colors
+    return out
 
 
 def load_obj(path):

@@ -376,12 +376,26 @@ class NeuralMap:
         delta = self.prepare_tsdf_volume() if self.tsdf_vol is not None else self.sdf_delta
         return self.volume.meshlize_sdf(self.pointnet.nerf, delta)
 
-    def extract_mesh(self, path=None, post_process=None, min_component_area=None):
+    def extract_mesh(self, path=None, post_process=None, min_component_area=None, normals=False, color=None,
+                     color_options=None):
         """run_e2e.py:164-167: mesh of the whole volume (TSDF prior included when enabled) -> TriMesh or None.
         ``post_process``: None, or a vertex threshold (run_e2e.py:293 uses voxel_size / 4) -- the mesh is then
         post-processed on the device, the same as mesh.post_process_mesh(extract_mesh(), post_process).
         ``min_component_area``: None, or an area -- connected components of the post-processed mesh below it are
-        removed on the device (mesh.remove_small_components); ValueError without ``post_process``."""
+        removed on the device (mesh.remove_small_components); ValueError without ``post_process``.
+        ``normals``: the mesh carries area-weighted ``vertex_normals``.  ``color``: None; True -- the vertices are
+        coloured from the key frames in ``self.frames`` that carry ``rgb`` (ValueError when none does); or an iterable
+        of frame dicts with ``rgb`` (mesh.VertexColorer; ``color_options``: its keyword arguments, ``max_depth``
+        defaults to the map's).  ``color`` implies ``normals``.  Both are computed on the device on the final mesh,
+        whose vertices and faces are byte for byte those of the call without them."""
+        if color is True:
+            color = [f for f in self.frames if f.get("rgb") is not None]
+            if not color:
+                raise ValueError("extract_mesh: color=True, but no key frame in self.frames carries 'rgb'")
+        elif color is False:
+            color = None
+        if color is not None:
+            color_options = dict({"max_depth": self.max_depth}, **(color_options or {}))
         if min_component_area is not None and post_process is None:
             raise ValueError("extract_mesh: min_component_area needs post_process (a vertex threshold): the unwelded "
                              "per-voxel mesh has one component per voxel patch")
@@ -389,7 +403,8 @@ class NeuralMap:
         delta = self.prepare_tsdf_volume() if self.tsdf_vol is not None else self.sdf_delta
         self.volume.to_tensor()
         out = self.volume.meshlize(self.pointnet.nerf, delta, path, post_process=post_process,
-                                   min_component_area=min_component_area)
+                                   min_component_area=min_component_area, normals=normals, color=color,
+                                   color_options=color_options)
         return None if out is None else out[1]
 
     def render(self, T_wc, intr_mat, H, W, normals=True):

@@ -168,13 +168,40 @@ def to_u16(depth, rounding="trunc"):
     return mm.to(torch.int32).to(torch.uint16)
 
 
+def render_color(depth, K, T_wc, color="procedural"):
+    """The colour image that goes with a clean depth image (fp32 [H, W] metres on the GPU, 0 = nothing): every pixel's
+    hit point, back-projected in float64 -- x = (c - cx) / fx d, y = (r - cy) / fy d, z = d (integer pixel coordinates
+    are pixel centres), then ((R0 x + R1 y) + R2 z) + t per world axis -- and coloured by ``color``: "procedural"
+    (``synthetic.surface_color``) or a callable of world points float64 [H, W, 3] -> [H, W, 3] in [0, 255].  -> uint8
+    [H, W, 3] (rounded half to even), 0 where nothing is hit.  Torch elementwise code: it makes a test asset."""
+    from . import synthetic
+    fn = synthetic.surface_color if isinstance(color, str) and color == "procedural" else color
+    if not callable(fn):
+        raise ValueError(f"color {color!r}: None, 'procedural' or a callable")
+    d = evaluate._on_gpu(depth, "depth", torch.float64)
+    H, W = int(d.shape[0]), int(d.shape[1])
+    K, T = np.asarray(K, dtype=np.float64), np.asarray(T_wc, dtype=np.float64)
+    c = torch.arange(W, dtype=torch.float64, device=d.device)[None, :]
+    r = torch.arange(H, dtype=torch.float64, device=d.device)[:, None]
+    x = (c - float(K[0, 2])) / float(K[0, 0]) * d
+    y = (r - float(K[1, 2])) / float(K[1, 1]) * d
+    world = torch.stack([((x * float(T[a, 0]) + y * float(T[a, 1])) + d * float(T[a, 2])) + float(T[a, 3])
+                         for a in range(3)], dim=-1)
+    rgb = torch.round(torch.as_tensor(fn(world), dtype=torch.float64, device=d.device)).clamp(0.0, 255.0)
+    return torch.where((d > 0)[..., None], rgb, torch.zeros_like(rgb)).to(torch.uint8)
+
+
 def scan_frames(scanner, poses, K, H, W, noise=None, seed=0, max_depth=math.inf, near=0.0, table=None,
-                rounding="trunc"):
+                rounding="trunc", color=None):
     """The frame dicts ``NeuralMap`` takes (``sequence.sweep_frames``' keys: ``frame_id``, ``depth`` uint16 millimetres
     on the scanner's device, ``intr_mat``, ``T_wc``) of the mesh seen from ``poses`` ([n, 4, 4]).  noise None: the
-    clean depth through ``to_u16(rounding=rounding)``; "kinect": ``simulate_sensor`` with ``seed`` and the frame's number."""
+    clean depth through ``to_u16(rounding=rounding)``; "kinect": ``simulate_sensor`` with ``seed`` and the frame's number.
+    ``color``: None (the keys above only), or "procedural" / a callable -- every frame then also carries ``rgb`` uint8
+    [H, W, 3] on the scanner's device (``render_color`` of the CLEAN depth)."""
     if noise not in (None, "kinect"):
         raise ValueError(f"noise {noise!r}: None or 'kinect'")
+    if color is not None and not (callable(color) or (isinstance(color, str) and color == "procedural")):
+        raise ValueError(f"color {color!r}: None, 'procedural' or a callable")
     poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
     K = np.asarray(K, dtype=np.float64)
     for s in range(0, len(poses), MAX_POSES):
@@ -182,7 +209,10 @@ def scan_frames(scanner, poses, K, H, W, noise=None, seed=0, max_depth=math.inf,
         for j in range(depth.shape[0]):
             i = s + j
             d = simulate_sensor(depth[j], seed, i, table=table) if noise == "kinect" else to_u16(depth[j], rounding)
-            yield {"frame_id": i, "depth": d, "intr_mat": K.copy(), "T_wc": poses[i].copy()}
+            frame = {"frame_id": i, "depth": d, "intr_mat": K.copy(), "T_wc": poses[i].copy()}
+            if color is not None:
+                frame["rgb"] = render_color(depth[j], K, poses[i], color)
+            yield frame
 
 
 def drift_poses(poses, sigma_t, sigma_r, seed=0):

@@ -377,3 +377,41 @@ def local_patches(n, M, seed=0, noise=0.0, n_pts=64, near_fraction=0.5, near_sig
         gt[i] = shape_sdf(s, q.astype(np.float64))
         shapes.append(s)
     return {"input_pts": inp, "training_pts": tp, "gt": gt, "shapes": shapes}
+
+
+# ---- a colour field to test mesh colouring with ---------------------------------------------------------------------
+# per channel two triangle waves: (axis, 1 / period in metres, phase in periods).  Periods of a few decimetres, other
+# periods and axes in every channel: a channel swap or an axis mix-up changes the field everywhere.
+COLOR_WAVES = (((0, 1.0 / 0.30, 0.00), (1, 1.0 / 0.50, 0.25)),
+               ((1, 1.0 / 0.40, 0.50), (2, 1.0 / 0.70, 0.00)),
+               ((2, 1.0 / 0.35, 0.25), (0, 1.0 / 0.60, 0.50)))
+
+
+def surface_color(points):
+    """A fixed procedural colour field of world position: ``points`` [..., 3] float64 (a numpy array or a torch tensor)
+    -> [..., 3] float64 in [0, 255] (red, green, blue; not rounded).  Each channel is the mean of two triangle waves
+    tri(s) = |2 (s - floor(s + 0.5))| of s = x[axis] / period + phase, times 255: floor, multiply and add only, one
+    rounding per operation and no transcendental function, so numpy and torch give the same bits."""
+    is_np = isinstance(points, np.ndarray)
+    if is_np:
+        points = np.asarray(points, dtype=np.float64)
+    channels = []
+    for waves in COLOR_WAVES:
+        acc = None
+        for axis, inv_period, phase in waves:
+            t = points[..., axis] * inv_period
+            t = t + phase
+            u = t + 0.5
+            u = np.floor(u) if is_np else u.floor()
+            d = t - u
+            d = d * 2.0
+            d = np.abs(d) if is_np else d.abs()
+            acc = d if acc is None else acc + d
+        acc = acc * 127.5
+        channels.append(acc)
+    return np.stack(channels, axis=-1) if is_np else _torch_stack(channels)
+
+
+def _torch_stack(channels):
+    import torch
+    return torch.stack(channels, dim=-1)

@@ -97,7 +97,13 @@ def main():
                     help="smooth every depth image on the GPU before fusion, tracking and optimisation "
                          "(frontend.DepthFilter: edge-preserving, range width SIGMA_DEPTH * z^2 metres).  Bare: radius 3 "
                          "and two disparity steps of the Kinect model at 1 m; or give both values.  Off by default")
+    ap.add_argument("--color", action="store_true",
+                    help="colour the final mesh from the sequence's colour images and write its vertex normals "
+                         "(mesh.color_vertices; needs Pillow to decode them).  The synthetic sequences have none")
     args = ap.parse_args()
+    if args.color and (args.synthetic or args.sweep or args.synthetic_arkit):
+        sys.exit("--color: the sequences --synthetic, --sweep and --synthetic-arkit write hold depth only, there is no "
+                 "colour image to take the colours from (a grey mesh is not written instead)")
     depth_filter = None
     if args.depth_filter is not None:
         from bnv_fusion_amd import frontend
@@ -135,9 +141,10 @@ def main():
                                      cap["poses"], cap["dimensions"], center=cap["center"])
     if args.arkit:
         data = datasets.ARKitDataset(args.data_dir, args.scan_id, confidence_level=args.confidence_level,
-                                     skip_images=args.skip_images, device=dev)
+                                     skip_images=args.skip_images, device=dev, load_rgb=args.color)
     else:
-        data = datasets.FusionInferenceDataset(args.data_dir, args.scan_id, skip_images=args.skip_images, device=dev)
+        data = datasets.FusionInferenceDataset(args.data_dir, args.scan_id, skip_images=args.skip_images, device=dev,
+                                               load_rgb=args.color)
     model = bnv.load_pretrained(device=dev, voxel_size=args.voxel_size, tiny_cuda=args.tiny_cuda, path=args.weights)
     nm = bnv.NeuralMap(data.dimensions, args.voxel_size, model, capacity=1 << 20, device=dev, tsdf=True,
                        max_depth=data.max_depth, depth_filter=depth_filter)
@@ -226,6 +233,10 @@ def main():
         print(f"components: {len(areas)}, the largest holds {share} of the area; below "
               f"{args.min_component_area:g} m^2: {int(gone.sum())} components, {n_before - len(mesh.faces)} faces, "
               f"{areas[gone].sum():.6f} m^2 removed")
+    if mesh is not None and args.color:
+        from bnv_fusion_amd.mesh import color_vertices
+        _, observed = color_vertices(mesh, nm.frames, max_depth=max_depth, device=dev)
+        print(f"colour: {observed.mean():.2%} of {len(mesh.vertices)} vertices observed in {len(nm.frames)} frames")
     if mesh is not None:
         mesh.export(os.path.join(args.out, "final.ply"))
     nm.save(args.out, scan_id=args.scan_id.split("/")[-1])

@@ -1264,6 +1264,86 @@ int bnv_depth_filter(const void* depth, int depth_dtype, int H, int W, double ma
                      double sigma_depth, double range_cut, const uint8_t* conf, int conf_level, float* out,
                      bnv_stream_t stream);
 
+/* ---- Mesh normals and colours (bnv_fusion_amd/csrc/meshcolor.hip; bnv_fusion_amd/mesh.py: vertex_normals_tensors,
+ * VertexColorer): the appearance of an extracted mesh -- area-weighted vertex normals, and per-vertex colours blended
+ * from the RGB frames at full image resolution with a depth test against each frame's own depth image.  The reference
+ * has no such stage (its only colour is the folded volume of TSDFVolume at the TSDF's voxel size);
+ * tests/mesh_color_restatement.py restates what follows in numpy.  Every operation is one IEEE float64 rounding in the
+ * order written (no contraction); division and sqrt are correctly rounded; rint is half to even.
+ *
+ * Normals.  vertices f32 [V, 3], faces i64 [T, 3], 1 <= V < 2^31 - 1, 0 <= T < 2^31 - 1.  Per face from the float32
+ * coordinates: e1 = b - a, e2 = c - a; cx = e1y*e2z - e1z*e2y, cy = e1z*e2x - e1x*e2z, cz = e1x*e2y - e1y*e2x (the
+ * area-weighted normal); q = (rint(cx 2^48), rint(cy 2^48), rint(cz 2^48)) as int64, added to the int64 sums of the
+ * face's three corners with integer atomics: any order of the faces and any schedule gives the same sums.  Per vertex:
+ * s = the three sums converted to float64 (to nearest even); a zero sum (an unreferenced vertex, degenerate faces only,
+ * faces that cancel) gives (0, 0, 0); else len = sqrt((sx sx + sy sy) + sz sz), n = (float)(s / len).
+ * The input is refused (device int32 *status = -1, else 0; normals_out is then unspecified) when a vertex is
+ * non-finite, a face index is outside [0, V), or the mesh's total area reaches 2^12 square units (per face
+ * area = 0.5 sqrt((cx cx + cy cy) + cz cz) must stay below 2^12 and the integer sum of rint(area 2^50) below 2^62,
+ * the rule of bnv_mesh_components): |2 area 2^48| then stays inside int64.  Workspace:
+ * bnv_mesh_normals_workspace_bytes (24 B per vertex + a header).  No allocation, synchronisation or host read.
+ *
+ * Colours.  The workspace (bnv_mesh_color_workspace_bytes) holds per vertex the float64 sums sum_r, sum_g, sum_b,
+ * sum_w ([V, 4] at offset 0) and an int32 count of contributing frames ([V] at offset align256(32 V));
+ * bnv_mesh_color_begin zeroes it.  bnv_mesh_color_accumulate adds 1 <= n_frames <= BNV_MESH_COLOR_MAX_FRAMES frames
+ * in one launch.  One thread owns one vertex and walks the frames in the order given, so every vertex's additions
+ * happen in frame order however the frames are split over launches: the result is bit-identical for any batching.
+ * normals f32 [V, 3] (bnv_mesh_vertex_normals' output or the caller's own, unit length or zero).
+ * A frame (bnv_mesh_color_frame_t, host memory; the images are device memory and only read): depth [height, width],
+ * depth_dtype 0 = uint16 millimetres (d = (double)mm / 1000.0) or 1 = float32 metres; conf uint8 [height, width] or
+ * NULL with conf_level as for bnv_depth_to_points_gated (a pixel is kept when conf >= conf_level; a level without a
+ * map is refused); rgb uint8 [color_height, color_width, 3]; K = (fx, fy, cx, cy) of the depth image and K_color of
+ * the colour image (the same pose); T_cw float64 [12]: rows 0..2 of the WORLD-TO-CAMERA matrix, inverted by the caller
+ * in float64; center: the camera centre in the world (the translation of T_wc).  Integer pixel coordinates are pixel
+ * centres, the front end's convention.  Per vertex x (float32 as float64) with normal n and per frame:
+ *   1. p_a = ((T[a][0] x0 + T[a][1] x1) + T[a][2] x2) + T[a][3];  skip unless near < p2 < max_depth.
+ *   2. u = (fx p0) / p2 + cx,  v = (fy p1) / p2 + cy;  skip unless 0 <= u <= width - 1 and 0 <= v <= height - 1.
+ *      x0 = floor(u), x1 = min(x0 + 1, width - 1), fu = u - x0; y0, y1, fv likewise.
+ *   3. Bilinear weights of (y0, x0), (y0, x1), (y1, x0), (y1, x1): (1 - fu)(1 - fv), fu (1 - fv), (1 - fu) fv, fu fv.
+ *      A neighbour passes when its depth d is finite, 0 < d < max_depth, its confidence passes the gate and
+ *      |d - p2| <= depth_tol; the weight of one that does not is set to 0.  wsum = ((w0 + w1) + w2) + w3;  skip unless
+ *      wsum > 0.  Background pixels at a silhouette are dropped, not blended in, and a vertex behind nearer geometry
+ *      takes nothing from the frame.
+ *   4. d = center - x, c = ((n0 d0 + n1 d1) + n2 d2) / sqrt((d0 d0 + d1 d1) + d2 d2);  skip unless c > cos_min;  a
+ *      vertex whose normal is (0, 0, 0) takes part in no frame.  w = c / (p2 p2): proportional to the image area the
+ *      surface element covers.
+ *   5. When the colour image has the depth image's size and K_color == K: the corner weights are w_i / wsum at the
+ *      same four pixels.  Otherwise u, v and the corners are recomputed with K_color and the colour image's size (skip
+ *      when out of bounds) and the weights are the plain bilinear ones.  Per channel
+ *      col = ((w0 c0 + w1 c1) + w2 c2) + w3 c3;  sum_rgb += w col,  sum_w += w,  count += 1.
+ * bnv_mesh_color_resolve: colors_out uint8 [V, 3] = rint(sum / sum_w) clamped to [0, 255] where count > 0, else
+ * fill[3]; observed_out uint8 [V] = count > 0; sum_w_out f64 [V] and count_out i32 [V] when not NULL.
+ * Null pointers (conf, sum_w_out and count_out excepted), V <= 0, n_frames outside 1..BNV_MESH_COLOR_MAX_FRAMES, an
+ * image size <= 0 or > 32768, depth_dtype other than 0 / 1, a non-finite K, K_color, T_cw or center, depth_tol
+ * negative or non-finite, cos_min outside [0, 1), near negative or non-finite and max_depth not finite or <= near are
+ * BNV_ERR_INVALID_ARGUMENT before any HIP call; a workspace below the size is BNV_ERR_WORKSPACE_TOO_SMALL.  Each
+ * entry is a fixed sequence of launches on stream: no allocation, synchronisation or host read. */
+#define BNV_MESH_COLOR_MAX_FRAMES 8
+typedef struct {
+  const void* depth;
+  const uint8_t* conf;
+  const uint8_t* rgb;
+  int32_t depth_dtype, conf_level;
+  int32_t height, width, color_height, color_width;
+  double K[4];
+  double K_color[4];
+  double T_cw[12];
+  double center[3];
+} bnv_mesh_color_frame_t;
+int bnv_mesh_normals_workspace_bytes(int64_t n_vertices, int64_t* bytes);
+int bnv_mesh_vertex_normals(const float* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces,
+                            void* workspace, int64_t ws_bytes, float* normals_out, int32_t* status,
+                            bnv_stream_t stream);
+int bnv_mesh_color_workspace_bytes(int64_t n_vertices, int64_t* bytes);
+int bnv_mesh_color_begin(void* workspace, int64_t ws_bytes, int64_t n_vertices, bnv_stream_t stream);
+int bnv_mesh_color_accumulate(const float* vertices, const float* normals, int64_t n_vertices,
+                              const bnv_mesh_color_frame_t* frames_host, int32_t n_frames, double depth_tol,
+                              double cos_min, double near, double max_depth, void* workspace, int64_t ws_bytes,
+                              bnv_stream_t stream);
+int bnv_mesh_color_resolve(const void* workspace, int64_t ws_bytes, int64_t n_vertices, const uint8_t fill[3],
+                           uint8_t* colors_out, uint8_t* observed_out, double* sum_w_out, int32_t* count_out,
+                           bnv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
