@@ -37,6 +37,8 @@ from .mesh import TriMesh, load_ply  # noqa: F401,E402
 from . import tracking  # noqa: F401,E402
 from .tracking import Tracker, icp_align  # noqa: F401,E402
 from .frontend import DepthFilter, filter_depth  # noqa: F401,E402
+from . import plan  # noqa: F401,E402
+from .plan import VolumePlan, VolumePlanner, plan_volume  # noqa: F401,E402
 
 
 MLP_MODE_FP32_EXACT = 0     # v_mfma_f32_32x32x2_f32

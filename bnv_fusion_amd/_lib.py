@@ -48,6 +48,7 @@ SYMBOLS = [
     "bnv_depth_filter",
     "bnv_mesh_normals_workspace_bytes", "bnv_mesh_vertex_normals", "bnv_mesh_color_workspace_bytes",
     "bnv_mesh_color_begin", "bnv_mesh_color_accumulate", "bnv_mesh_color_resolve",
+    "bnv_plan_workspace_bytes", "bnv_plan_workspace_reset", "bnv_plan_extent", "bnv_plan_count",
 ]
 
 
@@ -342,6 +343,13 @@ def load():
         "bnv_mesh_color_accumulate": (C.c_int, [vp, vp, i64, C.POINTER(MeshColorFrame), i32, C.c_double, C.c_double,
                                                 C.c_double, C.c_double, vp, i64, vp]),
         "bnv_mesh_color_resolve": (C.c_int, [vp, i64, i64, C.POINTER(C.c_uint8), vp, vp, vp, vp, vp]),
+        "bnv_plan_workspace_bytes": (sz, [C.c_int, C.c_int, C.POINTER(Grid), C.c_int, i64]),
+        "bnv_plan_workspace_reset": (C.c_int, [vp, sz, C.c_int, C.c_int, C.POINTER(Grid), C.c_int, i64, vp]),
+        "bnv_plan_extent": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.c_double, vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int, vp,
+                                      vp]),
+        "bnv_plan_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.c_double, vp, C.c_int, C.POINTER(Grid), C.c_int, i64, vp, sz, vp, vp]),
     }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it

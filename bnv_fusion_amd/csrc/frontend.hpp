@@ -1,6 +1,6 @@
 // frontend.hpp -- per-pixel arithmetic of the depth front end (depth image -> world point + normal), shared by
-// frontend.hip (compacting kernels behind bnv_depth_to_points) and encode.hip (k_front_mark: front end fused with the
-// voxel marking of the encode).  Reference: src/datasets/fusion_inference_dataset.py:40-90, src/utils/geometry.py:150-171,
+// frontend.hip (compacting kernels behind bnv_depth_to_points), encode.hip (k_front_mark: front end fused with the
+// voxel marking of the encode) and plan.hip (the volume planner: validity and the world point only).  Reference: src/datasets/fusion_inference_dataset.py:40-90, src/utils/geometry.py:150-171,
 // kornia 0.6.2 depth_to_normals as restated at geometry.py:515-527.  float64 in the reference's operation order
 // (compiled with -ffp-contract=off), one rounding to float32 at the end.
 #pragma once
@@ -54,6 +54,18 @@ __device__ __forceinline__ bool pixel_valid(const FrontArgs& a, int y, int x) {
   return depth_at(a, y, x) > 0.0 && conf_ok(a, (int64_t)y * a.W + x);
 }
 
+// World point of pixel (y, x) at depth d (metres, as depth_at returns it): depth2xyz with float32 pixel rays
+// (geometry.py:163-168), float64 products with T_wc in the written order, one rounding to float32.  Written once:
+// front_point and the volume planner (plan.hip) must give the same bits.
+__device__ __forceinline__ void world_point(const FrontArgs& a, int y, int x, double d, float (&p)[3]) {
+  const double ur = (double)__fdiv_rn(__fsub_rn((float)x, a.cxf), a.fxf);
+  const double vr = (double)__fdiv_rn(__fsub_rn((float)y, a.cyf), a.fyf);
+  const double pc[3] = {ur * d, vr * d, d};
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    p[r] = (float)(((a.T[r * 4 + 0] * pc[0] + a.T[r * 4 + 1] * pc[1]) + a.T[r * 4 + 2] * pc[2]) + a.T[r * 4 + 3]);
+}
+
 // World point (out[0..2]) and world normal (out[3..5]) of pixel (y, x), rounded to float32; false if the pixel is
 // invalid (depth 0 or >= max_depth, or confidence below the gate).
 __device__ __forceinline__ bool front_point(const FrontArgs& a, int y, int x, float (&out)[6]) {
@@ -75,12 +87,11 @@ __device__ __forceinline__ bool front_point(const FrontArgs& a, int y, int x, fl
 #pragma unroll
   for (int c = 0; c < 3; ++c) nrm[c] = nrm[c] / den;
   // ---- point: depth2xyz with float32 pixel rays, then T_wc ----
-  const double ur = (double)__fdiv_rn(__fsub_rn((float)x, a.cxf), a.fxf);
-  const double vr = (double)__fdiv_rn(__fsub_rn((float)y, a.cyf), a.fyf);
-  const double pc[3] = {ur * d, vr * d, d};
+  float pw[3];
+  world_point(a, y, x, d, pw);
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    out[r] = (float)(((a.T[r * 4 + 0] * pc[0] + a.T[r * 4 + 1] * pc[1]) + a.T[r * 4 + 2] * pc[2]) + a.T[r * 4 + 3]);
+    out[r] = pw[r];
     out[3 + r] = (float)((a.T[r * 4 + 0] * nrm[0] + a.T[r * 4 + 1] * nrm[1]) + a.T[r * 4 + 2] * nrm[2]);
   }
   return true;

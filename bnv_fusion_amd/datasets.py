@@ -161,15 +161,37 @@ def _scaled_intrinsics(intr, sy, sx):
     return out
 
 
+def _plan_extent(dataset, plan_options):
+    """``volume="plan"``: pass 1 of the volume planner (plan.VolumePlanner) over the dataset's own frames, served
+    unaligned -> its Extent.  ``plan_options``: keyword arguments of VolumePlanner (trim, margin, align_yaw, up, ...)."""
+    from .plan import VolumePlanner
+    planner = VolumePlanner(device=dataset.device, max_depth=dataset.max_depth, **(plan_options or {}))
+    for k in range(len(dataset)):
+        planner.add(dataset[k])
+    return planner.extent()
+
+
+def _volume_mode(volume):
+    if volume not in ("file", "plan"):
+        raise ValueError(f"volume {volume!r}: 'file' or 'plan'")
+    return volume
+
+
 class FusionInferenceDataset:
     """fusion_inference_dataset.py:105-146 for the per-frame path: ``dimensions`` and frames in order.  ``load_rgb``:
     every frame also carries ``rgb`` (uint8 [Hc, Wc, 3] on the host, ``image/<i>.jpg``) for
     mesh.VertexColorer, and ``rgb_intr_mat`` when the colour image is not of the depth image's size (the same view is
-    assumed: the depth intrinsics rescaled)."""
+    assumed: the depth intrinsics rescaled).  ``volume="file"``: ``dimensions`` from ``pose/dimensions.txt``, poses as
+    written (an origin-centred scene).  ``volume="plan"``: the file is not needed; ``dimensions`` and
+    ``axis_align_mat`` are planned from the sequence's own frames (``plan_options``: keyword arguments of
+    plan.VolumePlanner; ``extent``: its result) and every frame's ``T_wc`` is ``axis_align_mat @`` the written pose."""
 
     def __init__(self, data_dir, scan_id, skip_images=1, downsample_scale=1.0, max_depth=3.0, device="cuda:0",
-                 num_images=None, load_rgb=False):
+                 num_images=None, load_rgb=False, volume="file", plan_options=None):
         self.load_rgb = bool(load_rgb)
+        self.volume = _volume_mode(volume)
+        self.axis_align_mat = None      # volume="plan": set below
+        self.extent = None
         # max_depth: cfg.model.ray_tracer.ray_max_dist (fusion_inference_dataset.py:28; 3 m in
         # fusion_pointnet_model.yaml:43).  The frames carry the raw depth image; the cut-off is applied by the
         # kernels (NeuralMap(max_depth=dataset.max_depth)), where the reference's load_depth zeroes the image.
@@ -178,12 +200,17 @@ class FusionInferenceDataset:
         self.device = device
         self.max_depth = max_depth
         self.downsample_scale = float(downsample_scale)
-        with open(os.path.join(self.root, "pose", "dimensions.txt"), "r") as fh:
-            self.dimensions = np.asarray([float(v) for v in fh.read().splitlines()[0].split()])
+        self.dimensions = None
+        if self.volume == "file":
+            with open(os.path.join(self.root, "pose", "dimensions.txt"), "r") as fh:
+                self.dimensions = np.asarray([float(v) for v in fh.read().splitlines()[0].split()])
         n = len([f for f in os.listdir(os.path.join(self.root, "depth")) if f.endswith(".png")])
         if num_images is not None:
             n = min(n, int(num_images))
         self.indices = list(range(0, n, max(int(skip_images), 1)))
+        if self.volume == "plan":
+            self.extent = _plan_extent(self, plan_options)
+            self.dimensions, self.axis_align_mat = self.extent.dimensions, self.extent.axis_align_mat
 
     def __len__(self):
         return len(self.indices)
@@ -203,6 +230,8 @@ class FusionInferenceDataset:
             "intr_mat": intr.astype(np.float64),
             "T_wc": _read_matrix(os.path.join(self.root, "pose", f"T_wc_{i}.txt")).astype(np.float64),
         }
+        if self.axis_align_mat is not None:
+            frame["T_wc"] = self.axis_align_mat @ frame["T_wc"]
         if self.load_rgb:
             frame["rgb"] = read_rgb(os.path.join(self.root, "image", f"{i}.jpg"))
             if frame["rgb"].shape[:2] != depth.shape:
@@ -253,11 +282,17 @@ class ARKitDataset:
     pixels with ``0 < depth < max_depth`` and ``conf >= conf_level`` as points and as training rays; the normals and the
     TSDF side fusion see the range-masked depth, as in the reference.  ``skip_images`` (the reference ignores it for
     this layout) keeps every k-th frame; the default keeps all.  ``load_rgb``: every frame also carries ``rgb``
-    (``frame_<n>.jpg``, uint8 [1440, 1920, 3] on the host) and ``rgb_intr_mat``, the file's own intrinsics."""
+    (``frame_<n>.jpg``, uint8 [1440, 1920, 3] on the host) and ``rgb_intr_mat``, the file's own intrinsics.
+    ``volume="plan"``: ``export.obj`` is not needed; ``dimensions`` and ``axis_align_mat`` are planned from the capture's
+    own confidence-gated frames (``plan_options``: keyword arguments of plan.VolumePlanner, e.g. ``align_yaw=18``;
+    ``extent``: its result)."""
 
     def __init__(self, data_dir, scan_id, confidence_level=2, max_depth=3.0, downsample_scale=1.0,
-                 intr_scale=ARKIT_INTR_SCALE, skip_images=1, device="cuda:0", load_rgb=False):
+                 intr_scale=ARKIT_INTR_SCALE, skip_images=1, device="cuda:0", load_rgb=False, volume="file",
+                 plan_options=None):
         self.load_rgb = bool(load_rgb)
+        self.volume = _volume_mode(volume)
+        self.extent = None
         self.root = os.path.join(data_dir, scan_id)
         self.scan_id = scan_id
         self.device = device
@@ -265,16 +300,22 @@ class ARKitDataset:
         self.max_depth = max_depth
         self.downsample_scale = float(downsample_scale)
         self.intr_scale = float(intr_scale)
-        obj = os.path.join(self.root, "export.obj")
-        if not os.path.exists(obj):
-            raise FileNotFoundError(f"{obj}: missing -- the capture's rough mesh, whose bounds place the volume")
-        v = read_obj_vertices(obj)
-        lo, hi = v.min(axis=0), v.max(axis=0)
-        self.dimensions = hi - lo
         self.axis_align_mat = np.eye(4)
-        self.axis_align_mat[:3, 3] = -(lo + hi) / 2
+        self.dimensions = None
+        if self.volume == "file":
+            obj = os.path.join(self.root, "export.obj")
+            if not os.path.exists(obj):
+                raise FileNotFoundError(f"{obj}: missing -- the capture's rough mesh, whose bounds place the volume "
+                                        "(volume=\"plan\" places it from the frames instead)")
+            v = read_obj_vertices(obj)
+            lo, hi = v.min(axis=0), v.max(axis=0)
+            self.dimensions = hi - lo
+            self.axis_align_mat[:3, 3] = -(lo + hi) / 2
         names = [f.split("_")[1].split(".")[0] for f in os.listdir(self.root) if f.startswith("depth_")]
         self.names = sorted(names, key=int)[:: max(int(skip_images), 1)]
+        if self.volume == "plan":       # (the frames are served with the identity until the plan is there)
+            self.extent = _plan_extent(self, plan_options)
+            self.dimensions, self.axis_align_mat = self.extent.dimensions, self.extent.axis_align_mat
 
     def __len__(self):
         return len(self.names)

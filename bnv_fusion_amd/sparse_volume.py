@@ -43,6 +43,18 @@ def make_grid(n_xyz, bound_min, bound_max, voxel_size, min_pts_in_grid, shard=(0
     return g
 
 
+def track_n_pts_update(avg_n_pts, n_frames, min_pts, max_pts, n_pts):
+    """One step of the per-frame bookkeeping (sparse_volume.py:508-518) -> (avg_n_pts, n_frames, min_pts, max_pts).
+    Written once: SparseVolume.track_n_pts and the volume planner (plan.py) round the running mean the same way."""
+    avg_n_pts = (avg_n_pts * n_frames + n_pts) / (n_frames + 1)
+    return avg_n_pts, n_frames + 1, min(min_pts, n_pts), max(max_pts, n_pts)
+
+
+def n_pts_percentiles(n_pts_list):
+    """The 25 / 50 / 75 % figures of print_statistic (sparse_volume.py:520-523)."""
+    return np.percentile(n_pts_list, [25, 50, 75]) if len(n_pts_list) else [0, 0, 0]
+
+
 def _pow2_at_least(x):
     p = 1
     while p < x:
@@ -104,14 +116,12 @@ class SparseVolume:
     def track_n_pts(self, n_pts):
         n_pts = float(n_pts)
         self.n_pts_list.append(n_pts)
-        self.avg_n_pts = (self.avg_n_pts * self.n_frames + n_pts) / (self.n_frames + 1)
-        self.n_frames += 1
-        self.min_pts = min(self.min_pts, n_pts)
-        self.max_pts = max(self.max_pts, n_pts)
+        self.avg_n_pts, self.n_frames, self.min_pts, self.max_pts = track_n_pts_update(
+            self.avg_n_pts, self.n_frames, self.min_pts, self.max_pts, n_pts)
 
     def print_statistic(self):
         print("===========")
-        p = np.percentile(self.n_pts_list, [25, 50, 75]) if self.n_pts_list else [0, 0, 0]
+        p = n_pts_percentiles(self.n_pts_list)
         self.per_25, self.per_50, self.per_75 = p[0], p[1], p[2]
         print(f"25%: {p[0]}, 50%: {p[1]}, 75%:{p[2]}")
         print(f"mean: {self.avg_n_pts}, min: {self.min_pts}, max:{self.max_pts}")

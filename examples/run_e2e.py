@@ -9,6 +9,7 @@ sequence directory, periodic global optimisation, mesh extraction, final artefac
     python examples/run_e2e.py --sweep 60 --grid 256 --pose-drift 0.005 0.003 --track tsdf --no-optimize --out /tmp/trk
                                                     # drifting odometry, every frame aligned to the map before it is fused
     python examples/run_e2e.py ... --depth-filter                                           # smooth every depth image first
+    python examples/run_e2e.py ... --plan-volume --plan-voxel-sizes 0.01 0.02 0.04         # extent and voxel size from the frames
     python examples/run_e2e.py --sweep 600 --grid 512 --decode-frames --pipelined --no-optimize --out /tmp/sweep
                                                     # a moving-camera room sweep (bnv_fusion_amd/sequence.py), per-frame
                                                     # SDF decode of the touched voxels, two frames in flight
@@ -18,7 +19,9 @@ pose/dimensions.txt}`` (bnv_fusion_amd/datasets.py), the volume extent comes fro
 the reference; checkpoints default to the converted weights shipped with the package.  With ``--arkit`` they are read
 from a *3D Scanner* app export (``depth_<n>.png``, ``conf_<n>.png``, ``frame_<n>.json``, ``export.obj``:
 datasets.ARKitDataset, the reference's ``dataset=fusion_inference_dataset_arkit``); pixels whose depth confidence is
-below ``--confidence-level`` become neither points nor training rays.
+below ``--confidence-level`` become neither points nor training rays.  With ``--plan-volume`` neither
+``dimensions.txt`` nor ``export.obj`` is read: the extent is planned from the frames (bnv_fusion_amd/plan.py), and
+``--plan-voxel-sizes`` also chooses the voxel size among the given candidates.
 """
 import argparse
 import os
@@ -100,7 +103,14 @@ def main():
     ap.add_argument("--color", action="store_true",
                     help="colour the final mesh from the sequence's colour images and write its vertex normals "
                          "(mesh.color_vertices; needs Pillow to decode them).  The synthetic sequences have none")
+    ap.add_argument("--plan-volume", action="store_true",
+                    help="place the volume from the frames themselves (plan.VolumePlanner: bounds of the valid depth "
+                         "points plus a margin) instead of dimensions.txt / export.obj, and print the plan")
+    ap.add_argument("--plan-voxel-sizes", type=float, nargs="+", metavar="V",
+                    help="implies --plan-volume: count the per-frame points per voxel of these candidate sizes and use the "
+                         "smallest with min > 4 and mean >= 8 (the reference README's rule) in place of --voxel-size")
     args = ap.parse_args()
+    args.plan_volume = args.plan_volume or bool(args.plan_voxel_sizes)
     if args.color and (args.synthetic or args.sweep or args.synthetic_arkit):
         sys.exit("--color: the sequences --synthetic, --sweep and --synthetic-arkit write hold depth only, there is no "
                  "colour image to take the colours from (a grey mesh is not written instead)")
@@ -141,10 +151,24 @@ def main():
                                      cap["poses"], cap["dimensions"], center=cap["center"])
     if args.arkit:
         data = datasets.ARKitDataset(args.data_dir, args.scan_id, confidence_level=args.confidence_level,
-                                     skip_images=args.skip_images, device=dev, load_rgb=args.color)
+                                     skip_images=args.skip_images, device=dev, load_rgb=args.color,
+                                     volume="plan" if args.plan_volume else "file")
     else:
         data = datasets.FusionInferenceDataset(args.data_dir, args.scan_id, skip_images=args.skip_images, device=dev,
-                                               load_rgb=args.color)
+                                               load_rgb=args.color, volume="plan" if args.plan_volume else "file")
+    plan = None
+    if args.plan_volume:
+        # the dataset planned its extent and serves aligned frames; the candidates are counted in that frame
+        from bnv_fusion_amd import plan as planning
+        counter = planning.VolumePlanner(device=dev, max_depth=data.max_depth)
+        cands = counter.count(data, args.plan_voxel_sizes or [args.voxel_size], dimensions=data.dimensions,
+                              axis_align_mat=np.eye(4))
+        plan = planning.plan_from(data.extent, cands)
+        print(plan.table())
+        if args.plan_voxel_sizes:
+            if plan.voxel_size is None:
+                sys.exit("--plan-voxel-sizes: no candidate has min > 4 and mean >= 8 points per voxel; add larger sizes")
+            args.voxel_size = plan.voxel_size
     model = bnv.load_pretrained(device=dev, voxel_size=args.voxel_size, tiny_cuda=args.tiny_cuda, path=args.weights)
     nm = bnv.NeuralMap(data.dimensions, args.voxel_size, model, capacity=1 << 20, device=dev, tsdf=True,
                        max_depth=data.max_depth, depth_filter=depth_filter)
@@ -249,6 +273,8 @@ def main():
         from bnv_fusion_amd import evaluate
         from bnv_fusion_amd.mesh import load_ply
         gt = load_ply(args.eval_gt)
+        if plan is not None:        # the ground truth lives in the frames' world: bring it into the planned volume's
+            gt = TriMesh(plan.apply_points(gt.vertices).astype(np.float32), gt.faces)
         if mesh is not None:
             res = evaluate.evaluate_meshes(mesh, gt, generator=torch.Generator(device=dev).manual_seed(0), device=dev)
             print(evaluate.summary_line(res))

@@ -1344,6 +1344,58 @@ int bnv_mesh_color_resolve(const void* workspace, int64_t ws_bytes, int64_t n_ve
                            uint8_t* colors_out, uint8_t* observed_out, double* sum_w_out, int32_t* count_out,
                            bnv_stream_t stream);
 
+/* ---- Volume planning (bnv_fusion_amd/csrc/plan.hip; bnv_fusion_amd/plan.py: VolumePlanner, plan_volume): the extent
+ * of the scene and the per-frame voxel statistics of candidate voxel sizes, from the depth frames themselves and before
+ * anything is fused.  Both passes read a frame exactly as bnv_encode_begin_depth_gated does: depth / depth_dtype /
+ * max_depth / conf / conf_level as for bnv_depth_to_points_gated, a pixel is valid when 0 < z < max_depth and (with a
+ * map) conf >= conf_level, and its world point p is the front end's float32 point (float32 pixel rays, float64
+ * products with T_wc in the written order, one rounding).  Everything is integer counting: any schedule gives the same
+ * numbers; tests/plan_restatement.py restates both passes in numpy.
+ *
+ * Pass 1, bnv_plan_extent.  dirs_host float64 [n_dirs, 3] (host), 1 <= n_dirs <= BNV_PLAN_MAX_DIRS; n_bins a power of
+ * two in [2, 65536]; hist uint64 [n_dirs, n_bins], device memory the caller zeroes once and reads once: the counters
+ * accumulate over calls.  Per valid pixel and direction d:
+ *     t = (d0 (double)p0 + d1 (double)p1) + d2 (double)p2,  q = floor(t / bin_size) limited to [-n_bins, n_bins] (NaN:
+ *     -n_bins),  b = clamp((int64)q + n_bins / 2, 0, n_bins - 1),  hist[d][b] += 1.
+ * Bins 0 and n_bins - 1 are overflow bins.  A workgroup counts its 256 pixels in an LDS window first (one global atomic
+ * per touched bin) unless they span more than 256 bins.
+ *
+ * Pass 2, bnv_plan_count.  T_wc_host is the ALIGNED pose (axis_align_mat @ T_wc, formed by the caller in float64);
+ * grids_host: 1 <= n_sizes <= BNV_PLAN_MAX_SIZES grids as bnv_encode_* take them (the sharding and mode members are
+ * not read), each of fewer than 2^31 voxels.  Per grid: every valid pixel whose point passes the encoder's bounds mask
+ * counts as a point, and each of its 8 corner voxels (floor / ceil per axis of (p - bound_min) / voxel_size; two corners
+ * that name the same voxel both count) as one (point, corner) pair of that voxel.  rows_out int64
+ * [n_sizes, BNV_PLAN_ROW_WORDS], device memory zeroed by the caller, one row per grid for THIS frame:
+ *     [0] points in bounds (nv)   [1] touched voxels (U)   [2] status   [3] 0
+ *     [4 + c], c = 1 .. BNV_PLAN_HIST_CAP - 1: voxels with exactly c pairs;  [4 + BNV_PLAN_HIST_CAP]: with that many or
+ *     more ([4] and the words behind the histogram stay 0).
+ * The encoder's counters of the same frame follow: n_avg_pts = (float)(8 nv) / (float)U, rows written = the histogram's
+ * sum from min_pts_in_grid up.  status bit 0: the hash table went past half load; bit 1: a pair found no free slot (the
+ * row's counts are then short).  With table_slots = 0 every table has the smallest power of two of slots that is at least
+ * 2 min(8 H W, voxels), so neither can happen; table_slots > 0 (a power of two, 64 .. 2^30) forces that size on every
+ * table.  workspace: bnv_plan_workspace_bytes (8 B per slot and 4 B per 256 pixels, per grid; 0 for invalid arguments),
+ * initialised once by bnv_plan_workspace_reset with the same H, W, grids and table_slots; every call leaves the tables
+ * empty for the next frame.
+ * Null pointers (conf excepted), H or W <= 0 or > 32768 or more than 2^24 pixels, depth_dtype other than 0 / 1 / 2, a
+ * max_depth or bin_size that is not positive and finite, non-finite intrinsics, pose or directions, a zero focal
+ * length, a confidence level without a map, n_dirs, n_bins, n_sizes or table_slots out of range and a grid with a
+ * non-positive or non-finite member or 2^31 voxels or more are BNV_ERR_INVALID_ARGUMENT before any HIP call; a
+ * workspace below the size is BNV_ERR_WORKSPACE_TOO_SMALL.  Fixed sequences of launches on stream: no allocation,
+ * synchronisation or host read. */
+#define BNV_PLAN_MAX_DIRS 64
+#define BNV_PLAN_MAX_SIZES 8
+#define BNV_PLAN_ROW_WORDS 72
+#define BNV_PLAN_HIST_CAP 64
+size_t bnv_plan_workspace_bytes(int H, int W, const bnv_grid_t* grids_host, int n_sizes, int64_t table_slots);
+int bnv_plan_workspace_reset(void* workspace, size_t ws_bytes, int H, int W, const bnv_grid_t* grids_host, int n_sizes,
+                             int64_t table_slots, bnv_stream_t stream);
+int bnv_plan_extent(const void* depth, int depth_dtype, int H, int W, const double* intr_host, const double* T_wc_host,
+                    double max_depth, const uint8_t* conf, int conf_level, const double* dirs_host, int n_dirs,
+                    double bin_size, int n_bins, uint64_t* hist, bnv_stream_t stream);
+int bnv_plan_count(const void* depth, int depth_dtype, int H, int W, const double* intr_host, const double* T_wc_host,
+                   double max_depth, const uint8_t* conf, int conf_level, const bnv_grid_t* grids_host, int n_sizes,
+                   int64_t table_slots, void* workspace, size_t ws_bytes, int64_t* rows_out, bnv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
