@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "bnv_common.hpp"
+#include "scan.hpp"
 
 namespace bnv {
 namespace {
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void k_grid_bbox(const float* __restrict__ X, 
 inline int grid_bbox(const float* X, int64_t n, void* head, size_t bytes, hipStream_t s) {
   BNV_HIP_CHECK(hipMemsetAsync(head, 0, bytes, s));
   BNV_HIP_CHECK(hipMemsetAsync(head, 0xff, 3 * sizeof(uint32_t), s));   // min = the largest key
-  const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
+  const unsigned blocks = std::min(blocks_for(n, 256), 2048u);
   hipLaunchKernelGGL(k_grid_bbox, dim3(blocks), dim3(256), 0, s, X, n, (uint32_t*)head);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -100,7 +101,7 @@ __device__ inline double grid_cell_edge(const double L[3], int64_t n_entries, do
   return h;
 }
 
-// exclusive scan of count[0 .. n_bins) -> start (bnv_common.hpp's uint32 block scan + decoupled look-back): one tile of
+// exclusive scan of count[0 .. n_bins) -> start (scan.hpp's block scan + decoupled look-back): one tile of
 // kScanTile bins per workgroup, `state` one look-back word per tile, `epoch` from next_epoch()
 __global__ __launch_bounds__(kScanThreads) void k_grid_scan(const uint32_t* __restrict__ count, int64_t n_bins,
                                                             uint32_t* __restrict__ start, uint64_t* __restrict__ state,

@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "bnv_common.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 
@@ -31,36 +32,23 @@ static inline size_t lattice_ws_layout(int64_t n, int64_t row_capacity, char* ba
   if (n < 1) n = 1;
   int64_t cap = 27 * n;
   if (cap > row_capacity) cap = row_capacity;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off = (off + bytes + 255) / 256 * 256;
-    return p;
-  };
-  // stamp and table first: they persist across calls with the same row_capacity
-  char* st = take(row_capacity * 4);
-  char* tb = take(row_capacity * 27 * 4);
-  char* nm = take(row_capacity * 4);
-  char* os = take(row_capacity * 4);
-  char* nl = take(256);
-  char* nb = take(n * 27 * 4);
-  char* li = take(cap * 4);
   int64_t ecap = 27 * cap;
   if (ecap > 216 * n) ecap = 216 * n;
-  char* en = take(ecap * 4);
-  if (ws) {
-    ws->need_mask = (uint32_t*)nm;
-    ws->origin_stamp = (int32_t*)os;
-    ws->entries = (int32_t*)en;
-    ws->entry_capacity = ecap;
-    ws->stamp = (int32_t*)st;
-    ws->table = (float*)tb;
-    ws->n_list = (int32_t*)nl;
-    ws->nbr_rows = (int32_t*)nb;
-    ws->list = (int32_t*)li;
-    ws->list_capacity = cap;
-  }
-  return off;
+  Carver c(base);
+  LatticeWs t;
+  // stamp and table first: they persist across calls with the same row_capacity
+  t.stamp = c.take<int32_t>(row_capacity);
+  t.table = c.take<float>(row_capacity * 27);
+  t.need_mask = c.take<uint32_t>(row_capacity);
+  t.origin_stamp = c.take<int32_t>(row_capacity);
+  t.n_list = c.take<int32_t>(64);
+  t.nbr_rows = c.take<int32_t>(n * 27);
+  t.list = c.take<int32_t>(cap);
+  t.entries = c.take<int32_t>(ecap);
+  t.list_capacity = cap;
+  t.entry_capacity = ecap;
+  if (ws) *ws = t;
+  return c.bytes();
 }
 
 // grid of a grid-stride kernel: the blocks the work needs, at most `per_cu` per CU

@@ -3,6 +3,7 @@
 // k_decode_pts<PREC>, k_decode_pts_bwd, k_optim_step, k_decode_pts_bwd_t.
 #include "decode_host.hpp"
 #include "sdf_mlp.hpp"
+#include "volume_keys.hpp"
 
 namespace bnv {
 

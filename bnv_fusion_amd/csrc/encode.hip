@@ -15,6 +15,7 @@
 //                     scratch cleanup, the frame's counters                                    (HBM)
 #include "encode.hpp"
 #include "frontend.hpp"
+#include "scan.hpp"
 
 namespace bnv {
 
@@ -444,7 +445,7 @@ static int32_t* pair_list_of(const EncodeWs& ws, const bnv_grid_t& g) {
 // a mark kernel over n points (`in`: its arguments in front of the grid) with the frame's pair and orphan lists
 template <typename K, typename... In>
 static void launch_mark_points(K kernel, int64_t n, const EncodeWs& ws, const bnv_grid_t& g, hipStream_t stream, In... in) {
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in..., g, ws.bytemap,
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(n, 256)), dim3(256), 0, stream, in..., g, ws.bytemap,
                      ws.chunk_flag, ws.valid_blocks, pair_list_of(ws, g), &ws.ctl->n_pairs,
                      g.shard_state ? ws.orphan_list : (int32_t*)nullptr, &ws.ctl->n_orphans);
 }
@@ -648,7 +649,7 @@ int bnv_voxelize_pairs(const float* input_pts, int64_t n_points, const bnv_grid_
                        bnv_stream_t stream) {
   if (!input_pts || !grid_host || n_points < 0 || n_points > (1 << 27)) return BNV_ERR_INVALID_ARGUMENT;
   if (n_points == 0) return BNV_OK;
-  hipLaunchKernelGGL(k_voxelize_pairs, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(k_voxelize_pairs, dim3(blocks_for(n_points, 256)), dim3(256), 0,
                      (hipStream_t)stream, input_pts, (int)n_points, *grid_host, grid_ids, flat_ids, rel_xyz,
                      bound_mask);
   BNV_LAUNCH_CHECK();

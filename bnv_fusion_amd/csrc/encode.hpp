@@ -3,6 +3,8 @@
 // accumulators).
 #pragma once
 #include "bnv_common.hpp"
+#include "shard.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 
@@ -45,7 +47,7 @@ struct EncCtl {
                                // bound of the boundary records that rank will exchange for this frame, known on
                                // every rank (the voxelisation is replicated) before the encoder MLP starts
 };
-static_assert(sizeof(EncCtl) <= 512, "control block");
+static_assert(align256(sizeof(EncCtl)) == 512, "control block");
 
 struct EncodeWs {
   EncCtl* ctl;
@@ -86,29 +88,25 @@ static size_t encode_ws_layout(int64_t max_points, const int32_t n_xyz[3], char*
   const int64_t nb_words = (n_chunks + kRankTile - 1) / kRankTile;
   const int64_t nb_unique = (max_unique + kFinTile - 1) / kFinTile;
   const int64_t n_tiles = nb_words > nb_unique ? nb_words : nb_unique;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off = align256(off + bytes);
-    return p;
-  };
+  const int64_t points = max_points > 0 ? max_points : 1;
+  Carver c(base);
   EncodeWs w;   // (the pieces in the order they lie in the workspace)
-  w.ctl = (EncCtl*)take(512);   // control block first: its offset does not depend on the sizes
-  w.tile_state = (uint64_t*)take(n_tiles * 8);
-  w.valid_blocks = (int32_t*)take(((max_points + 255) / 256 + 1) * 4);
-  w.pair_list = (int32_t*)take((size_t)(max_points > 0 ? max_points : 1) * 8 * 4);
-  w.orphan_list = (int32_t*)take((size_t)(max_points > 0 ? max_points : 1) * 4);
-  w.bytemap = (uint8_t*)take(n_words * 32);
-  w.chunk_flag = (uint8_t*)take(n_chunks);
-  w.bitmap = (uint32_t*)take(n_words * 4);
-  w.word_prefix = (uint32_t*)take(n_words * 4);
-  w.ids = (int32_t*)take(max_unique * 4);
-  w.counts = (int32_t*)take(max_unique * 4);
-  w.acc = (long long*)take(max_unique * 8 * 8);
-  w.defer_list = (int32_t*)take(max_unique * 4);
+  w.ctl = c.take<EncCtl>(1);   // control block first: its offset does not depend on the sizes
+  w.tile_state = c.take<uint64_t>(n_tiles);
+  w.valid_blocks = c.take<int32_t>((max_points + 255) / 256 + 1);
+  w.pair_list = c.take<int32_t>(points * 8);
+  w.orphan_list = c.take<int32_t>(points);
+  w.bytemap = c.take<uint8_t>(n_words * 32);
+  w.chunk_flag = c.take<uint8_t>(n_chunks);
+  w.bitmap = c.take<uint32_t>(n_words);
+  w.word_prefix = c.take<uint32_t>(n_words);
+  w.ids = c.take<int32_t>(max_unique);
+  w.counts = c.take<int32_t>(max_unique);
+  w.acc = c.take<long long>(max_unique * 8);
+  w.defer_list = c.take<int32_t>(max_unique);
   w.n_words = n_words, w.n_chunks = n_chunks, w.max_unique = max_unique, w.n_tiles = n_tiles;
   if (ws) *ws = w;
-  return off;
+  return c.bytes();
 }
 
 // ---- corner k of the point at normalised coordinates (xn, yn, zn): ceil on x / y / z where bit 0 / 1 / 2 of k is set,

@@ -12,6 +12,8 @@
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
 #include "cell_grid.hpp"
+#include "scan.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 
@@ -34,20 +36,13 @@ struct SampleWs {
 };
 
 static size_t sample_ws_layout(int64_t n_faces, char* base, SampleWs* w) {
-  const int64_t tiles = (n_faces + kAreaTile - 1) / kAreaTile;
-  size_t off = 0;
-  const size_t o_prefix = off;
-  off += align256((size_t)n_faces * 8);
-  const size_t o_tiles = off;
-  off += align256((size_t)tiles * 8);
-  const size_t o_status = off;
-  off += align256(sizeof(SampleStatus));
-  if (w) {
-    w->prefix = (double*)(base + o_prefix);
-    w->tile_incl = (uint64_t*)(base + o_tiles);
-    w->status = (SampleStatus*)(base + o_status);
-  }
-  return off;
+  Carver c(base);
+  SampleWs t;
+  t.prefix = c.take<double>(n_faces);
+  t.tile_incl = c.take<uint64_t>((n_faces + kAreaTile - 1) / kAreaTile);
+  t.status = c.take<SampleStatus>(1);
+  if (w) *w = t;
+  return c.bytes();
 }
 
 // fp32 cross product e1 x e2 and its length sqrt((cx*cx + cy*cy) + cz*cz): one rounding per operation
@@ -68,7 +63,7 @@ __device__ __forceinline__ void tri_cross(const float* __restrict__ V, int32_t i
 
 // Face areas (0.5 * |e1 x e2| in fp32; 0 for a face with a bad index or a non-finite area) and their inclusive
 // prefix in float64.  Inside a tile: a fixed tree (per-thread runs, wave shuffles, wave totals in order).  Across
-// tiles: the decoupled look-back pattern of bnv_common.hpp cut down to its immediate predecessor -- a tile waits for
+// tiles: the decoupled look-back pattern of scan.hpp cut down to its immediate predecessor -- a tile waits for
 // the inclusive prefix of tile - 1 and adds its own sum -- because float64 addition is not associative: the prefix
 // of every face is then the same sum in the same order on every run.  Tiles are dispatched in index order, so the
 // predecessor is resident or finished when a tile waits for it.
@@ -102,12 +97,7 @@ __global__ __launch_bounds__(kAreaThreads) void k_face_area_prefix(const float* 
   }
   if (bad) atomicOr(&ws.status->bad_faces, 1u);
   // wave inclusive scan of the per-thread sums (Hillis-Steele: the same tree every run)
-  double incl = acc;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
+  const double incl = wave_inclusive_scan(acc);
   if (lane == 63) s_wave[wave] = incl;
   __syncthreads();
   double wbase = 0.0, tile_sum = 0.0;
@@ -224,46 +214,27 @@ struct NnWs {
 static size_t nn_ws_layout(int64_t n_ref, int64_t n_query, char* base, NnWs* w) {
   const int64_t n_bins = n_ref + 2;
   const int64_t tiles = (n_bins + kScanTile - 1) / kScanTile;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return base + o; };
-  char* p[17];
-  p[0] = take(2 * sizeof(NnParams));
-  p[1] = take((size_t)n_bins * 4);
-  p[2] = take((size_t)n_bins * 4);
-  p[3] = take((size_t)n_bins * 4);
-  p[4] = take((size_t)n_bins * 4);
-  p[5] = take((size_t)n_ref * 4);
-  p[6] = take((size_t)n_ref * 4);
-  p[7] = take((size_t)n_query * 4);
-  p[8] = take((size_t)n_query * 4);
-  p[9] = take((size_t)tiles * 3 * 8);
-  p[10] = take((size_t)n_ref * 16);
-  p[11] = take((size_t)n_query * 16);
-  p[12] = take((size_t)n_bins * 4);
-  p[13] = take((size_t)n_bins * 4);
-  p[14] = take((size_t)n_ref * 4);
-  p[15] = take((size_t)n_ref * 4);
-  p[16] = take((size_t)n_ref * 16);
-  if (w) {
-    w->P = (NnParams*)p[0];
-    w->ref_count = (uint32_t*)p[1];
-    w->ref_start = (uint32_t*)p[2];
-    w->q_count = (uint32_t*)p[3];
-    w->q_start = (uint32_t*)p[4];
-    w->ref_cell = (uint32_t*)p[5];
-    w->ref_slot = (uint32_t*)p[6];
-    w->q_cell = (uint32_t*)p[7];
-    w->q_slot = (uint32_t*)p[8];
-    w->scan_state = (uint64_t*)p[9];
-    w->ref_sorted = (float4*)p[10];
-    w->q_sorted = (float4*)p[11];
-    w->rc_count = (uint32_t*)p[12];
-    w->rc_start = (uint32_t*)p[13];
-    w->rc_cell = (uint32_t*)p[14];
-    w->rc_slot = (uint32_t*)p[15];
-    w->rc_sorted = (float4*)p[16];
-  }
-  return off;
+  Carver c(base);
+  NnWs t;
+  t.P = c.take<NnParams>(2);
+  t.ref_count = c.take<uint32_t>(n_bins);
+  t.ref_start = c.take<uint32_t>(n_bins);
+  t.q_count = c.take<uint32_t>(n_bins);
+  t.q_start = c.take<uint32_t>(n_bins);
+  t.ref_cell = c.take<uint32_t>(n_ref);
+  t.ref_slot = c.take<uint32_t>(n_ref);
+  t.q_cell = c.take<uint32_t>(n_query);
+  t.q_slot = c.take<uint32_t>(n_query);
+  t.scan_state = c.take<uint64_t>(tiles * 3);
+  t.ref_sorted = c.take<float4>(n_ref);
+  t.q_sorted = c.take<float4>(n_query);
+  t.rc_count = c.take<uint32_t>(n_bins);
+  t.rc_start = c.take<uint32_t>(n_bins);
+  t.rc_cell = c.take<uint32_t>(n_ref);
+  t.rc_slot = c.take<uint32_t>(n_ref);
+  t.rc_sorted = c.take<float4>(n_ref);
+  if (w) *w = t;
+  return c.bytes();
 }
 
 // the grid of cell size h (grown by 5/4 until it has at most `cap` cells) over the bounding box in P
@@ -435,10 +406,9 @@ int bnv_mesh_sample_surface(const float* vertices, int64_t n_vertices, const int
   if (!vertices || !faces || !uniforms || !workspace || !points_out || !face_ids_out) return BNV_ERR_INVALID_ARGUMENT;
   if (n_vertices <= 0 || n_vertices > INT32_MAX || n_faces <= 0 || n_faces > INT32_MAX || n <= 0 || n > INT32_MAX)
     return BNV_ERR_INVALID_ARGUMENT;
-  if (ws_bytes < (int64_t)sample_ws_layout(n_faces, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  hipStream_t s = (hipStream_t)stream;
   SampleWs ws;
-  sample_ws_layout(n_faces, (char*)workspace, &ws);
+  if (ws_bytes < (int64_t)sample_ws_layout(n_faces, (char*)workspace, &ws)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  hipStream_t s = (hipStream_t)stream;
   const int64_t tiles = (n_faces + kAreaTile - 1) / kAreaTile;
   BNV_HIP_CHECK(hipMemsetAsync(ws.tile_incl, 0xff, (size_t)tiles * 8, s));
   BNV_HIP_CHECK(hipMemsetAsync(ws.status, 0, sizeof(SampleStatus), s));
@@ -450,7 +420,7 @@ int bnv_mesh_sample_surface(const float* vertices, int64_t n_vertices, const int
   BNV_HIP_CHECK(hipMemcpyAsync(&st, ws.status, sizeof(st), hipMemcpyDeviceToHost, s));
   BNV_HIP_CHECK(hipStreamSynchronize(s));
   if (st.bad_faces || !(st.total > 0.0)) return BNV_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_sample_surface, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, vertices, faces, n_faces,
+  hipLaunchKernelGGL(k_sample_surface, dim3(blocks_for(n, 256)), dim3(256), 0, s, vertices, faces, n_faces,
                      uniforms, n, ws, points_out, face_ids_out, normals_out);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -467,10 +437,9 @@ int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_
                  int64_t ws_bytes, float* d2_out, int32_t* idx_out, bnv_stream_t stream) {
   if (!ref || !query || !workspace || !d2_out || !idx_out) return BNV_ERR_INVALID_ARGUMENT;
   if (n_ref <= 0 || n_query <= 0 || n_ref > INT32_MAX - 2 || n_query > INT32_MAX) return BNV_ERR_INVALID_ARGUMENT;
-  if (ws_bytes < (int64_t)nn_ws_layout(n_ref, n_query, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  hipStream_t s = (hipStream_t)stream;
   NnWs w;
-  nn_ws_layout(n_ref, n_query, (char*)workspace, &w);
+  if (ws_bytes < (int64_t)nn_ws_layout(n_ref, n_query, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  hipStream_t s = (hipStream_t)stream;
   const int64_t n_bins = n_ref + 2;
   const int64_t tiles = (n_bins + kScanTile - 1) / kScanTile;
   // everything the build accumulates into starts from a known state on every call (also when replayed from a graph):
@@ -479,7 +448,7 @@ int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_
   BNV_HIP_CHECK(hipMemsetAsync(w.q_count, 0, (size_t)n_bins * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(w.rc_count, 0, (size_t)n_bins * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(w.scan_state, 0, (size_t)tiles * 3 * 8, s));
-  const dim3 ref_blocks((unsigned)((n_ref + 255) / 256)), q_blocks((unsigned)((n_query + 255) / 256));
+  const dim3 ref_blocks(blocks_for(n_ref, 256)), q_blocks(blocks_for(n_query, 256));
   if (const int e = grid_bbox(ref, n_ref, w.P, 2 * sizeof(NnParams), s)) return e;
   hipLaunchKernelGGL(k_nn_params, dim3(1), dim3(64), 0, s, w.P, n_ref);
   BNV_LAUNCH_CHECK();

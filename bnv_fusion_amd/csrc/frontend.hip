@@ -8,6 +8,7 @@
 // rounding to float32 at the end, rows compacted by the validity mask in row-major pixel order with an
 // ordered prefix sum.  HBM-bound and tiny: 0.6 MB of depth in, 7.4 MB of points out per 640x480 frame.
 #include "frontend.hpp"
+#include "scan.hpp"
 
 namespace bnv {
 
@@ -30,22 +31,10 @@ __global__ __launch_bounds__(kFrontThreads) void k_front_count(FrontArgs a, uint
   if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
-// (256 threads: one wave per SIMD and 24 VGPRs fit beside the persistent MLP kernels of another stream; a 1024-thread
-// workgroup does not, and stalled its stream until the MLP kernel had finished -- rocprofv3 kernel trace)
-__global__ __launch_bounds__(256) void k_front_top(uint32_t* __restrict__ block_sums, int n_blocks,
-                                                    int32_t* __restrict__ total_out) {
-  __shared__ uint32_t wave_tot[16];
-  uint32_t carry = 0;
-  for (int base = 0; base < n_blocks; base += 256) {
-    const int i = base + threadIdx.x;
-    const uint32_t v = (i < n_blocks) ? block_sums[i] : 0;
-    uint32_t total;
-    const uint32_t ex = block_exclusive_scan<256>(v, wave_tot, &total);
-    if (i < n_blocks) block_sums[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *total_out = (int32_t)carry;
-}
+// the top level of the scan (k_scan_top) runs 256 threads here: one wave per SIMD and 24 VGPRs fit beside the
+// persistent MLP kernels of another stream; a 1024-thread workgroup does not, and stalled its stream until the MLP
+// kernel had finished -- rocprofv3 kernel trace
+constexpr int kFrontTopThreads = 256;
 
 // pad_total: when not null (= the valid-pixel count written by k_front_top), the rows behind the valid ones are
 // filled with NaN here -- invalid pixel i goes to row n_valid + (i - valid pixels before i) -- so that the caller
@@ -110,11 +99,11 @@ static int depth_to_points_impl(const void* depth, int depth_dtype, int H, int W
   a.conf = conf;
   a.conf_level = conf_level;
   hipStream_t stream = (hipStream_t)stream_;
-  const int nb = (int)(((int64_t)H * W + kFrontTile - 1) / kFrontTile);
+  const int nb = (int)blocks_for((int64_t)H * W, kFrontTile);
   uint32_t* sums = (uint32_t*)ws;
   hipLaunchKernelGGL(k_front_count, dim3(nb), dim3(kFrontThreads), 0, stream, a, sums);
   BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_front_top, dim3(1), dim3(256), 0, stream, sums, nb, n_out);
+  hipLaunchKernelGGL(k_scan_top<kFrontTopThreads>, dim3(1), dim3(kFrontTopThreads), 0, stream, sums, nb, n_out);
   BNV_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_front_points, dim3(nb), dim3(kFrontThreads), 0, stream, a, sums, out_pts,
                      pad ? (const int32_t*)n_out : (const int32_t*)nullptr);

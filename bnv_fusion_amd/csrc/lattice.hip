@@ -2,6 +2,8 @@
 // neighbour rows of every origin, the (row, l) table entries that live lattice points read (the work list of the table
 // kernels, decode.hip) and the blend of the tables into the SDF of the 3x3x3 meshing lattice.
 #include "decode_host.hpp"
+#include "scan.hpp"
+#include "volume_keys.hpp"
 #include "sdf_mlp.hpp"   // sample_delta only (k_lattice_blend<true>): the TSDF prior at a corner
 
 namespace bnv {
@@ -700,7 +702,7 @@ static size_t ws_offset(int64_t n_voxels, int64_t row_capacity, T* LatticeWs::*p
 // k_lattice_stamp over the call's origins; clear_ctl: it also clears the control words of the stages behind
 static int launch_stamp(const bnv_volume_t* vol, const int64_t* origins, int64_t n, int64_t row_limit,
                         const LatticeWs& ws, int32_t epoch, const int32_t* n_dev, bool clear_ctl, hipStream_t stream) {
-  hipLaunchKernelGGL(k_lattice_stamp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *vol, origins, n,
+  hipLaunchKernelGGL(k_lattice_stamp, dim3(blocks_for(n, 256)), dim3(256), 0, stream, *vol, origins, n,
                      row_limit, ws.origin_stamp, epoch, n_dev, clear_ctl ? ws.n_list : (int32_t*)nullptr);
   BNV_LAUNCH_CHECK();
   return BNV_OK;

@@ -17,6 +17,7 @@
 
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
+#include "scan.hpp"
 
 namespace bnv {
 
@@ -352,41 +353,14 @@ __global__ __launch_bounds__(256) void k_tm_count(TmGrid g, const int8_t* __rest
   }
 }
 
-__device__ __forceinline__ int64_t tm_wave_incl(int64_t x) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
-// exclusive scan over the block (blockDim.x = kTmScan); *total = the block's sum.  lds: 16 words
-__device__ __forceinline__ int64_t tm_block_excl(int64_t x, int64_t* lds, int64_t* total) {
-  const int w = threadIdx.x >> 6;
-  const int64_t inc = tm_wave_incl(x);
-  if ((threadIdx.x & 63) == 63) lds[w] = inc;
-  __syncthreads();
-  int64_t off = 0, sum = 0;
-  for (int k = 0; k < kTmScan / 64; ++k) {
-    const int64_t s = lds[k];
-    if (k < w) off += s;
-    sum += s;
-  }
-  __syncthreads();                       // lds is reused by the next call
-  *total = sum;
-  return off + inc - x;
-}
-
 __global__ __launch_bounds__(kTmScan) void k_tm_scan_reduce(const int64_t* __restrict__ n_verts,
                                                             const int64_t* __restrict__ n_tris, int64_t tiles,
                                                             int64_t* __restrict__ bsum) {
   __shared__ int64_t lds[kTmScan / 64];
   const int64_t t = (int64_t)blockIdx.x * kTmScan + threadIdx.x;
   int64_t sv, st;
-  tm_block_excl(t < tiles ? n_verts[t] : 0, lds, &sv);
-  tm_block_excl(t < tiles ? n_tris[t] : 0, lds, &st);
+  block_exclusive_scan<kTmScan>(t < tiles ? n_verts[t] : 0, lds, &sv);
+  block_exclusive_scan<kTmScan>(t < tiles ? n_tris[t] : 0, lds, &st);
   if (threadIdx.x == 0) {
     bsum[blockIdx.x * 2] = sv;
     bsum[blockIdx.x * 2 + 1] = st;
@@ -402,7 +376,7 @@ __global__ __launch_bounds__(kTmScan) void k_tm_scan_top(int64_t* __restrict__ b
     const int64_t b = b0 + threadIdx.x;
     const int64_t xv = b < blocks ? bsum[b * 2] : 0, xt = b < blocks ? bsum[b * 2 + 1] : 0;
     int64_t sv, st;
-    const int64_t ev = tm_block_excl(xv, lds, &sv), et = tm_block_excl(xt, lds, &st);
+    const int64_t ev = block_exclusive_scan<kTmScan>(xv, lds, &sv), et = block_exclusive_scan<kTmScan>(xt, lds, &st);
     if (b < blocks) {
       bsum[b * 2] = cv + ev;
       bsum[b * 2 + 1] = ct + et;
@@ -421,8 +395,8 @@ __global__ __launch_bounds__(kTmScan) void k_tm_scan_apply(int64_t* __restrict__
   __shared__ int64_t lds[kTmScan / 64];
   const int64_t t = (int64_t)blockIdx.x * kTmScan + threadIdx.x;
   int64_t sv, st;
-  const int64_t ev = tm_block_excl(t < tiles ? n_verts[t] : 0, lds, &sv);
-  const int64_t et = tm_block_excl(t < tiles ? n_tris[t] : 0, lds, &st);
+  const int64_t ev = block_exclusive_scan<kTmScan>(t < tiles ? n_verts[t] : 0, lds, &sv);
+  const int64_t et = block_exclusive_scan<kTmScan>(t < tiles ? n_tris[t] : 0, lds, &st);
   if (t < tiles) {
     n_verts[t] = bsum[blockIdx.x * 2] + ev;
     n_tris[t] = bsum[blockIdx.x * 2 + 1] + et;
@@ -478,7 +452,7 @@ __global__ __launch_bounds__(256) void k_tm_emit(TmGrid g, const float* __restri
       cs = tm_case(g, p);
       nt = tm_ntri(table, cs);
     }
-    const int64_t first = toff[tile] + tm_wave_incl(nt) - nt;
+    const int64_t first = toff[tile] + wave_inclusive_scan<int64_t>(nt) - nt;
     if (nt && first + nt <= t_cap) {
       const int8_t* row = table + cs * kMcRow;
       int64_t* fo = faces + first * 3;
@@ -546,7 +520,7 @@ int bnv_mc_count(const float* sdf, int64_t n, const int32_t* n_dev, float level,
                  int32_t* counts, bnv_stream_t stream) {
   if (n < 0 || (n > 0 && (!sdf || !tri_table || !counts))) return BNV_ERR_INVALID_ARGUMENT;
   if (n == 0) return BNV_OK;
-  hipLaunchKernelGGL(k_mc_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sdf, n, n_dev,
+  hipLaunchKernelGGL(k_mc_count, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, sdf, n, n_dev,
                      level, tri_table, counts);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -558,7 +532,7 @@ int bnv_mc_emit(const float* sdf, const int64_t* origins, int64_t n, const int32
   if (n < 0 || (n > 0 && (!sdf || !origins || !min_coords || !tri_table || !tri_offsets || !vertices)))
     return BNV_ERR_INVALID_ARGUMENT;
   if (n == 0) return BNV_OK;
-  hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sdf, origins, n,
+  hipLaunchKernelGGL(k_mc_emit, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, sdf, origins, n,
                      n_dev, level, voxel_size, min_coords[0], min_coords[1], min_coords[2], tri_table, tri_offsets,
                      vertices);
   BNV_LAUNCH_CHECK();
@@ -569,7 +543,7 @@ int bnv_mc_count_indexed(const float* sdf, int64_t n, const int32_t* n_dev, floa
                          int32_t* n_verts, int32_t* n_tris, bnv_stream_t stream) {
   if (n < 0 || (n > 0 && (!sdf || !tri_table || !n_verts || !n_tris))) return BNV_ERR_INVALID_ARGUMENT;
   if (n == 0) return BNV_OK;
-  hipLaunchKernelGGL(k_mc_count_indexed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sdf, n,
+  hipLaunchKernelGGL(k_mc_count_indexed, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, sdf, n,
                      n_dev, level, tri_table, n_verts, n_tris);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -583,7 +557,7 @@ int bnv_mc_emit_indexed(const float* sdf, const int64_t* origins, int64_t n, con
                           !faces)))
     return BNV_ERR_INVALID_ARGUMENT;
   if (n == 0) return BNV_OK;
-  hipLaunchKernelGGL(k_mc_emit_indexed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sdf,
+  hipLaunchKernelGGL(k_mc_emit_indexed, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, sdf,
                      origins, n, n_dev, level, voxel_size, min_coords[0], min_coords[1], min_coords[2], tri_table,
                      vert_offsets, tri_offsets, vertices, faces);
   BNV_LAUNCH_CHECK();
@@ -637,7 +611,7 @@ int bnv_tsdf_mesh_count(const float* tsdf, const float* weight, const int32_t di
   auto* toff = (int64_t*)(ws + L.toff);
   auto* bsum = (int64_t*)(ws + L.bsum);
   const TmGrid g = tm_grid(tsdf, weight, dim, level, observed_only);
-  hipLaunchKernelGGL(k_tm_count, dim3((unsigned)((L.tiles + kTmWaves - 1) / kTmWaves)), dim3(256), 0, s, g, tri_table,
+  hipLaunchKernelGGL(k_tm_count, dim3(blocks_for(L.tiles, kTmWaves)), dim3(256), 0, s, g, tri_table,
                      L.tiles, masks, voff, toff);
   BNV_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_tm_scan_reduce, dim3((unsigned)L.blocks), dim3(kTmScan), 0, s, voff, toff, L.tiles, bsum);
@@ -663,7 +637,7 @@ int bnv_tsdf_mesh_emit(const float* tsdf, const float* weight, const float* colo
   if (dim[0] < 2 || dim[1] < 2 || dim[2] < 2 || n_vertices == 0) return BNV_OK;
   const char* ws = (const char*)workspace;
   const TmGrid g = tm_grid(tsdf, weight, dim, level, observed_only);
-  hipLaunchKernelGGL(k_tm_emit, dim3((unsigned)((L.tiles + kTmWaves - 1) / kTmWaves)), dim3(256), 0,
+  hipLaunchKernelGGL(k_tm_emit, dim3(blocks_for(L.tiles, kTmWaves)), dim3(256), 0,
                      (hipStream_t)stream, g, color, tri_table, L.tiles, (const unsigned long long*)(ws + L.masks),
                      (const int64_t*)(ws + L.voff), (const int64_t*)(ws + L.toff), origin[0], origin[1], origin[2],
                      voxel_size, n_vertices, n_faces, vertices, faces, normals, colors);

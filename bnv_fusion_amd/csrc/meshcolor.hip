@@ -13,6 +13,7 @@
 
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 namespace {
@@ -35,12 +36,12 @@ struct NormWs {
 };
 
 static size_t norm_ws_layout(int64_t V, char* base, NormWs* w) {
-  const size_t hdr = align256(sizeof(NormHdr));
-  if (w) {
-    w->hdr = (NormHdr*)base;
-    w->sums = (unsigned long long*)(base + hdr);
-  }
-  return hdr + align256((size_t)V * 24);
+  Carver c(base);
+  NormWs t;
+  t.hdr = c.take<NormHdr>(1);
+  t.sums = c.take<unsigned long long>(3 * V);
+  if (w) *w = t;
+  return c.bytes();
 }
 
 struct ColorWs {
@@ -49,15 +50,13 @@ struct ColorWs {
 };
 
 static size_t color_ws_layout(int64_t V, char* base, ColorWs* w) {
-  const size_t sums = align256((size_t)V * 32);
-  if (w) {
-    w->sums = (double*)base;
-    w->count = (int32_t*)(base + sums);
-  }
-  return sums + align256((size_t)V * 4);
+  Carver c(base);
+  ColorWs t;
+  t.sums = c.take<double>(4 * V);
+  t.count = c.take<int32_t>(V);
+  if (w) *w = t;
+  return c.bytes();
 }
-
-inline unsigned blocks(int64_t n) { return (unsigned)((n + kColorThreads - 1) / kColorThreads); }
 
 // ---- vertex normals -------------------------------------------------------------------------------------------------
 // one thread per face: the cross product as three integers into the sums of its three corners; the face's area in units
@@ -289,12 +288,6 @@ __global__ __launch_bounds__(kColorThreads) void k_color_resolve(int64_t V, Colo
   if (count_out) count_out[i] = cnt;
 }
 
-static bool all_finite(const double* x, int n) {
-  for (int k = 0; k < n; ++k)
-    if (!std::isfinite(x[k])) return false;
-  return true;
-}
-
 static bool color_sizes_ok(int64_t V) { return V > 0 && V <= INT32_MAX - 1; }
 
 }  // namespace
@@ -316,13 +309,13 @@ int bnv_mesh_vertex_normals(const float* vertices, int64_t n_vertices, const int
   const int64_t V = n_vertices, T = n_faces;
   if (!vertices || !normals_out || !status || !color_sizes_ok(V) || T < 0 || T > INT32_MAX - 1 || (T && !faces))
     return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < (int64_t)norm_ws_layout(V, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  hipStream_t s = (hipStream_t)stream;
   NormWs w;
   const size_t bytes = norm_ws_layout(V, (char*)workspace, &w);
+  if (!workspace || ws_bytes < (int64_t)bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  hipStream_t s = (hipStream_t)stream;
   BNV_HIP_CHECK(hipMemsetAsync(workspace, 0, bytes, s));
-  if (T) k_vn_faces<<<blocks(T), kColorThreads, 0, s>>>(vertices, V, faces, T, w);
-  k_vn_normalize<<<blocks(V), kColorThreads, 0, s>>>(vertices, V, w, normals_out);
+  if (T) k_vn_faces<<<blocks_for(T, kColorThreads), kColorThreads, 0, s>>>(vertices, V, faces, T, w);
+  k_vn_normalize<<<blocks_for(V, kColorThreads), kColorThreads, 0, s>>>(vertices, V, w, normals_out);
   k_vn_status<<<1, 1, 0, s>>>(w, status);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -366,15 +359,14 @@ int bnv_mesh_color_accumulate(const float* vertices, const float* normals, int64
     a.shared[k] = f.color_height == f.height && f.color_width == f.width && f.K_color[0] == f.K[0] &&
                   f.K_color[1] == f.K[1] && f.K_color[2] == f.K[2] && f.K_color[3] == f.K[3];
   }
-  if (!workspace || ws_bytes < (int64_t)color_ws_layout(V, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  ColorWs w;
+  if (!workspace || ws_bytes < (int64_t)color_ws_layout(V, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
   a.n_frames = n_frames;
   a.depth_tol = depth_tol;
   a.cos_min = cos_min;
   a.near = near;
   a.max_depth = max_depth;
-  ColorWs w;
-  color_ws_layout(V, (char*)workspace, &w);
-  hipLaunchKernelGGL(k_color_accumulate, dim3(blocks(V)), dim3(kColorThreads), 0, (hipStream_t)stream, vertices,
+  hipLaunchKernelGGL(k_color_accumulate, dim3(blocks_for(V, kColorThreads)), dim3(kColorThreads), 0, (hipStream_t)stream, vertices,
                      normals, V, w, a);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -385,11 +377,11 @@ int bnv_mesh_color_resolve(const void* workspace, int64_t ws_bytes, int64_t n_ve
                            bnv_stream_t stream) {
   const int64_t V = n_vertices;
   if (!fill || !colors_out || !observed_out || !color_sizes_ok(V)) return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < (int64_t)color_ws_layout(V, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
   ColorWs w;
-  color_ws_layout(V, (char*)const_cast<void*>(workspace), &w);
+  if (!workspace || ws_bytes < (int64_t)color_ws_layout(V, (char*)const_cast<void*>(workspace), &w))
+    return BNV_ERR_WORKSPACE_TOO_SMALL;
   const Fill fl{{fill[0], fill[1], fill[2]}};
-  hipLaunchKernelGGL(k_color_resolve, dim3(blocks(V)), dim3(kColorThreads), 0, (hipStream_t)stream, V, w, fl,
+  hipLaunchKernelGGL(k_color_resolve, dim3(blocks_for(V, kColorThreads)), dim3(kColorThreads), 0, (hipStream_t)stream, V, w, fl,
                      colors_out, observed_out, sum_w_out, count_out);
   BNV_LAUNCH_CHECK();
   return BNV_OK;

@@ -15,6 +15,7 @@
 
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 namespace {
@@ -85,45 +86,38 @@ static size_t prim_bytes(int64_t V, int64_t T) {
 }
 
 static size_t post_ws_layout(int64_t V, int64_t T, char* base, PostWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += align256(bytes);
-    return base ? (void*)(base + o) : nullptr;
-  };
+  Carver c(base);
   PostWs l{};
   l.H = hash_slots(T);
-  l.hdr = (PostHdr*)take(sizeof(PostHdr));
-  for (int a = 0; a < 3; ++a) l.key[a] = (uint64_t*)take((size_t)V * 8);
-  l.ka = (uint64_t*)take((size_t)V * 8);
-  l.kb = (uint64_t*)take((size_t)V * 8);
-  l.pa = (int32_t*)take((size_t)V * 4);
-  l.pb = (int32_t*)take((size_t)V * 4);
-  l.flag = (int32_t*)take((size_t)V * 4);
-  l.scan = (int32_t*)take((size_t)V * 4);
-  l.inv = (int32_t*)take((size_t)V * 4);
-  l.parent = (int32_t*)take((size_t)V * 4);
-  l.cl = (int32_t*)take((size_t)V * 4);
-  l.ck = (uint32_t*)take((size_t)V * 4);
-  l.cks = (uint32_t*)take((size_t)V * 4);
-  l.cstart = (int32_t*)take((size_t)V * 4);
-  l.U = (double*)take((size_t)V * 24);
-  l.mean = (double*)take((size_t)V * 24);
-  l.canon = (int32_t*)take((size_t)T * 12);
-  l.slot_of = (int32_t*)take((size_t)T * 4);
-  l.keep = (int32_t*)take((size_t)T * 4);
-  l.fscan = (int32_t*)take((size_t)T * 4);
-  l.slots = (int32_t*)take((size_t)l.H * 4);
-  l.minf = (uint32_t*)take((size_t)l.H * 4);
-  l.edges = (uint64_t*)take((size_t)T * 48);
-  l.edges_s = (uint64_t*)take((size_t)T * 48);
+  l.hdr = c.take<PostHdr>(1);
+  for (int a = 0; a < 3; ++a) l.key[a] = c.take<uint64_t>(V);
+  l.ka = c.take<uint64_t>(V);
+  l.kb = c.take<uint64_t>(V);
+  l.pa = c.take<int32_t>(V);
+  l.pb = c.take<int32_t>(V);
+  l.flag = c.take<int32_t>(V);
+  l.scan = c.take<int32_t>(V);
+  l.inv = c.take<int32_t>(V);
+  l.parent = c.take<int32_t>(V);
+  l.cl = c.take<int32_t>(V);
+  l.ck = c.take<uint32_t>(V);
+  l.cks = c.take<uint32_t>(V);
+  l.cstart = c.take<int32_t>(V);
+  l.U = c.take<double>(3 * V);
+  l.mean = c.take<double>(3 * V);
+  l.canon = c.take<int32_t>(3 * T);
+  l.slot_of = c.take<int32_t>(T);
+  l.keep = c.take<int32_t>(T);
+  l.fscan = c.take<int32_t>(T);
+  l.slots = c.take<int32_t>(l.H);
+  l.minf = c.take<uint32_t>(l.H);
+  l.edges = c.take<uint64_t>(6 * T);
+  l.edges_s = c.take<uint64_t>(6 * T);
   l.tmp_bytes = prim_bytes(V, T);
-  l.tmp = take(l.tmp_bytes);
+  l.tmp = c.take<char>(l.tmp_bytes);
   if (w) *w = l;
-  return off;
+  return c.bytes();
 }
-
-inline unsigned blocks(int64_t n) { return (unsigned)((n + kPostThreads - 1) / kPostThreads); }
 
 // total order of doubles (no NaN) as unsigned integers; -0 was folded to +0 before
 __device__ __forceinline__ uint64_t sortable(double u) {
@@ -215,19 +209,32 @@ __global__ __launch_bounds__(kPostThreads) void k_pp_cells(int64_t V, double cel
                     : kPadKey;
 }
 
+// Union-find over parent[] (parent[x] <= x).  The weld walks plainly.  HALVE (the components: the whole room is one
+// component of millions of faces) halves the path as it walks: a node's parent is only ever replaced by an ancestor
+// further up (atomic min), so parent[x] <= x holds, every walk descends strictly, and the root found -- the
+// component's smallest member -- does not depend on what other threads do meanwhile.
+template <bool HALVE>
 __device__ __forceinline__ int32_t uf_find(int32_t* parent, int32_t x) {
   while (true) {
     const int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (p == x) return x;
-    x = p;
+    if constexpr (HALVE) {
+      const int32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (g == p) return p;
+      __hip_atomic_fetch_min(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      x = g;
+    } else {
+      x = p;
+    }
   }
 }
 
 // a root is only ever linked below a SMALLER root, so every component ends rooted at its smallest member
+template <bool HALVE>
 __device__ __forceinline__ void uf_union(int32_t* parent, int32_t a, int32_t b) {
   while (true) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
+    a = uf_find<HALVE>(parent, a);
+    b = uf_find<HALVE>(parent, b);
     if (a == b) return;
     if (a > b) {
       const int32_t t = a;
@@ -263,7 +270,7 @@ __global__ __launch_bounds__(kPostThreads) void k_pp_union(int64_t V, double cel
       const double dx = __dsub_rn(x, w.U[(int64_t)j * 3]), dy = __dsub_rn(y, w.U[(int64_t)j * 3 + 1]),
                    dz = __dsub_rn(z, w.U[(int64_t)j * 3 + 2]);
       const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-      if (d2 <= eps2) uf_union(w.parent, (int32_t)i, j);
+      if (d2 <= eps2) uf_union<false>(w.parent, (int32_t)i, j);
     }
   }
 }
@@ -274,7 +281,7 @@ __global__ __launch_bounds__(kPostThreads) void k_pp_roots(int64_t V, PostWs w) 
   const int64_t n = w.hdr->n_unique;
   int32_t is_root = 0;
   if (i < n) {
-    const int32_t r = uf_find(w.parent, (int32_t)i);
+    const int32_t r = uf_find<false>(w.parent, (int32_t)i);
     w.cl[i] = r;   // the component's smallest member (turned into the cluster number below)
     is_root = r == (int32_t)i;
   }
@@ -534,38 +541,32 @@ static size_t comp_prim_bytes(int64_t V, int64_t T) {
 }
 
 static size_t comp_ws_layout(int64_t V, int64_t T, char* base, CompWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += align256(bytes);
-    return base ? (void*)(base + o) : nullptr;
-  };
+  Carver c(base);
   CompWs l{};
-  const size_t t = (size_t)T, v = (size_t)V;
-  l.hdr = (CompHdr*)take(sizeof(CompHdr));
-  l.ekey = (uint64_t*)take(t * 24);
-  l.ekey_s = (uint64_t*)take(t * 24);
-  l.eface = (int32_t*)take(t * 12);
-  l.eface_s = (int32_t*)take(t * 12);
-  l.q = (int64_t*)take(t * 8);
-  l.parent = (int32_t*)take(t * 4);
-  l.flag = (int32_t*)take(t * 4);
-  l.scan = (int32_t*)take(t * 4);
-  l.sum = (unsigned long long*)take(t * 8);
-  l.labels = (int32_t*)take(t * 4);
-  l.cnt = (long long*)take(t * 8);
-  l.area = (double*)take(t * 8);
-  l.rkey = (uint64_t*)take(t * 8);
-  l.rkey_s = (uint64_t*)take(t * 8);
-  l.rval = (int32_t*)take(t * 4);
-  l.rval_s = (int32_t*)take(t * 4);
-  l.keepc = (int32_t*)take(t * 4);
-  l.vflag = (int32_t*)take(v * 4);
-  l.vscan = (int32_t*)take(v * 4);
+  l.hdr = c.take<CompHdr>(1);
+  l.ekey = c.take<uint64_t>(3 * T);
+  l.ekey_s = c.take<uint64_t>(3 * T);
+  l.eface = c.take<int32_t>(3 * T);
+  l.eface_s = c.take<int32_t>(3 * T);
+  l.q = c.take<int64_t>(T);
+  l.parent = c.take<int32_t>(T);
+  l.flag = c.take<int32_t>(T);
+  l.scan = c.take<int32_t>(T);
+  l.sum = c.take<unsigned long long>(T);
+  l.labels = c.take<int32_t>(T);
+  l.cnt = c.take<long long>(T);
+  l.area = c.take<double>(T);
+  l.rkey = c.take<uint64_t>(T);
+  l.rkey_s = c.take<uint64_t>(T);
+  l.rval = c.take<int32_t>(T);
+  l.rval_s = c.take<int32_t>(T);
+  l.keepc = c.take<int32_t>(T);
+  l.vflag = c.take<int32_t>(V);
+  l.vscan = c.take<int32_t>(V);
   l.tmp_bytes = comp_prim_bytes(V, T);
-  l.tmp = take(l.tmp_bytes);
+  l.tmp = c.take<char>(l.tmp_bytes);
   if (w) *w = l;
-  return off;
+  return c.bytes();
 }
 
 __global__ __launch_bounds__(kPostThreads) void k_mc_vcheck(const float* __restrict__ vin, int64_t n, int32_t* err) {
@@ -647,47 +648,19 @@ __global__ __launch_bounds__(kPostThreads) void k_mc_faces(const float* __restri
   }
 }
 
-// uf_find with path halving: the whole room is one component of millions of faces.  A node's parent is only ever
-// replaced by an ancestor further up (atomic min), so parent[x] <= x holds, every walk descends strictly, and the root
-// found -- the component's smallest member -- does not depend on what other threads do meanwhile.
-__device__ __forceinline__ int32_t uf_find_halve(int32_t* parent, int32_t x) {
-  while (true) {
-    const int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == x) return x;
-    const int32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (g == p) return p;
-    __hip_atomic_fetch_min(&parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = g;
-  }
-}
-
-__device__ __forceinline__ void uf_union_halve(int32_t* parent, int32_t a, int32_t b) {
-  while (true) {
-    a = uf_find_halve(parent, a);
-    b = uf_find_halve(parent, b);
-    if (a == b) return;
-    if (a > b) {
-      const int32_t t = a;
-      a = b;
-      b = t;
-    }
-    if (atomicCAS(&parent[b], b, a) == b) return;
-  }
-}
-
 // neighbours in the sorted edge array with equal keys: faces on one edge
 __global__ __launch_bounds__(kPostThreads) void k_mc_union(int64_t E, CompWs w) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k < 1 || k >= E) return;
   const uint64_t e = w.ekey_s[k];
   if (e == kPadKey || e != w.ekey_s[k - 1]) return;
-  uf_union_halve(w.parent, w.eface_s[k - 1], w.eface_s[k]);
+  uf_union<true>(w.parent, w.eface_s[k - 1], w.eface_s[k]);
 }
 
 __global__ __launch_bounds__(kPostThreads) void k_mc_roots(int64_t T, CompWs w) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
-  w.flag[t] = uf_find_halve(w.parent, (int32_t)t) == (int32_t)t;
+  w.flag[t] = uf_find<true>(w.parent, (int32_t)t) == (int32_t)t;
 }
 
 // components numbered in ascending order of their smallest face; per component the face count and the integer area,
@@ -706,7 +679,7 @@ __global__ __launch_bounds__(kPostThreads) void k_mc_labels(int64_t T, CompWs w,
   unsigned long long s = 0;
   long long n = 0;
   if (t < T) {
-    lab = w.scan[uf_find(w.parent, (int32_t)t)] - 1;
+    lab = w.scan[uf_find<false>(w.parent, (int32_t)t)] - 1;
     labels[t] = lab;
     s = (unsigned long long)w.q[t];
     n = 1;
@@ -845,13 +818,12 @@ int bnv_mesh_post_process(const float* vertices, int64_t n_vertices, const int64
   if (!counts || V < 0 || T < 0 || V > INT32_MAX - 1 || T > INT32_MAX - 1) return BNV_ERR_INVALID_ARGUMENT;
   if (!(vertex_threshold >= 0.0) || !std::isfinite(vertex_threshold)) return BNV_ERR_INVALID_ARGUMENT;
   if ((V && (!vertices || !vertices_out)) || (T && (!faces || !faces_out))) return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < (int64_t)post_ws_layout(V, T, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  hipStream_t s = (hipStream_t)stream;
   PostWs w;
-  post_ws_layout(V, T, (char*)workspace, &w);
+  if (!workspace || ws_bytes < (int64_t)post_ws_layout(V, T, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  hipStream_t s = (hipStream_t)stream;
   BNV_HIP_CHECK(hipMemsetAsync(w.hdr, 0, sizeof(PostHdr), s));
   if (V == 0 || T == 0) {   // nothing to weld (V == 0 with faces: every face index is out of range)
-    if (V) k_pp_passthrough<<<blocks(3 * V), kPostThreads, 0, s>>>(vertices, V, vertices_out, &w.hdr->error);
+    if (V) k_pp_passthrough<<<blocks_for(3 * V, kPostThreads), kPostThreads, 0, s>>>(vertices, V, vertices_out, &w.hdr->error);
     if (T) BNV_HIP_CHECK(hipMemsetAsync(&w.hdr->error, kErrFaceIndex, 1, s));
     k_pp_passthrough_counts<<<1, 1, 0, s>>>(T ? 0 : V, &w.hdr->error, counts);
     BNV_LAUNCH_CHECK();
@@ -861,46 +833,46 @@ int bnv_mesh_post_process(const float* vertices, int64_t n_vertices, const int64
   const size_t v = (size_t)V;
   size_t tb = w.tmp_bytes;
   // 1. weld: three stable LSD passes (z, y, x) of the 64-bit axis keys, ties in vertex order
-  k_pp_keys<<<blocks(V), kPostThreads, 0, s>>>(vertices, V, cell, w);
+  k_pp_keys<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(vertices, V, cell, w);
   BNV_PRIM_CHECK(rocprim::radix_sort_pairs(w.tmp, tb, w.key[2], w.kb, w.pa, w.pb, v, 0, 64, s));
-  k_pp_gather<<<blocks(V), kPostThreads, 0, s>>>(w.key[1], w.pb, V, w.ka);
+  k_pp_gather<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(w.key[1], w.pb, V, w.ka);
   BNV_PRIM_CHECK(rocprim::radix_sort_pairs(w.tmp, tb, w.ka, w.kb, w.pb, w.pa, v, 0, 64, s));
-  k_pp_gather<<<blocks(V), kPostThreads, 0, s>>>(w.key[0], w.pa, V, w.ka);
+  k_pp_gather<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(w.key[0], w.pa, V, w.ka);
   BNV_PRIM_CHECK(rocprim::radix_sort_pairs(w.tmp, tb, w.ka, w.kb, w.pa, w.pb, v, 0, 64, s));
-  k_pp_heads<<<blocks(V), kPostThreads, 0, s>>>(w.pb, V, w);
+  k_pp_heads<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(w.pb, V, w);
   BNV_PRIM_CHECK(rocprim::inclusive_scan(w.tmp, tb, w.flag, w.scan, v, rocprim::plus<int32_t>(), s));
-  k_pp_unique<<<blocks(V), kPostThreads, 0, s>>>(w.pb, V, w);
+  k_pp_unique<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(w.pb, V, w);
   // 2. clusters (eps = 0: every unique point is its own)
-  k_pp_cells<<<blocks(V), kPostThreads, 0, s>>>(V, cell, w);
+  k_pp_cells<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, cell, w);
   if (cell > 0.0) {
     BNV_PRIM_CHECK(rocprim::radix_sort_pairs(w.tmp, tb, w.ka, w.kb, w.pb, w.pa, v, 0, 64, s));
-    k_pp_union<<<blocks(V), kPostThreads, 0, s>>>(V, cell, eps2, w);
+    k_pp_union<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, cell, eps2, w);
   }
-  k_pp_roots<<<blocks(V), kPostThreads, 0, s>>>(V, w);
+  k_pp_roots<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, w);
   BNV_PRIM_CHECK(rocprim::inclusive_scan(w.tmp, tb, w.flag, w.scan, v, rocprim::plus<int32_t>(), s));
-  k_pp_labels<<<blocks(V), kPostThreads, 0, s>>>(V, w);
+  k_pp_labels<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, w);
   // 3. means (cluster keys sorted stably: members in ascending index order)
   BNV_PRIM_CHECK(rocprim::radix_sort_pairs(w.tmp, tb, w.ck, w.cks, w.pb, w.pa, v, 0, 32, s));
-  k_pp_cstart<<<blocks(V), kPostThreads, 0, s>>>(V, w);
-  k_pp_mean<<<blocks(V), kPostThreads, 0, s>>>(V, w);
+  k_pp_cstart<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, w);
+  k_pp_mean<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, w);
   // 4. faces
   BNV_HIP_CHECK(hipMemsetAsync(w.slots, 0xff, (size_t)w.H * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(w.minf, 0xff, (size_t)w.H * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(w.flag, 0, v * 4, s));
-  k_pp_face_canon<<<blocks(T), kPostThreads, 0, s>>>(faces, T, V, w);
-  k_pp_face_insert<<<blocks(T), kPostThreads, 0, s>>>(T, w);
-  k_pp_face_keep<<<blocks(T), kPostThreads, 0, s>>>(T, w);
+  k_pp_face_canon<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(faces, T, V, w);
+  k_pp_face_insert<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(T, w);
+  k_pp_face_keep<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(T, w);
   BNV_PRIM_CHECK(rocprim::inclusive_scan(w.tmp, tb, w.keep, w.fscan, (size_t)T, rocprim::plus<int32_t>(), s));
   // 5. referenced vertices
   BNV_PRIM_CHECK(rocprim::inclusive_scan(w.tmp, tb, w.flag, w.scan, v, rocprim::plus<int32_t>(), s));
-  k_pp_vert_compact<<<blocks(V), kPostThreads, 0, s>>>(V, T, w);
-  k_pp_face_write<<<blocks(T), kPostThreads, 0, s>>>(faces, T, V, w, faces_out);
+  k_pp_vert_compact<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, T, w);
+  k_pp_face_write<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(faces, T, V, w, faces_out);
   // 6. smoothing over the sorted directed edges
   const int64_t E = 6 * T;
   BNV_PRIM_CHECK(rocprim::radix_sort_keys(w.tmp, tb, w.edges, w.edges_s, (size_t)E, 0, 64, s));
   BNV_HIP_CHECK(hipMemsetAsync(w.cstart, 0xff, v * 4, s));
-  k_pp_rows<<<blocks(E), kPostThreads, 0, s>>>(E, w);
-  k_pp_smooth<<<blocks(V), kPostThreads, 0, s>>>(E, w, vertices_out);
+  k_pp_rows<<<blocks_for(E, kPostThreads), kPostThreads, 0, s>>>(E, w);
+  k_pp_smooth<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(E, w, vertices_out);
   k_pp_counts<<<1, 1, 0, s>>>(w, counts);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -915,13 +887,13 @@ static int mesh_components_run(const float* vertices, int64_t V, const int64_t* 
   size_t tb = w.tmp_bytes;
   BNV_HIP_CHECK(hipMemsetAsync(w.sum, 0, (size_t)T * 8, s));
   BNV_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)T * 8, s));
-  k_mc_faces<<<blocks(T), kPostThreads, 0, s>>>(vertices, V, faces, T, w);
+  k_mc_faces<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(vertices, V, faces, T, w);
   BNV_PRIM_CHECK(rocprim::radix_sort_pairs(w.tmp, tb, w.ekey, w.ekey_s, w.eface, w.eface_s, (size_t)E, 0, 64, s));
-  k_mc_union<<<blocks(E), kPostThreads, 0, s>>>(E, w);
-  k_mc_roots<<<blocks(T), kPostThreads, 0, s>>>(T, w);
+  k_mc_union<<<blocks_for(E, kPostThreads), kPostThreads, 0, s>>>(E, w);
+  k_mc_roots<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(T, w);
   BNV_PRIM_CHECK(rocprim::inclusive_scan(w.tmp, tb, w.flag, w.scan, (size_t)T, rocprim::plus<int32_t>(), s));
-  k_mc_labels<<<blocks(T), kPostThreads, 0, s>>>(T, w, labels, cnt);
-  k_mc_areas<<<blocks(T), kPostThreads, 0, s>>>(T, w, area);
+  k_mc_labels<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(T, w, labels, cnt);
+  k_mc_areas<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(T, w, area);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -942,12 +914,11 @@ int bnv_mesh_components(const float* vertices, int64_t n_vertices, const int64_t
   const int64_t V = n_vertices, T = n_faces;
   if (!count || !comp_sizes_ok(V, T)) return BNV_ERR_INVALID_ARGUMENT;
   if ((V && !vertices) || (T && (!faces || !labels || !n_faces_out || !areas_out))) return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < (int64_t)comp_ws_layout(V, T, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  hipStream_t s = (hipStream_t)stream;
   CompWs w;
-  comp_ws_layout(V, T, (char*)workspace, &w);
+  if (!workspace || ws_bytes < (int64_t)comp_ws_layout(V, T, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  hipStream_t s = (hipStream_t)stream;
   BNV_HIP_CHECK(hipMemsetAsync(w.hdr, 0, sizeof(CompHdr), s));
-  if (V) k_mc_vcheck<<<blocks(3 * V), kPostThreads, 0, s>>>(vertices, 3 * V, &w.hdr->error);
+  if (V) k_mc_vcheck<<<blocks_for(3 * V, kPostThreads), kPostThreads, 0, s>>>(vertices, 3 * V, &w.hdr->error);
   if (T) {
     const int rc = mesh_components_run(vertices, V, faces, T, w, labels, (long long*)n_faces_out, areas_out, s);
     if (rc != BNV_OK) return rc;
@@ -966,32 +937,31 @@ int bnv_mesh_filter_components(const float* vertices, int64_t n_vertices, const 
   if (!(min_area >= 0.0) || !std::isfinite(min_area) || min_faces < 0 || keep_largest < 0)
     return BNV_ERR_INVALID_ARGUMENT;
   if ((V && (!vertices || !vertices_out)) || (T && (!faces || !faces_out))) return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < (int64_t)comp_ws_layout(V, T, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  hipStream_t s = (hipStream_t)stream;
   CompWs w;
-  comp_ws_layout(V, T, (char*)workspace, &w);
+  if (!workspace || ws_bytes < (int64_t)comp_ws_layout(V, T, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  hipStream_t s = (hipStream_t)stream;
   BNV_HIP_CHECK(hipMemsetAsync(w.hdr, 0, sizeof(CompHdr), s));
-  if (V) k_mc_vcheck<<<blocks(3 * V), kPostThreads, 0, s>>>(vertices, 3 * V, &w.hdr->error);
+  if (V) k_mc_vcheck<<<blocks_for(3 * V, kPostThreads), kPostThreads, 0, s>>>(vertices, 3 * V, &w.hdr->error);
   if (T) {
     const int rc = mesh_components_run(vertices, V, faces, T, w, w.labels, w.cnt, w.area, s);
     if (rc != BNV_OK) return rc;
     size_t tb = w.tmp_bytes;
-    k_mc_keepc<<<blocks(T), kPostThreads, 0, s>>>(T, min_area, min_faces, w);
+    k_mc_keepc<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(T, min_area, min_faces, w);
     // The ranking sorts all T slots although only C are live: C is known on the device only, and reading it back would
     // be a host read.  Dead slots carry kPadKey.  A live component of area 0 has the same key (~bits(0.0) == kPadKey);
     // it still ranks before every dead slot because its index is smaller (live labels are 0..C-1) and the sort is
     // stable, and among live equals the smaller label comes first for the same reason.
     if (keep_largest > 0 && keep_largest < T) {   // (at most T components: a larger k keeps them all)
       BNV_PRIM_CHECK(rocprim::radix_sort_pairs(w.tmp, tb, w.rkey, w.rkey_s, w.rval, w.rval_s, (size_t)T, 0, 64, s));
-      k_mc_rank<<<blocks(T), kPostThreads, 0, s>>>(T, keep_largest, w);
+      k_mc_rank<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(T, keep_largest, w);
     }
     if (V) {
       BNV_HIP_CHECK(hipMemsetAsync(w.vflag, 0, (size_t)V * 4, s));
-      k_mc_fkeep<<<blocks(T), kPostThreads, 0, s>>>(faces, T, V, w);
+      k_mc_fkeep<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(faces, T, V, w);
       BNV_PRIM_CHECK(rocprim::inclusive_scan(w.tmp, tb, w.flag, w.scan, (size_t)T, rocprim::plus<int32_t>(), s));
       BNV_PRIM_CHECK(rocprim::inclusive_scan(w.tmp, tb, w.vflag, w.vscan, (size_t)V, rocprim::plus<int32_t>(), s));
-      k_mc_vwrite<<<blocks(V), kPostThreads, 0, s>>>(vertices, V, w, vertices_out);
-      k_mc_fwrite<<<blocks(T), kPostThreads, 0, s>>>(faces, T, w, faces_out);
+      k_mc_vwrite<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(vertices, V, w, vertices_out);
+      k_mc_fwrite<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(faces, T, w, faces_out);
     }
   }
   k_mc_fcounts<<<1, 1, 0, s>>>(V, T, w, counts);

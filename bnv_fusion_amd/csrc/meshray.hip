@@ -370,7 +370,7 @@ int bnv_mesh_ray_cast(const void* workspace, int64_t ws_bytes, const float* orig
   if (!workspace || !origins || !dirs || !t_out || n_rays <= 0 || n_rays > INT32_MAX) return BNV_ERR_INVALID_ARGUMENT;
   if (!(t_min <= t_max)) return BNV_ERR_INVALID_ARGUMENT;
   if (ws_bytes < (int64_t)msdf_layout(1, 1, nullptr, nullptr)) return BNV_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_ray_cast, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_ray_cast, dim3(blocks_for(n_rays, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const char*)workspace, ws_bytes, origins, dirs, n_rays, t_min, t_max, t_out, face_out, uv_out,
                      flags_out);
   BNV_LAUNCH_CHECK();

@@ -19,6 +19,7 @@
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
 #include "meshsdf.hpp"
+#include "scan.hpp"
 
 namespace bnv {
 namespace {
@@ -472,11 +473,10 @@ int bnv_mesh_sdf_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t* b
 int bnv_mesh_sdf_build(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
                        void* workspace, int64_t ws_bytes, bnv_stream_t stream) {
   if (!vertices || !faces || !workspace || !counts_ok(n_vertices, n_faces)) return BNV_ERR_INVALID_ARGUMENT;
-  const int64_t need = (int64_t)msdf_layout(n_vertices, n_faces, nullptr, nullptr);
+  Ws W;
+  const int64_t need = (int64_t)msdf_layout(n_vertices, n_faces, (char*)workspace, &W);
   if (ws_bytes < need) return BNV_ERR_INVALID_ARGUMENT;
   hipStream_t s = (hipStream_t)stream;
-  Ws W;
-  msdf_layout(n_vertices, n_faces, (char*)workspace, &W);
   const int64_t n_bins = W.cellcap + 2;
   // everything the build accumulates into starts from a known state on every call
   BNV_HIP_CHECK(hipMemsetAsync(W.vacc, 0, (size_t)n_vertices * 24, s));
@@ -487,7 +487,7 @@ int bnv_mesh_sdf_build(const float* vertices, int64_t n_vertices, const int32_t*
   BNV_HIP_CHECK(hipMemsetAsync(W.count[0], 0, (size_t)n_bins * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(W.count[1], 0, (size_t)n_bins * 4, s));
   BNV_HIP_CHECK(hipMemsetAsync(W.scan_state, 0, (size_t)W.tiles * 2 * 8, s));
-  const dim3 face_blocks((unsigned)((n_faces + 255) / 256));
+  const dim3 face_blocks(blocks_for(n_faces, 256));
   if (const int e = grid_bbox(vertices, n_vertices, W.H, sizeof(Header), s)) return e;   // clears the header
   hipLaunchKernelGGL(k_msdf_levels, dim3(1), dim3(64), 0, s, W.H, n_vertices, n_faces, need);
   BNV_LAUNCH_CHECK();
@@ -495,7 +495,7 @@ int bnv_mesh_sdf_build(const float* vertices, int64_t n_vertices, const int32_t*
   BNV_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_msdf_pick, dim3(1), dim3(64), 0, s, W.H, W.cellcap, W.paircap);
   BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_msdf_vflags, dim3((W.ecap + 255) / 256), dim3(256), 0, s, W);
+  hipLaunchKernelGGL(k_msdf_vflags, dim3(blocks_for(W.ecap, 256)), dim3(256), 0, s, W);
   BNV_LAUNCH_CHECK();
   for (int g = 0; g < 2; ++g) {
     hipLaunchKernelGGL(k_msdf_cells<false>, face_blocks, dim3(256), 0, s, W, g);
@@ -514,7 +514,7 @@ int bnv_mesh_sdf_query(const void* workspace, int64_t ws_bytes, const float* que
   if (!workspace || !query || !sdf_out || n_query <= 0 || n_query > INT32_MAX) return BNV_ERR_INVALID_ARGUMENT;
   if (ws_bytes < (int64_t)msdf_layout(1, 1, nullptr, nullptr)) return BNV_ERR_INVALID_ARGUMENT;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_msdf_query, dim3((unsigned)((n_query + 255) / 256)), dim3(256), 0, s, (char*)workspace, ws_bytes,
+  hipLaunchKernelGGL(k_msdf_query, dim3(blocks_for(n_query, 256)), dim3(256), 0, s, (char*)workspace, ws_bytes,
                      query, n_query, sdf_out, face_out, closest_out, feature_out);
   BNV_LAUNCH_CHECK();
   return BNV_OK;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "cell_grid.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 namespace {
@@ -69,37 +70,28 @@ __host__ __device__ inline size_t msdf_layout(int64_t nv, int64_t nf, char* base
   while ((int64_t)ecap < 4 * nf) ecap <<= 1;
   const int64_t cellcap = kCellsPerFace * nf + 64, paircap = kPairsPerFace * nf + 64;
   const int64_t n_bins = cellcap + 2, tiles = (n_bins + kScanTile - 1) / kScanTile;
-  size_t off = 0;
-  size_t o[14];
-  const size_t bytes[14] = {sizeof(Header), (size_t)nf * 48, (size_t)nv * 24, (size_t)nv * 4, (size_t)ecap * 8,
-                            (size_t)ecap * 24, (size_t)ecap * 4, (size_t)n_bins * 4, (size_t)n_bins * 4,
-                            (size_t)n_bins * 4, (size_t)n_bins * 4, (size_t)paircap * 4, (size_t)paircap * 4,
-                            (size_t)tiles * 2 * 8};
-  for (int k = 0; k < 14; ++k) {
-    o[k] = off;
-    off += align256(bytes[k]);
-  }
-  if (w) {
-    w->H = (Header*)(base + o[0]);
-    w->tri = (float4*)(base + o[1]);
-    w->vacc = (long long*)(base + o[2]);
-    w->vflag = (uint32_t*)(base + o[3]);
-    w->ekey = (unsigned long long*)(base + o[4]);
-    w->eacc = (long long*)(base + o[5]);
-    w->ecnt = (uint32_t*)(base + o[6]);
-    w->count[0] = (uint32_t*)(base + o[7]);
-    w->start[0] = (uint32_t*)(base + o[8]);
-    w->count[1] = (uint32_t*)(base + o[9]);
-    w->start[1] = (uint32_t*)(base + o[10]);
-    w->ids[0] = (uint32_t*)(base + o[11]);
-    w->ids[1] = (uint32_t*)(base + o[12]);
-    w->scan_state = (uint64_t*)(base + o[13]);
-    w->ecap = ecap;
-    w->cellcap = cellcap;
-    w->paircap = paircap;
-    w->tiles = tiles;
-  }
-  return off;
+  Carver c(base);
+  Ws t;
+  t.H = c.take<Header>(1);
+  t.tri = c.take<float4>(3 * nf);
+  t.vacc = c.take<long long>(3 * nv);
+  t.vflag = c.take<uint32_t>(nv);
+  t.ekey = c.take<unsigned long long>(ecap);
+  t.eacc = c.take<long long>(3 * (size_t)ecap);
+  t.ecnt = c.take<uint32_t>(ecap);
+  t.count[0] = c.take<uint32_t>(n_bins);
+  t.start[0] = c.take<uint32_t>(n_bins);
+  t.count[1] = c.take<uint32_t>(n_bins);
+  t.start[1] = c.take<uint32_t>(n_bins);
+  t.ids[0] = c.take<uint32_t>(paircap);
+  t.ids[1] = c.take<uint32_t>(paircap);
+  t.scan_state = c.take<uint64_t>(tiles * 2);
+  t.ecap = ecap;
+  t.cellcap = cellcap;
+  t.paircap = paircap;
+  t.tiles = tiles;
+  if (w) *w = t;
+  return c.bytes();
 }
 
 }  // namespace

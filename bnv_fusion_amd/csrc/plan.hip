@@ -15,6 +15,7 @@
 // All of it is integer counting: any schedule gives the same result, tests/plan_restatement.py restates it in numpy.
 #include "encode.hpp"
 #include "frontend.hpp"
+#include "workspace.hpp"
 
 #include <cmath>
 
@@ -255,19 +256,13 @@ __global__ void k_plan_finish(PlanCountArgs p) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------
-static bool plan_all_finite(const double* v, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 static bool plan_frame_args_ok(const void* depth, int depth_dtype, int H, int W, const double* intr, const double* T_wc,
                                double max_depth, const uint8_t* conf, int conf_level) {
   if (!depth || !intr || !T_wc || H <= 0 || W <= 0 || H > 32768 || W > 32768 || (int64_t)H * W > kPlanMaxPixels ||
       depth_dtype < 0 || depth_dtype > 2 || !front_conf_args_ok(conf, conf_level))
     return false;
   if (!(std::isfinite(max_depth) && max_depth > 0.0)) return false;
-  return plan_all_finite(intr, 9) && plan_all_finite(T_wc, 12) && intr[0] != 0.0 && intr[4] != 0.0;
+  return all_finite(intr, 9) && all_finite(T_wc, 12) && intr[0] != 0.0 && intr[4] != 0.0;
 }
 
 static bool plan_grid_ok(const bnv_grid_t& g) {
@@ -298,25 +293,20 @@ static bool plan_slots_arg_ok(int64_t table_slots) {
 static size_t plan_ws_layout(int H, int W, const bnv_grid_t* grids, int n_sizes, int64_t table_slots, char* base,
                              PlanTable* tables) {
   const int64_t n_blocks = ((int64_t)H * W + kPlanThreads - 1) / kPlanThreads;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off = align256(off + bytes);
-    return p;
-  };
+  Carver c(base);
   for (int s = 0; s < n_sizes; ++s) {
     const int64_t slots = plan_table_slots(H, W, grids[s], table_slots);
     PlanTable t;
-    t.keys = (uint32_t*)take((size_t)slots * 4);
-    t.counts = (uint32_t*)take((size_t)slots * 4);
-    t.valid_blocks = (int32_t*)take((size_t)n_blocks * 4);
+    t.keys = c.take<uint32_t>(slots);
+    t.counts = c.take<uint32_t>(slots);
+    t.valid_blocks = c.take<int32_t>(n_blocks);
     t.slots = (uint32_t)slots;
     int lg = 0;
     while (((int64_t)1 << lg) < slots) ++lg;
     t.shift = 32 - lg;
     if (tables) tables[s] = t;
   }
-  return off;
+  return c.bytes();
 }
 
 static bool plan_count_shape_ok(int H, int W, const bnv_grid_t* grids, int n_sizes, int64_t table_slots) {
@@ -358,7 +348,7 @@ extern "C" int bnv_plan_extent(const void* depth, int depth_dtype, int H, int W,
   if (!plan_frame_args_ok(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, conf, conf_level) || !dirs_host ||
       !hist || n_dirs < 1 || n_dirs > kPlanMaxDirs || n_bins < 2 || n_bins > 65536 || (n_bins & (n_bins - 1)) != 0)
     return BNV_ERR_INVALID_ARGUMENT;
-  if (!(std::isfinite(bin_size) && bin_size > 0.0) || !plan_all_finite(dirs_host, 3 * n_dirs))
+  if (!(std::isfinite(bin_size) && bin_size > 0.0) || !all_finite(dirs_host, 3 * n_dirs))
     return BNV_ERR_INVALID_ARGUMENT;
   PlanExtentArgs p{};
   front_args_fill(p.front, depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth);
@@ -369,7 +359,7 @@ extern "C" int bnv_plan_extent(const void* depth, int depth_dtype, int H, int W,
   p.bin_size = bin_size;
   for (int i = 0; i < 3 * n_dirs; ++i) p.dirs[i] = dirs_host[i];
   p.hist = (unsigned long long*)hist;
-  const unsigned n_blocks = (unsigned)(((int64_t)H * W + kPlanThreads - 1) / kPlanThreads);
+  const unsigned n_blocks = blocks_for((int64_t)H * W, kPlanThreads);
   hipLaunchKernelGGL(k_plan_extent, dim3(n_blocks), dim3(kPlanThreads), 0, (hipStream_t)stream_, p);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -396,7 +386,7 @@ extern "C" int bnv_plan_count(const void* depth, int depth_dtype, int H, int W, 
   }
   p.rows = (long long*)rows_out;
   hipStream_t stream = (hipStream_t)stream_;
-  const int n_blocks = (int)(((int64_t)H * W + kPlanThreads - 1) / kPlanThreads);
+  const int n_blocks = (int)blocks_for((int64_t)H * W, kPlanThreads);
   hipLaunchKernelGGL(k_plan_count, dim3((unsigned)n_blocks), dim3(kPlanThreads), 0, stream, p);
   BNV_LAUNCH_CHECK();
   const unsigned per_block = kPlanThreads * kPlanReduceItems;

@@ -20,6 +20,7 @@
 
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
+#include "volume_keys.hpp"
 
 namespace bnv {
 
@@ -245,7 +246,7 @@ int bnv_ray_samples(const float* uv, const float* gt_pts, const float* ray_mask,
   a.truncated_dist = truncated_dist;
   a.pts = pts; a.target = target; a.weight = weight;
   const int64_t threads = (int64_t)n * (n_fine + n_coarse);
-  hipLaunchKernelGGL(k_ray_samples, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_ray_samples, dim3(blocks_for(threads, 256)), dim3(256), 0, (hipStream_t)stream, a);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -255,7 +256,7 @@ int bnv_ray_loss_splits(const float* pred, const float* target, const float* wei
   if (m < 0 || split_samples < 0 || (m > 0 && (!pred || !target || !weight || !n_valid || !loss || !grad)))
     return BNV_ERR_INVALID_ARGUMENT;
   if (m == 0) return BNV_OK;
-  hipLaunchKernelGGL(k_ray_loss, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pred, target,
+  hipLaunchKernelGGL(k_ray_loss, dim3(blocks_for(m, 256)), dim3(256), 0, (hipStream_t)stream, pred, target,
                      weight, n_valid, m, split_samples, loss, grad);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -273,7 +274,7 @@ int bnv_volume_count_optim_splits(const bnv_volume_t* vol, const bnv_grid_t* gri
     return BNV_ERR_INVALID_ARGUMENT;
   if (m == 0) return BNV_OK;
   if (!pts) return BNV_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_count_optim_splits, dim3((unsigned)((m * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_count_optim_splits, dim3(blocks_for(m * 8, 256)), dim3(256), 0, (hipStream_t)stream,
                      *vol, *grid, pts, m, is_coords, row_limit, split_samples, split_mask);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -282,7 +283,7 @@ int bnv_volume_count_optim_splits(const bnv_volume_t* vol, const bnv_grid_t* gri
 int bnv_volume_apply_split_counts(float* weights, uint32_t* split_mask, int64_t n_rows, bnv_stream_t stream) {
   if (n_rows < 0 || (n_rows > 0 && (!weights || !split_mask))) return BNV_ERR_INVALID_ARGUMENT;
   if (n_rows == 0) return BNV_OK;
-  hipLaunchKernelGGL(k_apply_split_counts, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_apply_split_counts, dim3(blocks_for(n_rows, 256)), dim3(256), 0, (hipStream_t)stream,
                      weights, split_mask, n_rows);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -294,7 +295,7 @@ int bnv_volume_count_optim_pts(const bnv_volume_t* vol, const bnv_grid_t* grid, 
   if (!vol || !grid || m < 0 || !stamp || !weights) return BNV_ERR_INVALID_ARGUMENT;
   if (m == 0) return BNV_OK;
   if (!pts) return BNV_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_count_optim_pts, dim3((unsigned)((m * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *vol,
+  hipLaunchKernelGGL(k_count_optim_pts, dim3(blocks_for(m * 8, 256)), dim3(256), 0, (hipStream_t)stream, *vol,
                      *grid, pts, m, is_coords, weights, row_limit, stamp, epoch);
   BNV_LAUNCH_CHECK();
   return BNV_OK;

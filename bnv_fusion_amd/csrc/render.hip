@@ -18,6 +18,9 @@
 
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
+#include "scan.hpp"
+#include "volume_keys.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 
@@ -100,12 +103,7 @@ __device__ __forceinline__ void normalise3(float (&g)[3]) {
 // wave-wide exclusive prefix of `count`; lane 63 reserves the wave's total from *counter (one atomic per wave)
 __device__ __forceinline__ int32_t wave_alloc(int32_t count, int32_t* counter) {
   const int lane = threadIdx.x & 63;
-  int32_t incl = count;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int32_t y = __shfl_up(incl, off);
-    if (lane >= off) incl += y;
-  }
+  const int32_t incl = wave_inclusive_scan(count);
   const int32_t total = __shfl(incl, 63);
   int32_t base = 0;
   if (lane == 63 && total > 0) base = atomicAdd(counter, total);
@@ -139,29 +137,24 @@ struct RenderWs {
 };
 
 static size_t render_ws_layout(int64_t n, int k, char* base, RenderWs* w) {
-  size_t off = 0;
   const int64_t m = k + 1 > 6 ? k + 1 : 6;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align256(bytes);
-    return p;
-  };
+  Carver c(base);
   RenderWs t;
-  t.cursor = (int32_t*)take(n * 4);
-  t.prev_k = (int32_t*)take(n * 4);
-  t.prev_f = (float*)take(n * 4);
-  t.hit_t = (float*)take(n * 4);
-  t.slot_base = (int32_t*)take(n * 4);
-  t.slot_cnt = (int32_t*)take(n * 4);
-  t.active[0] = (int32_t*)take(n * 4);
-  t.active[1] = (int32_t*)take(n * 4);
-  t.hit_list = (int32_t*)take(n * 4);
-  t.sample_k = (int32_t*)take(n * (k + 1) * 4);
-  t.pts = (float*)take(n * m * 12);
-  t.vals = (float*)take(n * m * 4);
-  t.ctr = (RenderCtr*)take(sizeof(RenderCtr));
+  t.cursor = c.take<int32_t>(n);
+  t.prev_k = c.take<int32_t>(n);
+  t.prev_f = c.take<float>(n);
+  t.hit_t = c.take<float>(n);
+  t.slot_base = c.take<int32_t>(n);
+  t.slot_cnt = c.take<int32_t>(n);
+  t.active[0] = c.take<int32_t>(n);
+  t.active[1] = c.take<int32_t>(n);
+  t.hit_list = c.take<int32_t>(n);
+  t.sample_k = c.take<int32_t>(n * (k + 1));
+  t.pts = c.take<float>(n * m * 3);
+  t.vals = c.take<float>(n * m);
+  t.ctr = c.take<RenderCtr>(1);
   if (w) *w = t;
-  return off;
+  return c.bytes();
 }
 
 struct NeuralField {
@@ -482,16 +475,10 @@ __global__ __launch_bounds__(kRenderThreads) void k_tsdf_render(RenderCam cam, T
 
 // ---- host ----------------------------------------------------------------------------------------------------------
 
-static bool finite_all(const float* v, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!isfinite(v[i])) return false;
-  return true;
-}
-
 // camera + box from the caller's arguments; false on an invalid camera
 static bool make_cam(const float T_wc[16], const float K[9], int32_t H, int32_t W, float near_z, float max_depth,
                      float step_world, const float lo[3], const float hi[3], RenderCam* c) {
-  if (!T_wc || !K || H <= 0 || W <= 0 || !finite_all(T_wc, 16) || !finite_all(K, 9)) return false;
+  if (!T_wc || !K || H <= 0 || W <= 0 || !all_finite(T_wc, 16) || !all_finite(K, 9)) return false;
   if (!(K[0] != 0.f) || !(K[4] != 0.f) || !(step_world > 0.f) || !isfinite(step_world)) return false;
   if (!(near_z >= 0.f) || !isfinite(near_z) || !(max_depth >= 0.f) || isnan(max_depth)) return false;
   for (int a = 0; a < 3; ++a)
@@ -519,8 +506,6 @@ static bool render_dims_ok(int32_t H, int32_t W, int32_t k) {
   return n * m * 3 < INT32_MAX;
 }
 
-static unsigned blocks_for(int64_t n) { return (unsigned)((n + kRenderThreads - 1) / kRenderThreads); }
-
 }  // namespace bnv
 
 using namespace bnv;
@@ -544,7 +529,8 @@ int bnv_render_depth(const bnv_volume_t* vol, const bnv_grid_t* grid, const floa
   if (grid->shard_world > 1) return BNV_ERR_INVALID_ARGUMENT;
   if (!render_dims_ok(H, W, k) || !(step >= BNV_RENDER_MIN_STEP)) return BNV_ERR_INVALID_ARGUMENT;
   const int64_t n = (int64_t)H * W;
-  if (ws_bytes < render_ws_layout(n, k, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  RenderWs w;
+  if (ws_bytes < render_ws_layout(n, k, (char*)ws, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
   float lo[3], hi[3];
   for (int a = 0; a < 3; ++a) {
     lo[a] = grid->bound_min[a];
@@ -554,8 +540,6 @@ int bnv_render_depth(const bnv_volume_t* vol, const bnv_grid_t* grid, const floa
   RenderCam cam;
   if (!make_cam(T_wc, K, H, W, near_z, max_depth, step * grid->voxel_size, lo, hi, &cam))
     return BNV_ERR_INVALID_ARGUMENT;
-  RenderWs w;
-  render_ws_layout(n, k, (char*)ws, &w);
   NeuralField F;
   F.vol = *vol;
   F.grid = *grid;
@@ -563,7 +547,7 @@ int bnv_render_depth(const bnv_volume_t* vol, const bnv_grid_t* grid, const floa
   F.row_limit = row_limit;
   hipStream_t s = (hipStream_t)stream;
   BNV_HIP_CHECK(hipMemsetAsync(w.ctr, 0, sizeof(RenderCtr), s));
-  hipLaunchKernelGGL(k_render_init, dim3(blocks_for(n)), dim3(kRenderThreads), 0, s, cam, w, n, depth_out,
+  hipLaunchKernelGGL(k_render_init, dim3(blocks_for(n, kRenderThreads)), dim3(kRenderThreads), 0, s, cam, w, n, depth_out,
                      normals_out);
   BNV_LAUNCH_CHECK();
   int cur = 0;
@@ -572,7 +556,7 @@ int bnv_render_depth(const bnv_volume_t* vol, const bnv_grid_t* grid, const floa
     BNV_HIP_CHECK(hipMemsetAsync(&w.ctr->n_samples, 0, 4, s));
     BNV_HIP_CHECK(hipMemsetAsync(&w.ctr->n_active[cur ^ 1], 0, 4, s));
     if (bound > 0) {
-      hipLaunchKernelGGL(k_render_emit, dim3(blocks_for(bound)), dim3(kRenderThreads), 0, s, cam, w, F, cur, (int)k,
+      hipLaunchKernelGGL(k_render_emit, dim3(blocks_for(bound, kRenderThreads)), dim3(kRenderThreads), 0, s, cam, w, F, cur, (int)k,
                          stats_host ? 1 : 0);
       BNV_LAUNCH_CHECK();
     }
@@ -589,7 +573,7 @@ int bnv_render_depth(const bnv_volume_t* vol, const bnv_grid_t* grid, const floa
                                     w.vals, stream);
       if (rc != BNV_OK) return rc;
     }
-    hipLaunchKernelGGL(k_render_resolve, dim3(blocks_for(n_act)), dim3(kRenderThreads), 0, s, cam, w, cur, n_act,
+    hipLaunchKernelGGL(k_render_resolve, dim3(blocks_for(n_act, kRenderThreads)), dim3(kRenderThreads), 0, s, cam, w, cur, n_act,
                        depth_out);
     BNV_LAUNCH_CHECK();
     bound = n_act;
@@ -597,7 +581,7 @@ int bnv_render_depth(const bnv_volume_t* vol, const bnv_grid_t* grid, const floa
   }
   int32_t n_hits = 0;
   if (normals_out || stats_host) {
-    hipLaunchKernelGGL(k_render_hit_points, dim3(blocks_for(n)), dim3(kRenderThreads), 0, s, cam, w, n,
+    hipLaunchKernelGGL(k_render_hit_points, dim3(blocks_for(n, kRenderThreads)), dim3(kRenderThreads), 0, s, cam, w, n,
                        BNV_RENDER_NORMAL_EPS * grid->voxel_size);
     BNV_LAUNCH_CHECK();
     BNV_HIP_CHECK(hipMemcpyAsync(&n_hits, &w.ctr->n_hits, 4, hipMemcpyDeviceToHost, s));
@@ -607,7 +591,7 @@ int bnv_render_depth(const bnv_volume_t* vol, const bnv_grid_t* grid, const floa
     const int rc = bnv_decode_pts(vol, grid, features, weights, row_limit, sdfmlp_pack, w.pts, (int64_t)n_hits * 6, 0,
                                   delta, w.vals, stream);
     if (rc != BNV_OK) return rc;
-    hipLaunchKernelGGL(k_render_normals, dim3(blocks_for(n_hits)), dim3(kRenderThreads), 0, s, w, n_hits, normals_out);
+    hipLaunchKernelGGL(k_render_normals, dim3(blocks_for(n_hits, kRenderThreads)), dim3(kRenderThreads), 0, s, w, n_hits, normals_out);
     BNV_LAUNCH_CHECK();
   }
   if (stats_host) {
@@ -644,7 +628,7 @@ int bnv_tsdf_render_depth(const float* tsdf, const float* weight, const int32_t 
   RenderCam cam;
   if (!make_cam(T_wc, K, H, W, near_z, max_depth, step * voxel_size, lo, hi, &cam)) return BNV_ERR_INVALID_ARGUMENT;
   const int64_t n = (int64_t)H * W;
-  hipLaunchKernelGGL(k_tsdf_render, dim3(blocks_for(n)), dim3(kRenderThreads), 0, (hipStream_t)stream, cam, T, n,
+  hipLaunchKernelGGL(k_tsdf_render, dim3(blocks_for(n, kRenderThreads)), dim3(kRenderThreads), 0, (hipStream_t)stream, cam, T, n,
                      depth_out, normals_out);
   BNV_LAUNCH_CHECK();
   return BNV_OK;

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "encode.hpp"
+#include "scan.hpp"
 
 namespace bnv {
 
@@ -36,7 +37,7 @@ void prof_mark(int kind, bool begin, hipStream_t stream) {
     ++g_prof_used[kind];
   }
 }
-// every launch of a look-back kernel takes a fresh epoch (bnv_common.hpp: lookback_exclusive)
+// every launch of a look-back kernel takes a fresh epoch (scan.hpp: lookback_exclusive)
 // (atomic: host threads driving different streams / volumes each get their own; the 30-bit tag never takes the value
 // 0, which is what a zero-initialised workspace word carries)
 static std::atomic<uint32_t> g_epoch{0};

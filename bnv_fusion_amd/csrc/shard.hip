@@ -19,6 +19,8 @@
 // First-touch ownership (bnv_grid_t.shard_state: a table instead of the hash) runs inside the encode, behind k_rank:
 //   k_shard_assign / k_shard_own   owners for a frame's new blocks; the pair list and exchange bound left open till then
 #include "encode.hpp"
+#include "scan.hpp"
+#include "volume_keys.hpp"
 
 namespace bnv {
 
@@ -458,7 +460,7 @@ int launch_shard_own(const EncodeWs& ws, const bnv_grid_t& g, const float* pts, 
   hipLaunchKernelGGL(k_shard_assign, dim3(1), dim3(256), 0, stream, g, (const EncCtl*)ws.ctl);
   BNV_LAUNCH_CHECK();
   // (a frame without a new block leaves it nothing to do: a small grid that strides, not a workgroup per 256 points)
-  const int nb = (n_points + 255) / 256;
+  const int nb = (int)blocks_for(n_points, 256);
   const int cap = 64;
   hipLaunchKernelGGL(k_shard_own, dim3(nb < cap ? (nb > 0 ? nb : 1) : cap), dim3(256), 0, stream, pts, n_points, g,
                      pair_list, &ws.ctl->n_pairs, ws.orphan_list, ws.ids, ws.defer_list, ws.ctl);
@@ -501,7 +503,7 @@ int bnv_shard_pack(const bnv_volume_t* vol, const bnv_grid_t* grid, const int64_
   hipLaunchKernelGGL(k_shard_pack_header, dim3(1), dim3(1), 0, stream, (ShardRec*)block, grid->shard_rank);
   BNV_LAUNCH_CHECK();
   if (n == 0) return BNV_OK;
-  hipLaunchKernelGGL(k_shard_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *vol, *grid, coords, n,
+  hipLaunchKernelGGL(k_shard_pack, dim3(blocks_for(n, 256)), dim3(256), 0, stream, *vol, *grid, coords, n,
                      n_dev, (ShardRec*)block, capacity);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -513,7 +515,7 @@ int bnv_shard_install_reset(const bnv_volume_t* vol, const bnv_grid_t* grid, con
     return BNV_ERR_INVALID_ARGUMENT;
   if (capacity == 0 || world == 1) return BNV_OK;
   const int64_t total = (int64_t)world * capacity;
-  hipLaunchKernelGGL(k_shard_install, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, *vol,
+  hipLaunchKernelGGL(k_shard_install, dim3(blocks_for(total, 256)), dim3(256), 0, (hipStream_t)stream_, *vol,
                      *grid, (const ShardRec*)blocks, world, capacity, vol->n_rows + 1, (ShardRec*)own_send_block);
   BNV_LAUNCH_CHECK();
   return BNV_OK;

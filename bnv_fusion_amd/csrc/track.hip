@@ -338,12 +338,6 @@ __global__ __launch_bounds__(64) void k_icp_solve(IcpSolve a, const double* __re
     for (int i = 0; i < 16; ++i) poses[(int64_t)a.n_iter * 16 + i] = Tn[i];
 }
 
-bool all_finite(const double* m, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(m[i])) return false;
-  return true;
-}
-
 // total iterations of a schedule, or -1 when it is not one
 int64_t schedule_iterations(int32_t n_levels, const int32_t* levels) {
   if (!levels || n_levels < 1 || n_levels > kMaxLevels) return -1;
@@ -365,6 +359,7 @@ extern "C" {
 size_t bnv_icp_workspace_bytes(int32_t n_levels, const int32_t* levels_host) {
   const int64_t n_iter = schedule_iterations(n_levels, levels_host);
   if (n_iter < 0) return 0;
+  // (packed, not carved: the records follow the partial rows directly, as include/bnv_fusion.h documents them)
   return ((size_t)kBlocks * kSums + (size_t)n_iter * kRecord) * sizeof(double);
 }
 

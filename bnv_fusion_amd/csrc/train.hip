@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "bnv_common.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 namespace train {
@@ -319,7 +320,6 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
 }
 
 // ---- host side ----
-static inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 constexpr int64_t kMaxSplits = 64;
 constexpr int64_t kMinChunkRows = 256;
@@ -350,34 +350,29 @@ static int64_t partial_floats(int64_t Re, int64_t Rd) {
 }
 static size_t layout_ws(int64_t B, int n, int64_t M, char* base, Ws* w) {
   const int64_t Re = B * n, Rd = B * M;
-  size_t off = 0;
-  auto take = [&](int64_t floats) -> float* {
-    float* p = base ? (float*)(base + off) : nullptr;
-    off += (size_t)cdiv(floats, 64) * 64 * sizeof(float);
-    return p;
-  };
+  Carver c(base);
   Ws t;
-  t.X0 = take(Re * kNin);
-  for (int l = 0; l < 4; ++l) t.Z[l] = take(Re * (l < 3 ? kC : kF));
-  for (int l = 0; l < 3; ++l) t.A[l] = take(Re * kC);
-  t.Y4 = take(Re * kF);
-  t.stats = take(8 * kC);       // per layer: mean [C], rstd [C]
-  t.feats = take(B * kF);
-  t.D0 = take(Rd * kDin);
-  for (int l = 0; l < 4; ++l) t.Hd[l] = take(Rd * kH);
-  t.pred = take(Rd);
-  t.dpred = take(Rd);
-  t.dH[0] = take(Rd * kH);
-  t.dH[1] = take(Rd * kH);
-  t.dfrows = take(Rd * kF);
-  t.dfeats = take(B * kF);
-  t.dE[0] = take(Re * kC);
-  t.dE[1] = take(Re * kC);
-  t.part = take(partial_floats(Re, Rd));
-  t.loss_tmp = take(4);
-  t.bytes = off;
+  t.X0 = c.take<float>(Re * kNin);
+  for (int l = 0; l < 4; ++l) t.Z[l] = c.take<float>(Re * (l < 3 ? kC : kF));
+  for (int l = 0; l < 3; ++l) t.A[l] = c.take<float>(Re * kC);
+  t.Y4 = c.take<float>(Re * kF);
+  t.stats = c.take<float>(8 * kC);       // per layer: mean [C], rstd [C]
+  t.feats = c.take<float>(B * kF);
+  t.D0 = c.take<float>(Rd * kDin);
+  for (int l = 0; l < 4; ++l) t.Hd[l] = c.take<float>(Rd * kH);
+  t.pred = c.take<float>(Rd);
+  t.dpred = c.take<float>(Rd);
+  t.dH[0] = c.take<float>(Rd * kH);
+  t.dH[1] = c.take<float>(Rd * kH);
+  t.dfrows = c.take<float>(Rd * kF);
+  t.dfeats = c.take<float>(B * kF);
+  t.dE[0] = c.take<float>(Re * kC);
+  t.dE[1] = c.take<float>(Re * kC);
+  t.part = c.take<float>(partial_floats(Re, Rd));
+  t.loss_tmp = c.take<float>(4);
+  t.bytes = c.bytes();
   if (w) *w = t;
-  return off;
+  return c.bytes();
 }
 
 static bool shape_ok(int64_t B, int64_t n, int64_t M) {
@@ -402,7 +397,7 @@ static int gemm_dw(hipStream_t s, const float* dZ, int64_t N_out, const float* X
   GemmArgs g{dZ, 1, N_out, X, K_in, 1, part, K_in, N_out, K_in, R, rows, nullptr, nullptr, 0, 0};
   dim3 grid((unsigned)cdiv(N_out, TM), (unsigned)cdiv(K_in, TN), (unsigned)S);
   k_gemm<<<grid, kGemmThreads, 0, s>>>(g);
-  k_sum_partials<<<blocks256(N_out * K_in), 256, 0, s>>>(part, S, N_out * K_in, out);
+  k_sum_partials<<<blocks_for(N_out * K_in, 256), 256, 0, s>>>(part, S, N_out * K_in, out);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -412,8 +407,8 @@ static int colsum(hipStream_t s, const float* X, const float* Y, int64_t R, int 
   const int64_t rows = kColChunkRows, S = cdiv(R, rows);
   float* p2 = part + S * C;
   k_col_partials<<<(unsigned)S, 256, 0, s>>>(X, Y, R, C, C, rows, mean, mode, part, p2);
-  k_sum_partials<<<blocks256(C), 256, 0, s>>>(part, S, C, out);
-  if (mode == 2) k_sum_partials<<<blocks256(C), 256, 0, s>>>(p2, S, C, out2);
+  k_sum_partials<<<blocks_for(C, 256), 256, 0, s>>>(part, S, C, out);
+  if (mode == 2) k_sum_partials<<<blocks_for(C, 256), 256, 0, s>>>(p2, S, C, out2);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -423,7 +418,7 @@ static int forward(hipStream_t s, const Layout& L, const float* params, float* r
                    const float* training_pts, const float* gt, int64_t B, int n, int64_t M, int train, Ws& w,
                    float* loss_out) {
   const int64_t Re = B * n, Rd = B * M;
-  k_gather_input<<<blocks256(Re * kNin), 256, 0, s>>>(input_pts, B, n, w.X0);
+  k_gather_input<<<blocks_for(Re * kNin, 256), 256, 0, s>>>(input_pts, B, n, w.X0);
   const int cin[4] = {kNin, kC, kC, kC}, cout[4] = {kC, kC, kC, kF};
   const float* X = w.X0;
   for (int l = 0; l < 4; ++l) {
@@ -443,12 +438,12 @@ static int forward(hipStream_t s, const Layout& L, const float* params, float* r
       k_bn_stats<<<1, kC, 0, s>>>(0, 1, 0, C, Re, mean, rstd, rm, rv);
     }
     float* out = l < 3 ? w.A[l] : w.Y4;
-    k_bn_apply<<<blocks256(Re * C), 256, 0, s>>>(w.Z[l], Re, C, mean, rstd, params + L.bn_w[l], params + L.bn_b[l],
+    k_bn_apply<<<blocks_for(Re * C, 256), 256, 0, s>>>(w.Z[l], Re, C, mean, rstd, params + L.bn_w[l], params + L.bn_b[l],
                                                  l < 3, out);
     X = out;
   }
-  k_patch_mean<<<blocks256(B * kF), 256, 0, s>>>(w.Y4, B, n, w.feats);
-  k_decoder_input<<<blocks256(Rd), 256, 0, s>>>(training_pts, w.feats, B, M, w.D0);
+  k_patch_mean<<<blocks_for(B * kF, 256), 256, 0, s>>>(w.Y4, B, n, w.feats);
+  k_decoder_input<<<blocks_for(Rd, 256), 256, 0, s>>>(training_pts, w.feats, B, M, w.D0);
   const float* H = w.D0;
   int64_t din = kDin;
   for (int l = 0; l < 4; ++l) {
@@ -485,9 +480,9 @@ static int backward(hipStream_t s, const Layout& L, const float* params, float* 
       BNV_TRY(gemm(s, dG, kH, 1, params + L.geo_w[0] + 9, kDin, 1, w.dfrows, kF, Rd, kF, kH, nullptr, 0, nullptr, 0));
     }
   }
-  k_dfeats<<<blocks256(B * kF), 256, 0, s>>>(w.dfrows, w.feats, B, M, w.dfeats);
+  k_dfeats<<<blocks_for(B * kF, 256), 256, 0, s>>>(w.dfrows, w.feats, B, M, w.dfeats);
   // encoder: mean, then (BatchNorm, conv) for layers 4 .. 1
-  k_mean_backward<<<blocks256(Re * kF), 256, 0, s>>>(w.dfeats, B, n, w.dE[0]);
+  k_mean_backward<<<blocks_for(Re * kF, 256), 256, 0, s>>>(w.dfeats, B, n, w.dE[0]);
   const int cin[4] = {kNin, kC, kC, kC}, cout[4] = {kC, kC, kC, kF};
   cur = 0;
   for (int l = 3; l >= 0; --l) {
@@ -496,7 +491,7 @@ static int backward(hipStream_t s, const Layout& L, const float* params, float* 
     float* dY = w.dE[cur];
     float* dZ = w.dE[cur ^ 1];
     BNV_TRY(colsum(s, dY, w.Z[l], Re, C, nullptr, 2, w.part, grads + L.bn_b[l], grads + L.bn_w[l]));
-    k_bn_backward<<<blocks256(Re * C), 256, 0, s>>>(dY, w.Z[l], Re, C, grads + L.bn_b[l], grads + L.bn_w[l], rstd,
+    k_bn_backward<<<blocks_for(Re * C, 256), 256, 0, s>>>(dY, w.Z[l], Re, C, grads + L.bn_b[l], grads + L.bn_w[l], rstd,
                                                     params + L.bn_w[l], dZ);
     // conv bias: sum_r dz = (rstd gamma) (sum_dy - R mean_dy - sum_xhat mean_dyxh) = 0 exactly, since the batch mean
     // centres xhat.  Written as the exact 0: summing the rounded dz leaves ~1e-6 of the weight gradient, which Adam
@@ -537,17 +532,16 @@ int bnv_train_step(float* params, float* grads, float* adam_m, float* adam_v, fl
     return BNV_ERR_INVALID_ARGUMENT;
   if (!params || !grads || !adam_m || !adam_v || !running || !input_pts || !training_pts || !gt || !loss_out)
     return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < layout_ws(B, n, M, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  Ws w;
+  if (!workspace || ws_bytes < layout_ws(B, n, M, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
   if (bnv::g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   hipStream_t s = (hipStream_t)stream;
   const Layout L = make_layout();
-  Ws w;
-  layout_ws(B, n, M, (char*)workspace, &w);
   BNV_TRY(forward(s, L, params, running, input_pts, training_pts, gt, B, n, M, 1, w, loss_out));
   BNV_TRY(backward(s, L, params, grads, B, n, M, w));
   // bias corrections in double on the host, like torch's python-float step_size / bias_correction2 ** 0.5
   const double bc1 = 1.0 - pow((double)beta1, (double)adam_step), bc2 = 1.0 - pow((double)beta2, (double)adam_step);
-  k_adam<<<blocks256(L.total), 256, 0, s>>>(params, grads, adam_m, adam_v, L.total, beta1, beta2, eps,
+  k_adam<<<bnv::blocks_for(L.total, 256), 256, 0, s>>>(params, grads, adam_m, adam_v, L.total, beta1, beta2, eps,
                                             (float)((double)lr / bc1), (float)sqrt(bc2));
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -558,10 +552,9 @@ int bnv_train_eval_loss(const float* params, const float* running, const float* 
                         size_t ws_bytes, bnv_stream_t stream) {
   if (!shape_ok(B, n, M)) return BNV_ERR_INVALID_ARGUMENT;
   if (!params || !running || !input_pts || !training_pts || !gt || !loss_out) return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < layout_ws(B, n, M, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  if (bnv::g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   Ws w;
-  layout_ws(B, n, M, (char*)workspace, &w);
+  if (!workspace || ws_bytes < layout_ws(B, n, M, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  if (bnv::g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   return forward((hipStream_t)stream, make_layout(), params, const_cast<float*>(running), input_pts, training_pts, gt,
                  B, n, M, 0, w, loss_out);
 }

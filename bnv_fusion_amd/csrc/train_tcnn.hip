@@ -39,6 +39,7 @@
 #include <math.h>
 
 #include "bnv_common.hpp"
+#include "workspace.hpp"
 #include "tcnn_mlp.hpp"
 
 namespace bnv {
@@ -458,7 +459,6 @@ __global__ void k_tcnn_adam(float* __restrict__ p, const float* __restrict__ g, 
 
 // ---- host side ----
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline unsigned blocks256(int64_t n) { return (unsigned)cdiv(n, 256); }
 
 static bool shape_ok(int64_t B, int64_t n, int64_t M) {
   return B >= 1 && n >= 1 && n <= kMaxN && M >= 1 && B <= (1LL << 24) && M <= (1LL << 24) && B * M <= (1LL << 24);
@@ -502,27 +502,22 @@ static int64_t image_halves(const Net& N, int64_t T) {
 static size_t layout_ws(int64_t B, int n, int64_t M, char* base, Ws* w) {
   const int64_t Re = B * n, Rd = B * M, Te = cdiv(Re, 32), Td = cdiv(Rd, 32);
   const Net E = make_net(16), D = make_net(32);
-  size_t off = 0;
-  auto take = [&](int64_t bytes) -> char* {
-    char* p = base ? base + off : nullptr;
-    off += (size_t)cdiv(bytes, 256) * 256;
-    return p;
-  };
+  Carver c(base);
   Ws t;
-  t.img_e = (_Float16*)take(2 * (fwd_halves(1) + kBwdHalves));
-  t.img_d = (_Float16*)take(2 * (fwd_halves(2) + kBwdHalves));
-  t.Y = (float*)take(4 * Re * kF);
-  t.feats = (float*)take(4 * B * kF);
-  t.egrad = (float*)take(4 * B * kF);
-  t.dfrows = (float*)take(4 * Rd * kF);
-  t.ltile = (float*)take(4 * Td);
+  t.img_e = c.take<_Float16>(fwd_halves(1) + kBwdHalves);
+  t.img_d = c.take<_Float16>(fwd_halves(2) + kBwdHalves);
+  t.Y = c.take<float>(Re * kF);
+  t.feats = c.take<float>(B * kF);
+  t.egrad = c.take<float>(B * kF);
+  t.dfrows = c.take<float>(Rd * kF);
+  t.ltile = c.take<float>(Td);
   const int64_t ie = image_halves(E, Te), id = image_halves(D, Td);
-  t.act = (_Float16*)take(2 * (ie > id ? ie : id));
-  t.part = (float*)take(4 * kMaxChunks * (E.P > D.P ? E.P : D.P));   // cdiv(T, tiles_per_chunk(T)) <= kMaxChunks
-  t.st = (float*)take(4 * 4);
-  t.bytes = off;
+  t.act = c.take<_Float16>(ie > id ? ie : id);
+  t.part = c.take<float>(kMaxChunks * (E.P > D.P ? E.P : D.P));   // cdiv(T, tiles_per_chunk(T)) <= kMaxChunks
+  t.st = c.take<float>(4);
+  t.bytes = c.bytes();
   if (w) *w = t;
-  return off;
+  return c.bytes();
 }
 
 // image pointers of one network inside the act region
@@ -579,7 +574,7 @@ static int weight_grads(hipStream_t s, const Ws& w, int nin0, int64_t T, float s
   d.P = N.P;
   const int64_t S = cdiv(T, d.tpc);
   k_tcnn_dw<<<dim3((unsigned)nb, (unsigned)S), 64, 0, s>>>(d);
-  k_tcnn_sum<<<blocks256(N.P), 256, 0, s>>>(w.part, S, N.P, scale, grads);
+  k_tcnn_sum<<<blocks_for(N.P, 256), 256, 0, s>>>(w.part, S, N.P, scale, grads);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -587,10 +582,10 @@ static int weight_grads(hipStream_t s, const Ws& w, int nin0, int64_t T, float s
 // pack, encoder forward, patch means
 static int encode(hipStream_t s, const float* params, const float* input_pts, int64_t B, int n, const Ws& w) {
   const int64_t tot = fwd_halves(1) + fwd_halves(2) + 2 * kBwdHalves;
-  k_tcnn_pack<<<blocks256(tot), 256, 0, s>>>(params, w.img_e, w.img_d);
+  k_tcnn_pack<<<blocks_for(tot, 256), 256, 0, s>>>(params, w.img_e, w.img_d);
   const TileArgs a = tile_args(w, 0, B * n, input_pts, n, nullptr, nullptr, 0);
-  k_tcnn_tile<0, 0><<<(unsigned)cdiv(a.T, 4), 256, 0, s>>>(a);
-  k_tcnn_patch_mean<<<blocks256(B * kF), 256, 0, s>>>(w.Y, B, n, w.feats);
+  k_tcnn_tile<0, 0><<<blocks_for(a.T, 4), 256, 0, s>>>(a);
+  k_tcnn_patch_mean<<<blocks_for(B * kF, 256), 256, 0, s>>>(w.Y, B, n, w.feats);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -618,28 +613,27 @@ int bnv_train_tcnn_step(float* params, float* grads, float* adam_m, float* adam_
     return BNV_ERR_INVALID_ARGUMENT;
   if (!params || !grads || !adam_m || !adam_v || !adam_step || !input_pts || !training_pts || !gt || !loss_out)
     return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < layout_ws(B, n, M, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  Ws w;
+  if (!workspace || ws_bytes < layout_ws(B, n, M, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
   if (bnv::g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   hipStream_t s = (hipStream_t)stream;
-  Ws w;
-  layout_ws(B, n, M, (char*)workspace, &w);
   const int64_t Re = B * n, Rd = B * M;
   BNV_TRY(encode(s, params, input_pts, B, n, w));
   // decoder: forward, loss partials, backward to the feature columns; its weight gradients
   TileArgs d = tile_args(w, 1, Rd, nullptr, n, training_pts, gt, M);
   d.ltile = w.ltile;
-  k_tcnn_tile<1, 1><<<(unsigned)cdiv(d.T, 4), 256, 0, s>>>(d);
+  k_tcnn_tile<1, 1><<<bnv::blocks_for(d.T, 4), 256, 0, s>>>(d);
   BNV_LAUNCH_CHECK();
   BNV_TRY(weight_grads(s, w, 32, d.T, 1.0f / (float)Rd, grads + kEncParams));
   // encoder: d feats, then forward again and backward; its weight gradients
-  k_tcnn_dfeats<<<blocks256(B * kF), 256, 0, s>>>(w.dfrows, w.feats, B, M, w.egrad);
+  k_tcnn_dfeats<<<bnv::blocks_for(B * kF, 256), 256, 0, s>>>(w.dfrows, w.feats, B, M, w.egrad);
   const TileArgs e = tile_args(w, 0, Re, input_pts, n, nullptr, nullptr, 0);
-  k_tcnn_tile<0, 1><<<(unsigned)cdiv(e.T, 4), 256, 0, s>>>(e);
+  k_tcnn_tile<0, 1><<<bnv::blocks_for(e.T, 4), 256, 0, s>>>(e);
   BNV_LAUNCH_CHECK();
   BNV_TRY(weight_grads(s, w, 16, e.T, 1.0f / (float)Re, grads));
   k_tcnn_loss<<<1, kLossThreads, 0, s>>>(w.ltile, d.T, Rd, w.feats, B, grads, 1, lr, beta1, beta2, adam_step, w.st,
                                          loss_out);
-  k_tcnn_adam<<<blocks256(kParams), 256, 0, s>>>(params, grads, adam_m, adam_v, kParams, beta1, beta2, eps, w.st);
+  k_tcnn_adam<<<bnv::blocks_for(kParams, 256), 256, 0, s>>>(params, grads, adam_m, adam_v, kParams, beta1, beta2, eps, w.st);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -649,15 +643,14 @@ int bnv_train_tcnn_eval_loss(const float* params, const float* input_pts, const 
                              bnv_stream_t stream) {
   if (!shape_ok(B, n, M)) return BNV_ERR_INVALID_ARGUMENT;
   if (!params || !input_pts || !training_pts || !gt || !loss_out) return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < layout_ws(B, n, M, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  Ws w;
+  if (!workspace || ws_bytes < layout_ws(B, n, M, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
   if (bnv::g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   hipStream_t s = (hipStream_t)stream;
-  Ws w;
-  layout_ws(B, n, M, (char*)workspace, &w);
   BNV_TRY(encode(s, params, input_pts, B, n, w));
   TileArgs d = tile_args(w, 1, B * M, nullptr, n, training_pts, gt, M);
   d.ltile = w.ltile;
-  k_tcnn_tile<1, 0><<<(unsigned)cdiv(d.T, 4), 256, 0, s>>>(d);
+  k_tcnn_tile<1, 0><<<bnv::blocks_for(d.T, 4), 256, 0, s>>>(d);
   k_tcnn_loss<<<1, kLossThreads, 0, s>>>(w.ltile, d.T, B * M, w.feats, B, nullptr, 0, 0.0f, 0.0f, 0.0f, nullptr,
                                          nullptr, loss_out);
   BNV_LAUNCH_CHECK();
@@ -669,15 +662,14 @@ int bnv_train_tcnn_forward(const float* params, const float* input_pts, const fl
                            bnv_stream_t stream) {
   if (!shape_ok(B, n, M)) return BNV_ERR_INVALID_ARGUMENT;
   if (!params || !input_pts || !training_pts || !feats || !pred) return BNV_ERR_INVALID_ARGUMENT;
-  if (!workspace || ws_bytes < layout_ws(B, n, M, nullptr, nullptr)) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  Ws w;
+  if (!workspace || ws_bytes < layout_ws(B, n, M, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
   if (bnv::g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   hipStream_t s = (hipStream_t)stream;
-  Ws w;
-  layout_ws(B, n, M, (char*)workspace, &w);
   BNV_TRY(encode(s, params, input_pts, B, n, w));
   TileArgs d = tile_args(w, 1, B * M, nullptr, n, training_pts, nullptr, M);
   d.pred = pred;
-  k_tcnn_tile<1, 0><<<(unsigned)cdiv(d.T, 4), 256, 0, s>>>(d);
+  k_tcnn_tile<1, 0><<<bnv::blocks_for(d.T, 4), 256, 0, s>>>(d);
   BNV_HIP_CHECK(hipMemcpyAsync(feats, w.feats, sizeof(float) * B * kF, hipMemcpyDeviceToDevice, s));
   BNV_LAUNCH_CHECK();
   return BNV_OK;

@@ -7,6 +7,10 @@
 //
 // All kernels are HBM/L2-latency bound gather/scatter: one thread per key, 64-B payload rows.
 #include "bnv_common.hpp"
+#include "scan.hpp"
+#include "shard.hpp"
+#include "volume_keys.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 
@@ -29,33 +33,19 @@ struct VolWs {
 // the words are epoch-tagged and never cleared, and a stale slot index in their place could pass for a published
 // prefix of the current epoch (the workspace is shared by insert / integrate / integrate_batch calls of any size).
 // n keys take >= 8 bytes of workspace, i.e. ws_bytes / 2048 + 2 words cover every tile count a call can have.
-static size_t vol_tile_bytes(size_t ws_bytes) { return ((ws_bytes / 2048 + 2) * 8 + 255) / 256 * 256; }
-
 static size_t vol_ws_layout(int64_t n, char* base, size_t ws_bytes, VolWs* ws) {
   if (n < 1) n = 1;
-  const int64_t nb = (n + kVolTile - 1) / kVolTile;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off = (off + bytes + 255) / 256 * 256;
-    return p;
-  };
-  char* d = take(256);   // control words first: their offsets do not depend on n
-  char* t = take(vol_tile_bytes(ws_bytes));
-  char* a = take(n * 4);
-  char* b = take(n * 4);
-  char* c = take((nb + 1) * 4);
-  char* e = take(((n + 255) / 256 + 1) * 4);
-  if (ws) {
-    ws->tile_state = (uint64_t*)t;
-    ws->slot_of = (int32_t*)a;
-    ws->is_new = (int32_t*)b;
-    ws->block_sums = (uint32_t*)c;
-    ws->block_new = (uint32_t*)e;
-    ws->total_new = (int32_t*)d;
-    ws->error = nullptr;   // set by the entry points: the word behind the volume's row counter
-  }
-  return off;
+  Carver c(base);
+  VolWs t;
+  t.total_new = c.take<int32_t>(64);   // control words first: their offsets do not depend on n
+  t.tile_state = c.take<uint64_t>(ws_bytes / 2048 + 2);
+  t.slot_of = c.take<int32_t>(n);
+  t.is_new = c.take<int32_t>(n);
+  t.block_sums = c.take<uint32_t>((n + kVolTile - 1) / kVolTile + 1);
+  t.block_new = c.take<uint32_t>((n + 255) / 256 + 1);
+  t.error = nullptr;   // set by the entry points: the word behind the volume's row counter
+  if (ws) *ws = t;
+  return c.bytes();
 }
 
 __global__ __launch_bounds__(256) void k_vol_clear(uint64_t* __restrict__ slot_keys,
@@ -143,21 +133,6 @@ __global__ __launch_bounds__(kVolThreads) void k_vol_scan_partial(const int32_t*
   uint32_t total;
   block_exclusive_scan<kVolThreads>(s, wave_tot, &total);
   if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void k_vol_scan_top(uint32_t* __restrict__ block_sums, int n_blocks,
-                                                       int32_t* __restrict__ total_out) {
-  __shared__ uint32_t wave_tot[16];
-  uint32_t carry = 0;
-  for (int base = 0; base < n_blocks; base += 1024) {
-    const int i = base + threadIdx.x;
-    const uint32_t val = (i < n_blocks) ? block_sums[i] : 0;
-    uint32_t total;
-    const uint32_t ex = block_exclusive_scan<1024>(val, wave_tot, &total);
-    if (i < n_blocks) block_sums[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *total_out = (int32_t)carry;
 }
 
 // assigns rows to the created slots in batch order: row = n_rows + (number of created keys before i)
@@ -598,15 +573,14 @@ static bool vol_ok(const bnv_volume_t* v) {
 
 static int vol_upsert_rows(const bnv_volume_t& v, const int64_t* coords, int64_t n, const int32_t* n_dev,
                            const VolWs& ws, hipStream_t stream) {
-  const int nbt = (int)((n + kVolTile - 1) / kVolTile);
-  const unsigned nb256 = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(k_vol_probe_insert, dim3(nb256), dim3(256), 0, stream, v, coords, n, n_dev, ws.slot_of,
+  const int nbt = (int)blocks_for(n, kVolTile);
+  hipLaunchKernelGGL(k_vol_probe_insert, dim3(blocks_for(n, 256)), dim3(256), 0, stream, v, coords, n, n_dev, ws.slot_of,
                      ws.is_new, ws.error);
   BNV_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_vol_scan_partial, dim3(nbt), dim3(kVolThreads), 0, stream, ws.is_new, n, n_dev,
                      ws.block_sums);
   BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_vol_scan_top, dim3(1), dim3(1024), 0, stream, ws.block_sums, nbt, ws.total_new);
+  hipLaunchKernelGGL(k_scan_top<1024>, dim3(1), dim3(1024), 0, stream, ws.block_sums, nbt, ws.total_new);
   BNV_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_vol_assign_rows, dim3(nbt), dim3(kVolThreads), 0, stream, v, coords, n, n_dev,
                      ws.slot_of, ws.is_new, ws.block_sums, ws.error);
@@ -636,7 +610,7 @@ int bnv_volume_clear(const bnv_volume_t* vol, bnv_stream_t stream) {
     const size_t nvox = (size_t)vol->brick_dims[0] * vol->brick_dims[1] * vol->brick_dims[2];
     BNV_HIP_CHECK(hipMemsetAsync(vol->brick, 0xff, nvox * 4, (hipStream_t)stream));   // every word -1
   }
-  hipLaunchKernelGGL(k_vol_clear, dim3((unsigned)((vol->n_slots + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_vol_clear, dim3(blocks_for(vol->n_slots, 256)), dim3(256), 0, (hipStream_t)stream,
                      vol->slot_keys, vol->slot_rows, vol->n_slots, vol->n_rows);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -644,10 +618,10 @@ int bnv_volume_clear(const bnv_volume_t* vol, bnv_stream_t stream) {
 
 int bnv_volume_rehash(const bnv_volume_t* vol, bnv_stream_t stream) {
   if (!vol_ok(vol)) return BNV_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_vol_clear, dim3((unsigned)((vol->n_slots + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_vol_clear, dim3(blocks_for(vol->n_slots, 256)), dim3(256), 0, (hipStream_t)stream,
                      vol->slot_keys, vol->slot_rows, vol->n_slots, (int32_t*)nullptr);
   BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_vol_rehash, dim3((unsigned)((vol->row_capacity + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(k_vol_rehash, dim3(blocks_for(vol->row_capacity, 256)), dim3(256), 0,
                      (hipStream_t)stream, *vol, vol->n_rows + 1);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -663,7 +637,7 @@ int bnv_volume_integrate(const bnv_volume_t* vol, const int64_t* coords, const f
   if (vol_ws_layout(n, (char*)ws_ptr, ws_bytes, &ws) > ws_bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
   ws.error = vol->n_rows + 1;
   hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(k_vol_integrate<false>, dim3((unsigned)((n + kIntThreads - 1) / kIntThreads)), dim3(kIntThreads), 0, stream, *vol, coords, feats, pcounts, n, n_dev,
+  hipLaunchKernelGGL(k_vol_integrate<false>, dim3(blocks_for(n, kIntThreads)), dim3(kIntThreads), 0, stream, *vol, coords, feats, pcounts, n, n_dev,
                      ws.tile_state, next_epoch(), ws.error, IntegrateExtras{});
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -691,7 +665,7 @@ int bnv_volume_integrate_frame(const bnv_volume_t* vol, const int64_t* coords, c
   if (vol_ws_layout(n, (char*)ws_ptr, ws_bytes, &ws) > ws_bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
   ws.error = vol->n_rows + 1;
   hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(k_vol_integrate<true>, dim3((unsigned)((n + kIntThreads - 1) / kIntThreads)), dim3(kIntThreads), 0, stream, *vol, coords, feats, pcounts, n, n_dev,
+  hipLaunchKernelGGL(k_vol_integrate<true>, dim3(blocks_for(n, kIntThreads)), dim3(kIntThreads), 0, stream, *vol, coords, feats, pcounts, n, n_dev,
                      ws.tile_state, next_epoch(), ws.error, X);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -745,7 +719,7 @@ int bnv_volume_insert(const bnv_volume_t* vol, const int64_t* coords, const floa
   hipStream_t stream = (hipStream_t)stream_;
   const int rc = vol_upsert_rows(*vol, coords, n, nullptr, ws, stream);
   if (rc != BNV_OK) return rc;
-  hipLaunchKernelGGL(k_vol_insert_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *vol, feats,
+  hipLaunchKernelGGL(k_vol_insert_apply, dim3(blocks_for(n, 256)), dim3(256), 0, stream, *vol, feats,
                      weights, num_hits, n, (const int32_t*)nullptr, ws.slot_of);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -757,7 +731,7 @@ int bnv_volume_query(const bnv_volume_t* vol, const int64_t* coords, int64_t n, 
   if (!vol_ok(vol) || n < 0) return BNV_ERR_INVALID_ARGUMENT;
   if (n == 0) return BNV_OK;
   if (!coords || !features || !weights || !num_hits) return BNV_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_vol_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *vol,
+  hipLaunchKernelGGL(k_vol_query, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *vol,
                      coords, n, features, weights, num_hits, row_limit, out_feats, out_weights, out_hits, out_rows);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
@@ -767,7 +741,7 @@ int bnv_volume_count_optim(const bnv_volume_t* vol, const int64_t* coords, int64
                            int64_t row_limit, int32_t* stamp, int32_t epoch, bnv_stream_t stream) {
   if (!vol_ok(vol) || n < 0 || !stamp || !weights) return BNV_ERR_INVALID_ARGUMENT;
   if (n == 0) return BNV_OK;
-  hipLaunchKernelGGL(k_vol_count_optim, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_vol_count_optim, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
                      *vol, coords, n, weights, row_limit, stamp, epoch);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
