@@ -8,50 +8,6 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BNV_FUSION_LIB") or os.path.join(_HERE, "libbnv_fusion_hip.so")
 
-# every symbol include/bnv_fusion.h declares
-SYMBOLS = [
-    "bnv_init", "bnv_num_compute_units", "bnv_status_string", "bnv_last_hip_error",
-    "bnv_encode_workspace_bytes", "bnv_encode_workspace_reset", "bnv_pointnet_pack_floats",
-    "bnv_sdfmlp_pack_floats", "bnv_encode_pointcloud", "bnv_encode_begin", "bnv_encode_begin_depth",
-    "bnv_encode_finish", "bnv_encode_finish_image", "bnv_encode_shard_counts_offset", "bnv_shard_pack", "bnv_shard_install", "bnv_voxelize_pairs",
-    "bnv_volume_clear", "bnv_volume_rehash", "bnv_volume_workspace_bytes", "bnv_volume_integrate",
-    "bnv_volume_integrate_batch",
-    "bnv_volume_insert", "bnv_volume_query", "bnv_volume_count_optim",
-    "bnv_depth_workspace_bytes", "bnv_depth_to_points", "bnv_depth_to_points_padded", "bnv_tsdf_integrate", "bnv_tsdf_integrate_u16", "bnv_tsdf_integrate_batch_u16", "bnv_set_mlp_mode", "bnv_get_mlp_mode", "bnv_set_option", "bnv_profile_enable", "bnv_profile_read", "bnv_probe_mfma_rate", "bnv_probe_spin", "bnv_decode_lattice_count_offset",
-    "bnv_decode_lattice_table_offset", "bnv_decode_lattice_list_offset", "bnv_lattice_neighbors",
-    "bnv_lattice_mark", "bnv_lattice_table", "bnv_lattice_blend",
-    "bnv_decode_pts", "bnv_sdfmlp_bwd_pack_floats", "bnv_sdfmlp_tcnn_bwd_pack_floats", "bnv_decode_pts_backward",
-    "bnv_png_unfilter", "bnv_mc_count", "bnv_mc_emit", "bnv_mc_count_indexed", "bnv_mc_emit_indexed", "bnv_ray_samples", "bnv_ray_loss", "bnv_volume_count_optim_pts",
-    "bnv_volume_count_optim_splits", "bnv_volume_apply_split_counts", "bnv_decode_pts_splits",
-    "bnv_decode_pts_backward_splits", "bnv_ray_loss_splits", "bnv_optim_step",
-    "bnv_decode_lattice_workspace_bytes", "bnv_decode_lattice", "bnv_decode_dense",
-    "bnv_shard_install_reset", "bnv_volume_integrate_frame", "bnv_decode_lattice_stamped", "bnv_readback_words",
-    "bnv_decode_dense_mode", "bnv_frame_pipe_set_mlp_mode", "bnv_decode_lattice_stamped_tables",
-    "bnv_encode_finish_image_wg", "bnv_encode_finish_image_parts", "bnv_shard_state_bytes", "bnv_shard_state_loads_offset", "bnv_shard_state_table_offset",
-    "bnv_frame_pipe_create", "bnv_frame_pipe_destroy", "bnv_frame_begin_depth", "bnv_frame_begin_points",
-    "bnv_frame_upsert", "bnv_frame_bound", "bnv_frame_finish", "bnv_frame_result", "bnv_frame_ready", "bnv_frame_pipe_timeline_enable", "bnv_frame_timeline",
-    "bnv_frame_side_depth", "bnv_frame_cancel", "bnv_frame_pipe_forget_workspaces", "bnv_shard_state_configure",
-    "bnv_mesh_sample_surface_workspace", "bnv_mesh_sample_surface", "bnv_nn_workspace_bytes", "bnv_nn_query",
-    "bnv_tsdf_mesh_workspace_bytes", "bnv_tsdf_mesh_count", "bnv_tsdf_mesh_emit",
-    "bnv_render_workspace_bytes", "bnv_render_depth", "bnv_tsdf_render_depth",
-    "bnv_mesh_post_workspace_bytes", "bnv_mesh_post_process",
-    "bnv_mesh_components_workspace_bytes", "bnv_mesh_components", "bnv_mesh_filter_components",
-    "bnv_depth_to_points_gated", "bnv_depth_to_points_padded_gated", "bnv_encode_begin_depth_gated",
-    "bnv_frame_begin_depth_gated",
-    "bnv_train_param_floats", "bnv_train_running_floats", "bnv_train_workspace_bytes", "bnv_train_step",
-    "bnv_train_eval_loss",
-    "bnv_train_tcnn_param_floats", "bnv_train_tcnn_workspace_bytes", "bnv_train_tcnn_step", "bnv_train_tcnn_eval_loss",
-    "bnv_train_tcnn_forward",
-    "bnv_mesh_sdf_workspace_bytes", "bnv_mesh_sdf_build", "bnv_mesh_sdf_query",
-    "bnv_mesh_ray_workspace_bytes", "bnv_mesh_ray_cast", "bnv_mesh_render_depth", "bnv_depth_sensor",
-    "bnv_icp_workspace_bytes", "bnv_icp_align",
-    "bnv_depth_filter",
-    "bnv_mesh_normals_workspace_bytes", "bnv_mesh_vertex_normals", "bnv_mesh_color_workspace_bytes",
-    "bnv_mesh_color_begin", "bnv_mesh_color_accumulate", "bnv_mesh_color_resolve",
-    "bnv_plan_workspace_bytes", "bnv_plan_workspace_reset", "bnv_plan_extent", "bnv_plan_count",
-]
-
-
 class Grid(C.Structure):
     _fields_ = [("bound_min", C.c_float * 3), ("bound_lo", C.c_float * 3), ("bound_hi", C.c_float * 3),
                 ("voxel_size", C.c_float), ("n_xyz", C.c_int32 * 3), ("min_pts_in_grid", C.c_int32),
@@ -109,6 +65,176 @@ class MeshColorFrame(C.Structure):      # bnv_mesh_color_frame_t
                 ("T_cw", C.c_double * 12), ("center", C.c_double * 3)]
 
 
+vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
+# every function include/bnv_fusion.h declares: name -> (restype, argtypes)
+SIGNATURES = {
+    "bnv_init": (C.c_int, [C.c_int]),
+    "bnv_num_compute_units": (C.c_int, []),
+    "bnv_status_string": (C.c_char_p, [C.c_int]),
+    "bnv_last_hip_error": (C.c_int, []),
+    "bnv_encode_workspace_bytes": (sz, [i64, C.POINTER(i32)]),
+    "bnv_pointnet_pack_floats": (sz, []),
+    "bnv_sdfmlp_pack_floats": (sz, []),
+    "bnv_encode_pointcloud": (C.c_int, [vp, i64, C.POINTER(Grid), vp, vp, sz, i64, vp, vp, vp, vp, i64, C.c_int,
+                                        vp, vp]),
+    "bnv_encode_begin": (C.c_int, [vp, i64, C.POINTER(Grid), vp, sz, i64, vp]),
+    "bnv_encode_begin_depth": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double), C.c_double, vp, C.c_int, C.POINTER(Grid), vp,
+                                         sz, i64, vp, vp]),
+    "bnv_encode_finish": (C.c_int, [vp, i64, C.c_int, C.POINTER(Grid), vp, vp, sz, i64, vp, vp, vp, vp, i64,
+                                    C.c_int, vp, vp]),
+    "bnv_encode_shard_counts_offset": (sz, []),
+    "bnv_shard_pack": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, vp, vp, i64, vp]),
+    "bnv_voxelize_pairs": (C.c_int, [vp, i64, C.POINTER(Grid), vp, vp, vp, vp, vp]),
+    "bnv_volume_clear": (C.c_int, [C.POINTER(Volume), vp]),
+    "bnv_volume_rehash": (C.c_int, [C.POINTER(Volume), vp]),
+    "bnv_volume_workspace_bytes": (sz, [i64]),
+    "bnv_volume_integrate_batch": (C.c_int, [C.POINTER(Volume), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "bnv_volume_insert": (C.c_int, [C.POINTER(Volume), vp, vp, vp, vp, i64, vp, sz, vp]),
+    "bnv_volume_query": (C.c_int, [C.POINTER(Volume), vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
+    "bnv_volume_count_optim": (C.c_int, [C.POINTER(Volume), vp, i64, vp, i64, vp, i32, vp]),
+    "bnv_sdfmlp_bwd_pack_floats": (sz, []),
+    "bnv_sdfmlp_tcnn_bwd_pack_floats": (sz, []),
+    "bnv_png_unfilter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
+    "bnv_ray_samples": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp,
+                                  C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp]),
+    "bnv_ray_loss": (C.c_int, [vp, vp, vp, vp, i64, i64, vp, vp, vp]),
+    "bnv_volume_count_optim_splits": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, C.c_int, i64, i64, vp, vp]),
+    "bnv_volume_apply_split_counts": (C.c_int, [vp, vp, i64, vp]),
+    "bnv_decode_pts": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, i64, C.c_int,
+                                 C.POINTER(SdfDelta), vp, i64, vp, vp]),
+    "bnv_decode_pts_backward": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, vp, i64,
+                                          C.c_int, vp, i64, vp, vp, vp]),
+    "bnv_optim_step": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, vp, i64, C.c_int,
+                                 C.POINTER(SdfDelta), vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "bnv_volume_count_optim_pts": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, C.c_int, vp, i64, vp, i32,
+                                             vp]),
+    "bnv_mc_count": (C.c_int, [vp, i64, vp, C.c_float, vp, vp, vp]),
+    "bnv_mc_emit": (C.c_int, [vp, vp, i64, vp, C.c_float, C.c_float, C.POINTER(C.c_float), vp, vp, vp, vp]),
+    "bnv_mc_count_indexed": (C.c_int, [vp, i64, vp, C.c_float, vp, vp, vp, vp]),
+    "bnv_mc_emit_indexed": (C.c_int, [vp, vp, i64, vp, C.c_float, C.c_float, C.POINTER(C.c_float), vp, vp, vp, vp, vp,
+                                      vp]),
+    "bnv_decode_lattice_workspace_bytes": (sz, [i64, i64]),
+    "bnv_decode_lattice_count_offset": (sz, [i64]),
+    "bnv_decode_lattice_table_offset": (sz, [i64]),
+    "bnv_decode_lattice_list_offset": (sz, [i64, i64]),
+    "bnv_lattice_neighbors": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, vp, i64, vp, vp, C.c_int, vp,
+                                        sz, i32, vp]),
+    "bnv_lattice_mark": (C.c_int, [C.POINTER(Volume), i64, vp, vp, sz, i32, vp]),
+    "bnv_lattice_table": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, C.c_int, vp, sz, vp]),
+    "bnv_lattice_blend": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, vp, C.POINTER(SdfDelta), vp, sz,
+                                    vp, vp]),
+    "bnv_depth_workspace_bytes": (sz, [C.c_int, C.c_int]),
+    "bnv_depth_to_points": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.c_double, vp, C.c_int, C.c_int, vp, sz, vp, vp,
+                                      vp]),
+    "bnv_tsdf_integrate": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float, vp,
+                                     C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float,
+                                     vp, vp]),
+    "bnv_tsdf_integrate_batch_u16": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float,
+                                               C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                               C.POINTER(C.c_float), C.c_float, C.c_float, vp]),
+    "bnv_set_mlp_mode": (C.c_int, [C.c_int]),
+    "bnv_get_mlp_mode": (C.c_int, []),
+    "bnv_set_option": (C.c_int, [C.c_char_p, C.c_int]),
+    "bnv_profile_enable": (C.c_int, [C.c_int]),
+    "bnv_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(i64)]),
+    "bnv_probe_mfma_rate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bnv_probe_spin": (C.c_int, [C.c_int, i64, vp]),
+    "bnv_decode_lattice": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, i64, vp,
+                                     C.POINTER(SdfDelta), vp, sz, i32, C.c_int, vp, vp]),
+    "bnv_shard_state_bytes": (sz, [C.POINTER(i32), i32]),
+    "bnv_shard_state_loads_offset": (sz, []),
+    "bnv_shard_state_table_offset": (sz, []),
+    "bnv_decode_dense": (C.c_int, [vp, vp, C.POINTER(i32), C.c_float, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
+    "bnv_frame_pipe_set_mlp_mode": (C.c_int, [vp, i32]),
+    "bnv_shard_install": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, C.c_int, i64, vp, vp]),
+    "bnv_volume_integrate": (C.c_int, [C.POINTER(Volume), vp, vp, vp, i64, vp, vp, sz,
+                                       C.POINTER(IntegrateExtras), vp]),
+    "bnv_readback_words": (C.c_int, [vp, vp, vp, vp]),
+    "bnv_frame_pipe_create": (C.c_int, [C.POINTER(FramePipeConfig), C.POINTER(vp)]),
+    "bnv_frame_pipe_destroy": (C.c_int, [vp]),
+    "bnv_frame_begin_depth": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), vp, C.c_int, vp]),
+    "bnv_frame_begin_points": (C.c_int, [vp, C.c_int, vp, i64]),
+    "bnv_frame_upsert": (C.c_int, [vp, C.c_int, C.POINTER(Volume), vp, sz, vp, i32]),
+    "bnv_frame_bound": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),
+    "bnv_frame_finish": (C.c_int, [vp, C.c_int, C.POINTER(Volume), vp, i64, vp, C.POINTER(SdfDelta), vp, sz, i32]),
+    "bnv_frame_result": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),
+    "bnv_frame_ready": (C.c_int, [vp, C.c_int]),
+    "bnv_frame_pipe_timeline_enable": (C.c_int, [vp, C.c_int]),
+    "bnv_frame_timeline": (C.c_int, [vp, C.c_int, C.POINTER(C.c_float)]),
+    "bnv_frame_side_depth": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), vp]),
+    "bnv_frame_cancel": (C.c_int, [vp, C.c_int]),
+    "bnv_frame_pipe_forget_workspaces": (C.c_int, [vp]),
+    "bnv_shard_state_configure": (C.c_int, [vp, i32, i32, vp]),
+    "bnv_mesh_sample_surface_workspace": (C.c_int, [i64, C.POINTER(i64)]),
+    "bnv_mesh_sample_surface": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
+    "bnv_nn_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+    "bnv_nn_query": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+    "bnv_tsdf_mesh_workspace_bytes": (C.c_int, [C.POINTER(i32), C.POINTER(i64)]),
+    "bnv_tsdf_mesh_count": (C.c_int, [vp, vp, C.POINTER(i32), C.c_float, C.c_int, vp, vp, i64, vp, vp]),
+    "bnv_tsdf_mesh_emit": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float,
+                                     C.c_int, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "bnv_render_workspace_bytes": (sz, [i64, i32]),
+    "bnv_render_depth": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, C.POINTER(SdfDelta),
+                                   C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, C.c_float, C.c_float,
+                                   C.c_float, i32, vp, sz, vp, vp, C.POINTER(i64), vp]),
+    "bnv_tsdf_render_depth": (C.c_int, [vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, C.c_float, C.c_float,
+                                        C.c_float, vp, vp, vp]),
+    "bnv_mesh_post_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+    "bnv_mesh_post_process": (C.c_int, [vp, i64, vp, i64, C.c_double, vp, i64, vp, vp, vp, vp]),
+    "bnv_mesh_components_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+    "bnv_mesh_components": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "bnv_mesh_filter_components": (C.c_int, [vp, i64, vp, i64, C.c_double, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "bnv_train_param_floats": (i64, []),
+    "bnv_train_running_floats": (i64, []),
+    "bnv_train_workspace_bytes": (sz, [i64, i32, i64]),
+    "bnv_train_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, C.c_float, C.c_float, C.c_float,
+                                 C.c_float, i64, vp, vp, sz, vp]),
+    "bnv_train_eval_loss": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
+    "bnv_train_tcnn_param_floats": (i64, []),
+    "bnv_train_tcnn_workspace_bytes": (sz, [i64, i32, i64]),
+    "bnv_train_tcnn_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, C.c_float, C.c_float,
+                                      C.c_float, C.c_float, vp, vp, sz, vp]),
+    "bnv_train_tcnn_eval_loss": (C.c_int, [vp, vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
+    "bnv_train_tcnn_forward": (C.c_int, [vp, vp, vp, i64, i32, i64, vp, vp, vp, sz, vp]),
+    "bnv_mesh_sdf_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+    "bnv_mesh_sdf_build": (C.c_int, [vp, i64, vp, i64, vp, i64, vp]),
+    "bnv_mesh_sdf_query": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "bnv_mesh_ray_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+    "bnv_mesh_ray_cast": (C.c_int, [vp, i64, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+    "bnv_mesh_render_depth": (C.c_int, [vp, i64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                        C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, i64, vp]),
+    "bnv_depth_sensor": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_uint32, C.c_double, C.c_double,
+                                   C.c_double, vp, vp]),
+    "bnv_icp_workspace_bytes": (sz, [i32, C.POINTER(i32)]),
+    "bnv_icp_align": (C.c_int, [vp, C.c_int, i32, i32, C.POINTER(C.c_double), C.c_double, vp, vp, i32, i32,
+                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                C.POINTER(C.c_double), i32, C.POINTER(i32), C.c_double, C.c_double, C.c_double, vp,
+                                sz, vp, vp, vp, vp, vp]),
+    "bnv_depth_filter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, vp,
+                                   C.c_int, vp, vp]),
+    "bnv_mesh_normals_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
+    "bnv_mesh_vertex_normals": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+    "bnv_mesh_color_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
+    "bnv_mesh_color_begin": (C.c_int, [vp, i64, i64, vp]),
+    "bnv_mesh_color_accumulate": (C.c_int, [vp, vp, i64, C.POINTER(MeshColorFrame), i32, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, vp, i64, vp]),
+    "bnv_mesh_color_resolve": (C.c_int, [vp, i64, i64, C.POINTER(C.c_uint8), vp, vp, vp, vp, vp]),
+    "bnv_plan_workspace_bytes": (sz, [C.c_int, C.c_int, C.POINTER(Grid), C.c_int, i64]),
+    "bnv_plan_workspace_reset": (C.c_int, [vp, sz, C.c_int, C.c_int, C.POINTER(Grid), C.c_int, i64, vp]),
+    "bnv_plan_extent": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  C.c_double, vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int, vp,
+                                  vp]),
+    "bnv_plan_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                 C.c_double, vp, C.c_int, C.POINTER(Grid), C.c_int, i64, vp, sz, vp, vp]),
+}
+SYMBOLS = list(SIGNATURES)
+
+
 class BnvError(RuntimeError):
     pass
 
@@ -153,207 +279,9 @@ def load():
             f"{LIB_PATH} not found: build it with `python bnv_fusion_amd/csrc/build.py` "
             "(hipcc, gfx950).  bnv_fusion_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
-    sig = {
-        "bnv_init": (C.c_int, [C.c_int]),
-        "bnv_num_compute_units": (C.c_int, []),
-        "bnv_status_string": (C.c_char_p, [C.c_int]),
-        "bnv_last_hip_error": (C.c_int, []),
-        "bnv_encode_workspace_bytes": (sz, [i64, C.POINTER(i32)]),
-        "bnv_encode_workspace_reset": (C.c_int, [vp, sz, vp]),
-        "bnv_pointnet_pack_floats": (sz, []),
-        "bnv_sdfmlp_pack_floats": (sz, []),
-        "bnv_encode_pointcloud": (C.c_int, [vp, i64, C.POINTER(Grid), vp, vp, sz, i64, vp, vp, vp, vp, i64, C.c_int,
-                                            vp, vp]),
-        "bnv_encode_begin": (C.c_int, [vp, i64, C.POINTER(Grid), vp, sz, i64, vp]),
-        "bnv_encode_begin_depth": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
-                                             C.POINTER(C.c_double), C.c_double, C.POINTER(Grid), vp, sz, i64, vp, vp]),
-        "bnv_encode_begin_depth_gated": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
-                                                   C.POINTER(C.c_double), C.c_double, vp, C.c_int, C.POINTER(Grid), vp,
-                                                   sz, i64, vp, vp]),
-        "bnv_encode_finish": (C.c_int, [vp, i64, C.POINTER(Grid), vp, vp, sz, i64, vp, vp, vp, vp, i64, C.c_int,
-                                        vp, vp]),
-        "bnv_encode_finish_image": (C.c_int, [vp, i64, C.c_int, C.POINTER(Grid), vp, vp, sz, i64, vp, vp, vp, vp, i64,
-                                              C.c_int, vp, vp]),
-        "bnv_encode_shard_counts_offset": (sz, []),
-        "bnv_shard_pack": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, vp, vp, i64, vp]),
-        "bnv_shard_install": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, C.c_int, i64, vp]),
-        "bnv_voxelize_pairs": (C.c_int, [vp, i64, C.POINTER(Grid), vp, vp, vp, vp, vp]),
-        "bnv_volume_clear": (C.c_int, [C.POINTER(Volume), vp]),
-        "bnv_volume_rehash": (C.c_int, [C.POINTER(Volume), vp]),
-        "bnv_volume_workspace_bytes": (sz, [i64]),
-        "bnv_volume_integrate": (C.c_int, [C.POINTER(Volume), vp, vp, vp, i64, vp, vp, sz, vp]),
-        "bnv_volume_integrate_batch": (C.c_int, [C.POINTER(Volume), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-        "bnv_volume_insert": (C.c_int, [C.POINTER(Volume), vp, vp, vp, vp, i64, vp, sz, vp]),
-        "bnv_volume_query": (C.c_int, [C.POINTER(Volume), vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
-        "bnv_volume_count_optim": (C.c_int, [C.POINTER(Volume), vp, i64, vp, i64, vp, i32, vp]),
-        "bnv_decode_pts": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, i64, C.c_int,
-                                     C.POINTER(SdfDelta), vp, vp]),
-        "bnv_sdfmlp_bwd_pack_floats": (sz, []),
-        "bnv_sdfmlp_tcnn_bwd_pack_floats": (sz, []),
-        "bnv_decode_pts_backward": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, vp, i64,
-                                              C.c_int, vp, vp, vp]),
-        "bnv_png_unfilter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
-        "bnv_ray_samples": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp,
-                                      C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp]),
-        "bnv_ray_loss": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp]),
-        "bnv_ray_loss_splits": (C.c_int, [vp, vp, vp, vp, i64, i64, vp, vp, vp]),
-        "bnv_volume_count_optim_splits": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, C.c_int, i64, i64, vp, vp]),
-        "bnv_volume_apply_split_counts": (C.c_int, [vp, vp, i64, vp]),
-        "bnv_decode_pts_splits": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, i64, C.c_int,
-                                            C.POINTER(SdfDelta), vp, i64, vp, vp]),
-        "bnv_decode_pts_backward_splits": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, vp, i64,
-                                                     C.c_int, vp, i64, vp, vp, vp]),
-        "bnv_optim_step": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, vp, i64, C.c_int,
-                                     C.POINTER(SdfDelta), vp, i64, vp, vp, vp, vp, vp, vp, vp]),
-        "bnv_volume_count_optim_pts": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, C.c_int, vp, i64, vp, i32,
-                                                 vp]),
-        "bnv_mc_count": (C.c_int, [vp, i64, vp, C.c_float, vp, vp, vp]),
-        "bnv_mc_emit": (C.c_int, [vp, vp, i64, vp, C.c_float, C.c_float, C.POINTER(C.c_float), vp, vp, vp, vp]),
-        "bnv_mc_count_indexed": (C.c_int, [vp, i64, vp, C.c_float, vp, vp, vp, vp]),
-        "bnv_mc_emit_indexed": (C.c_int, [vp, vp, i64, vp, C.c_float, C.c_float, C.POINTER(C.c_float), vp, vp, vp, vp, vp,
-                                          vp]),
-        "bnv_decode_lattice_workspace_bytes": (sz, [i64, i64]),
-        "bnv_encode_finish_image_parts": (C.c_int, [vp, i64, C.c_int, C.POINTER(Grid), vp, vp, sz, i64, vp, vp, vp, vp, i64,
-                                                    C.c_int, vp, C.c_int, C.c_int, vp]),
-        "bnv_decode_lattice_count_offset": (sz, [i64]),
-        "bnv_decode_lattice_table_offset": (sz, [i64]),
-        "bnv_decode_lattice_list_offset": (sz, [i64, i64]),
-        "bnv_lattice_neighbors": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, vp, i64, vp, vp, C.c_int, vp,
-                                            sz, i32, vp]),
-        "bnv_lattice_mark": (C.c_int, [C.POINTER(Volume), i64, vp, vp, sz, i32, vp]),
-        "bnv_lattice_table": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, C.c_int, vp, sz, vp]),
-        "bnv_lattice_blend": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, i64, vp, C.POINTER(SdfDelta), vp, sz,
-                                        vp, vp]),
-        "bnv_depth_workspace_bytes": (sz, [C.c_int, C.c_int]),
-        "bnv_depth_to_points": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                          C.c_double, vp, sz, vp, vp, vp]),
-        "bnv_depth_to_points_padded": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                          C.c_double, vp, sz, vp, vp, vp]),
-        "bnv_depth_to_points_gated": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
-                                                C.POINTER(C.c_double), C.c_double, vp, C.c_int, vp, sz, vp, vp, vp]),
-        "bnv_depth_to_points_padded_gated": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
-                                                       C.POINTER(C.c_double), C.c_double, vp, C.c_int, vp, sz, vp, vp,
-                                                       vp]),
-        "bnv_tsdf_integrate": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float, vp, vp,
-                                         C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float,
-                                         vp, vp]),
-        "bnv_tsdf_integrate_u16": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float, vp, vp,
-                                         C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float,
-                                         vp, vp]),
-        "bnv_tsdf_integrate_batch_u16": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float,
-                                                   C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_float),
-                                                   C.POINTER(C.c_float), C.c_float, C.c_float, vp]),
-        "bnv_set_mlp_mode": (C.c_int, [C.c_int]),
-        "bnv_get_mlp_mode": (C.c_int, []),
-        "bnv_set_option": (C.c_int, [C.c_char_p, C.c_int]),
-        "bnv_profile_enable": (C.c_int, [C.c_int]),
-        "bnv_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(i64)]),
-        "bnv_probe_mfma_rate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-        "bnv_probe_spin": (C.c_int, [C.c_int, i64, vp]),
-        "bnv_decode_lattice": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, i64, vp,
-                                         C.POINTER(SdfDelta), vp, sz, i32, vp, vp]),
-        "bnv_decode_dense": (C.c_int, [vp, vp, C.POINTER(i32), C.c_float, i32, vp, vp, i64, i32, vp, vp, vp, vp]),
-        "bnv_decode_lattice_stamped_tables": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, i64, vp,
-                                                        vp, sz, i32, vp]),
-        "bnv_encode_finish_image_wg": (C.c_int, [vp, i64, C.c_int, C.POINTER(Grid), vp, vp, sz, i64, vp, vp, vp, vp, i64,
-                                                 C.c_int, vp, C.c_int, vp]),
-        "bnv_shard_state_bytes": (sz, [C.POINTER(i32), i32]),
-        "bnv_shard_state_loads_offset": (sz, []),
-        "bnv_shard_state_table_offset": (sz, []),
-        "bnv_decode_dense_mode": (C.c_int, [vp, vp, C.POINTER(i32), C.c_float, i32, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
-        "bnv_frame_pipe_set_mlp_mode": (C.c_int, [vp, i32]),
-        "bnv_shard_install_reset": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, C.c_int, i64, vp, vp]),
-        "bnv_volume_integrate_frame": (C.c_int, [C.POINTER(Volume), vp, vp, vp, i64, vp, vp, sz,
-                                                 C.POINTER(IntegrateExtras), vp]),
-        "bnv_readback_words": (C.c_int, [vp, vp, vp, vp]),
-        "bnv_decode_lattice_stamped": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, vp, i64, vp,
-                                                 C.POINTER(SdfDelta), vp, sz, i32, vp, vp]),
-        "bnv_frame_pipe_create": (C.c_int, [C.POINTER(FramePipeConfig), C.POINTER(vp)]),
-        "bnv_frame_pipe_destroy": (C.c_int, [vp]),
-        "bnv_frame_begin_depth": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
-                                            C.POINTER(C.c_double), vp]),
-        "bnv_frame_begin_depth_gated": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
-                                                  C.POINTER(C.c_double), vp, C.c_int, vp]),
-        "bnv_frame_begin_points": (C.c_int, [vp, C.c_int, vp, i64]),
-        "bnv_frame_upsert": (C.c_int, [vp, C.c_int, C.POINTER(Volume), vp, sz, vp, i32]),
-        "bnv_frame_bound": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),
-        "bnv_frame_finish": (C.c_int, [vp, C.c_int, C.POINTER(Volume), vp, i64, vp, C.POINTER(SdfDelta), vp, sz, i32]),
-        "bnv_frame_result": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),
-        "bnv_frame_ready": (C.c_int, [vp, C.c_int]),
-        "bnv_frame_pipe_timeline_enable": (C.c_int, [vp, C.c_int]),
-        "bnv_frame_timeline": (C.c_int, [vp, C.c_int, C.POINTER(C.c_float)]),
-        "bnv_frame_side_depth": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
-                                           C.POINTER(C.c_double), vp]),
-        "bnv_frame_cancel": (C.c_int, [vp, C.c_int]),
-        "bnv_frame_pipe_forget_workspaces": (C.c_int, [vp]),
-        "bnv_shard_state_configure": (C.c_int, [vp, i32, i32, vp]),
-        "bnv_mesh_sample_surface_workspace": (C.c_int, [i64, C.POINTER(i64)]),
-        "bnv_mesh_sample_surface": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
-        "bnv_nn_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
-        "bnv_nn_query": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
-        "bnv_tsdf_mesh_workspace_bytes": (C.c_int, [C.POINTER(i32), C.POINTER(i64)]),
-        "bnv_tsdf_mesh_count": (C.c_int, [vp, vp, C.POINTER(i32), C.c_float, C.c_int, vp, vp, i64, vp, vp]),
-        "bnv_tsdf_mesh_emit": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float,
-                                         C.c_int, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
-        "bnv_render_workspace_bytes": (sz, [i64, i32]),
-        "bnv_render_depth": (C.c_int, [C.POINTER(Volume), C.POINTER(Grid), vp, vp, i64, vp, C.POINTER(SdfDelta),
-                                       C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, C.c_float, C.c_float,
-                                       C.c_float, i32, vp, sz, vp, vp, C.POINTER(i64), vp]),
-        "bnv_tsdf_render_depth": (C.c_int, [vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float,
-                                            C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, C.c_float, C.c_float,
-                                            C.c_float, vp, vp, vp]),
-        "bnv_mesh_post_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
-        "bnv_mesh_post_process": (C.c_int, [vp, i64, vp, i64, C.c_double, vp, i64, vp, vp, vp, vp]),
-        "bnv_mesh_components_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
-        "bnv_mesh_components": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
-        "bnv_mesh_filter_components": (C.c_int, [vp, i64, vp, i64, C.c_double, i64, i64, vp, i64, vp, vp, vp, vp]),
-        "bnv_train_param_floats": (i64, []),
-        "bnv_train_running_floats": (i64, []),
-        "bnv_train_workspace_bytes": (sz, [i64, i32, i64]),
-        "bnv_train_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, C.c_float, C.c_float, C.c_float,
-                                     C.c_float, i64, vp, vp, sz, vp]),
-        "bnv_train_eval_loss": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
-        "bnv_train_tcnn_param_floats": (i64, []),
-        "bnv_train_tcnn_workspace_bytes": (sz, [i64, i32, i64]),
-        "bnv_train_tcnn_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, C.c_float, C.c_float,
-                                          C.c_float, C.c_float, vp, vp, sz, vp]),
-        "bnv_train_tcnn_eval_loss": (C.c_int, [vp, vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
-        "bnv_train_tcnn_forward": (C.c_int, [vp, vp, vp, i64, i32, i64, vp, vp, vp, sz, vp]),
-        "bnv_mesh_sdf_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
-        "bnv_mesh_sdf_build": (C.c_int, [vp, i64, vp, i64, vp, i64, vp]),
-        "bnv_mesh_sdf_query": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),
-        "bnv_mesh_ray_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
-        "bnv_mesh_ray_cast": (C.c_int, [vp, i64, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
-        "bnv_mesh_render_depth": (C.c_int, [vp, i64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
-                                            C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, i64, vp]),
-        "bnv_depth_sensor": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_uint32, C.c_double, C.c_double,
-                                       C.c_double, vp, vp]),
-        "bnv_icp_workspace_bytes": (sz, [i32, C.POINTER(i32)]),
-        "bnv_icp_align": (C.c_int, [vp, C.c_int, i32, i32, C.POINTER(C.c_double), C.c_double, vp, vp, i32, i32,
-                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                    C.POINTER(C.c_double), i32, C.POINTER(i32), C.c_double, C.c_double, C.c_double, vp,
-                                    sz, vp, vp, vp, vp, vp]),
-        "bnv_depth_filter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, vp,
-                                       C.c_int, vp, vp]),
-        "bnv_mesh_normals_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
-        "bnv_mesh_vertex_normals": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
-        "bnv_mesh_color_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
-        "bnv_mesh_color_begin": (C.c_int, [vp, i64, i64, vp]),
-        "bnv_mesh_color_accumulate": (C.c_int, [vp, vp, i64, C.POINTER(MeshColorFrame), i32, C.c_double, C.c_double,
-                                                C.c_double, C.c_double, vp, i64, vp]),
-        "bnv_mesh_color_resolve": (C.c_int, [vp, i64, i64, C.POINTER(C.c_uint8), vp, vp, vp, vp, vp]),
-        "bnv_plan_workspace_bytes": (sz, [C.c_int, C.c_int, C.POINTER(Grid), C.c_int, i64]),
-        "bnv_plan_workspace_reset": (C.c_int, [vp, sz, C.c_int, C.c_int, C.POINTER(Grid), C.c_int, i64, vp]),
-        "bnv_plan_extent": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                      C.c_double, vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int, vp,
-                                      vp]),
-        "bnv_plan_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                     C.c_double, vp, C.c_int, C.POINTER(Grid), C.c_int, i64, vp, sz, vp, vp]),
-    }
     for name in SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the library does not export it
-        fn.restype, fn.argtypes = sig[name]
+        fn.restype, fn.argtypes = SIGNATURES[name]
     _lib = lib
     # A/B switches from the environment (tools, experiments): BNV_OPTIONS="name=value,name=value" -> bnv_set_option.
     # They choose between implementations with identical results.

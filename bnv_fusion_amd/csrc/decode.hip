@@ -926,15 +926,8 @@ int bnv_set_option(const char* name, int value) {
 
 int bnv_decode_dense(const float* feat_grid, const float* pts_weight, const int32_t dims[3], float voxel_size,
                      int32_t min_pts_in_grid, const float* sdfmlp_pack, const float* voxel_coords, int64_t n,
-                     int32_t variant, float* out_sdf, float* out_feats, int32_t* status, bnv_stream_t stream) {
-  return bnv_decode_dense_mode(feat_grid, pts_weight, dims, voxel_size, min_pts_in_grid, sdfmlp_pack, voxel_coords, n,
-                               variant, 0, out_sdf, out_feats, status, stream);
-}
-
-int bnv_decode_dense_mode(const float* feat_grid, const float* pts_weight, const int32_t dims[3], float voxel_size,
-                          int32_t min_pts_in_grid, const float* sdfmlp_pack, const float* voxel_coords, int64_t n,
-                          int32_t variant, int32_t mlp_mode, float* out_sdf, float* out_feats, int32_t* status,
-                          bnv_stream_t stream) {
+                     int32_t variant, int32_t mlp_mode, float* out_sdf, float* out_feats, int32_t* status,
+                     bnv_stream_t stream) {
   if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   if (!feat_grid || !pts_weight || !dims || !sdfmlp_pack || n < 0 || !mlp_mode_field_ok(mlp_mode))
     return BNV_ERR_INVALID_ARGUMENT;

@@ -93,5 +93,11 @@ __attribute__((visibility("hidden"))) int lattice_table_impl(const bnv_volume_t*
                                                              int64_t n_voxels, int use_entries, void* ws_ptr,
                                                              size_t ws_bytes, int max_workgroups, bnv_stream_t stream);
 __attribute__((visibility("hidden"))) int decode_pts_init();
+// bnv_decode_lattice by stages (lattice.hip): 1 = neighbour rows + live entries, 2 = table MLP, 4 = blend into out_sdf.
+// The frame pipeline (pipeline.hip) runs 1 | 2 on one stream and blends on another; bnv_decode_lattice is all three.
+__attribute__((visibility("hidden"))) int decode_lattice_stages(
+    const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features, const float* weights, int64_t row_limit,
+    const float* sdfmlp_pack, const int64_t* origins, int64_t n, const int32_t* n_dev, const bnv_sdf_delta_t* delta,
+    void* ws, size_t ws_bytes, int32_t epoch, bool prestamped, float* out_sdf, int stages, bnv_stream_t stream);
 
 }  // namespace bnv

@@ -769,10 +769,10 @@ static bool splits_ok(const uint32_t* split_mask, int64_t split_samples, int64_t
   return split_samples > 0 && (n + split_samples - 1) / split_samples <= 31;
 }
 
-int bnv_decode_pts_splits(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features, const float* weights,
-                          int64_t row_limit, const float* sdfmlp_pack, const float* coords, int64_t n, int is_coords,
-                          const bnv_sdf_delta_t* delta, const uint32_t* split_mask, int64_t split_samples,
-                          float* out_sdf, bnv_stream_t stream) {
+int bnv_decode_pts(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features, const float* weights,
+                   int64_t row_limit, const float* sdfmlp_pack, const float* coords, int64_t n, int is_coords,
+                   const bnv_sdf_delta_t* delta, const uint32_t* split_mask, int64_t split_samples, float* out_sdf,
+                   bnv_stream_t stream) {
   if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   if (!vol_ok_ro(vol) || !grid || !features || !weights || !sdfmlp_pack || n < 0) return BNV_ERR_INVALID_ARGUMENT;
   if (!mlp_mode_field_ok(grid->mlp_mode) || !splits_ok(split_mask, split_samples, n)) return BNV_ERR_INVALID_ARGUMENT;
@@ -790,21 +790,14 @@ int bnv_decode_pts_splits(const bnv_volume_t* vol, const bnv_grid_t* grid, const
   return BNV_OK;
 }
 
-int bnv_decode_pts(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features, const float* weights,
-                   int64_t row_limit, const float* sdfmlp_pack, const float* coords, int64_t n, int is_coords,
-                   const bnv_sdf_delta_t* delta, float* out_sdf, bnv_stream_t stream) {
-  return bnv_decode_pts_splits(vol, grid, features, weights, row_limit, sdfmlp_pack, coords, n, is_coords, delta,
-                               nullptr, 0, out_sdf, stream);
-}
-
 size_t bnv_sdfmlp_bwd_pack_floats(void) { return SB_PACK_FLOATS; }
 size_t bnv_sdfmlp_tcnn_bwd_pack_floats(void) { return TB_TOTAL / 2; }
 
-int bnv_decode_pts_backward_splits(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features,
-                                   const float* weights, int64_t row_limit, const float* sdfmlp_pack,
-                                   const float* sdfmlp_bwd_pack, const float* coords, int64_t n, int is_coords,
-                                   const uint32_t* split_mask, int64_t split_samples, const float* grad_sdf,
-                                   float* grad_features, bnv_stream_t stream) {
+int bnv_decode_pts_backward(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features,
+                            const float* weights, int64_t row_limit, const float* sdfmlp_pack,
+                            const float* sdfmlp_bwd_pack, const float* coords, int64_t n, int is_coords,
+                            const uint32_t* split_mask, int64_t split_samples, const float* grad_sdf,
+                            float* grad_features, bnv_stream_t stream) {
   if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   if (!vol_ok_ro(vol) || !grid || !features || !weights || !sdfmlp_pack || !sdfmlp_bwd_pack || n < 0 ||
       !mlp_mode_field_ok(grid->mlp_mode) || !splits_ok(split_mask, split_samples, n))
@@ -825,14 +818,6 @@ int bnv_decode_pts_backward_splits(const bnv_volume_t* vol, const bnv_grid_t* gr
     hipLaunchKernelGGL(k_decode_pts_bwd, nblk, dim3(512), C_TOTAL * 4, (hipStream_t)stream, b);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
-}
-
-int bnv_decode_pts_backward(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features,
-                            const float* weights, int64_t row_limit, const float* sdfmlp_pack,
-                            const float* sdfmlp_bwd_pack, const float* coords, int64_t n, int is_coords,
-                            const float* grad_sdf, float* grad_features, bnv_stream_t stream) {
-  return bnv_decode_pts_backward_splits(vol, grid, features, weights, row_limit, sdfmlp_pack, sdfmlp_bwd_pack, coords,
-                                        n, is_coords, nullptr, 0, grad_sdf, grad_features, stream);
 }
 
 int bnv_optim_step(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features, const float* weights,

@@ -468,113 +468,12 @@ static bool grid_ok(const bnv_grid_t& g) {
          g.shard_rank < g.shard_world && mlp_mode_field_ok(g.mlp_mode);
 }
 
-// ==========================================================================================
-// C ABI
-// ==========================================================================================
-extern "C" {
-
-size_t bnv_pointnet_pack_floats(void) { return PN_PACK_FLOATS; }
-
-size_t bnv_encode_workspace_bytes(int64_t max_points, const int32_t n_xyz[3]) {
-  return encode_ws_layout(max_points, n_xyz, nullptr, nullptr);
-}
-
-int bnv_encode_workspace_reset(void* ws, size_t ws_bytes, bnv_stream_t stream) {
-  if (!ws) return BNV_ERR_INVALID_ARGUMENT;
-  BNV_HIP_CHECK(hipMemsetAsync(ws, 0, ws_bytes, (hipStream_t)stream));
-  return BNV_OK;
-}
-
-size_t bnv_encode_shard_counts_offset(void) { return offsetof(EncCtl, shard_boundary); }
-
-// ---- encode in two halves.  begin = voxelise (bounds mask, 8 corner voxels, bitmap) + sorted-unique (rank);
-// finish = PointNet + scatter-mean + min-points filter + ordered compaction.  Everything between the two lives in
-// the workspace; bnv_encode_pointcloud is begin + finish.
-
-int bnv_encode_begin(const float* input_pts, int64_t n_points, const bnv_grid_t* grid_host, void* ws_ptr,
-                     size_t ws_bytes, int64_t ws_max_points, bnv_stream_t stream_) {
-  if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
-  if (!input_pts || !grid_host || !ws_ptr || n_points < 0 || n_points > (1 << 27) || ws_max_points < n_points)
-    return BNV_ERR_INVALID_ARGUMENT;
-  const bnv_grid_t g = *grid_host;
-  if (!grid_ok(g)) return BNV_ERR_INVALID_ARGUMENT;
-  hipStream_t stream = (hipStream_t)stream_;
-  EncodeWs ws;
-  // the layout is a function of the workspace's capacity, not of this frame's point count, so
-  // the scratch the previous frame left clean stays where this frame expects it
-  if (encode_ws_layout(ws_max_points, g.n_xyz, (char*)ws_ptr, &ws) > ws_bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  if (n_points == 0) return BNV_OK;
-  const int n = (int)n_points;
-  launch_mark_points(k_mark, n, ws, g, stream, input_pts, n);
-  BNV_LAUNCH_CHECK();
-  return encode_rank(ws, g, input_pts, n, stream);
-}
-
-int bnv_encode_begin_depth(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                           const double* T_wc_host, double max_depth, const bnv_grid_t* grid_host, void* ws_ptr,
-                           size_t ws_bytes, int64_t ws_max_points, float* out_pts, bnv_stream_t stream_) {
-  return bnv_encode_begin_depth_gated(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, nullptr, 0, grid_host,
-                                      ws_ptr, ws_bytes, ws_max_points, out_pts, stream_);
-}
-
-int bnv_encode_begin_depth_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                                 const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
-                                 const bnv_grid_t* grid_host, void* ws_ptr, size_t ws_bytes, int64_t ws_max_points,
-                                 float* out_pts, bnv_stream_t stream_) {
-  if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
-  if (!depth || !intr_host || !T_wc_host || !grid_host || !ws_ptr || !out_pts || H <= 0 || W <= 0 || depth_dtype < 0 ||
-      depth_dtype > 2 || (int64_t)H * W > (1 << 27) || ws_max_points < (int64_t)H * W ||
-      !front_conf_args_ok(conf, conf_level))
-    return BNV_ERR_INVALID_ARGUMENT;
-  const bnv_grid_t g = *grid_host;
-  if (!grid_ok(g)) return BNV_ERR_INVALID_ARGUMENT;
-  hipStream_t stream = (hipStream_t)stream_;
-  EncodeWs ws;
-  if (encode_ws_layout(ws_max_points, g.n_xyz, (char*)ws_ptr, &ws) > ws_bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  FrontArgs a;
-  front_args_fill(a, depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth);
-  a.conf = conf;
-  a.conf_level = conf_level;
-  const int64_t n = (int64_t)H * W;
-  launch_mark_points(k_front_mark, n, ws, g, stream, a, out_pts);
-  BNV_LAUNCH_CHECK();
-  return encode_rank(ws, g, out_pts, (int)n, stream);
-}
-
-int bnv_encode_finish(const float* input_pts, int64_t n_points, const bnv_grid_t* grid_host,
-                      const float* pointnet_pack, void* ws_ptr, size_t ws_bytes, int64_t ws_max_points,
-                      float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids, int64_t* out_grid_ids,
-                      int64_t out_capacity, int emit_all, bnv_encode_counters_t* counters, bnv_stream_t stream) {
-  return bnv_encode_finish_image(input_pts, n_points, 0, grid_host, pointnet_pack, ws_ptr, ws_bytes, ws_max_points,
-                                 out_feats, out_pcounts, out_flat_ids, out_grid_ids, out_capacity, emit_all, counters,
-                                 stream);
-}
-
-int bnv_encode_finish_image(const float* input_pts, int64_t n_points, int image_width, const bnv_grid_t* grid_host,
-                            const float* pointnet_pack, void* ws_ptr, size_t ws_bytes, int64_t ws_max_points,
-                            float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids, int64_t* out_grid_ids,
-                            int64_t out_capacity, int emit_all, bnv_encode_counters_t* counters, bnv_stream_t stream_) {
-  return bnv_encode_finish_image_wg(input_pts, n_points, image_width, grid_host, pointnet_pack, ws_ptr, ws_bytes,
-                                    ws_max_points, out_feats, out_pcounts, out_flat_ids, out_grid_ids, out_capacity,
-                                    emit_all, counters, 0, stream_);
-}
-
-int bnv_encode_finish_image_wg(const float* input_pts, int64_t n_points, int image_width, const bnv_grid_t* grid_host,
-                               const float* pointnet_pack, void* ws_ptr, size_t ws_bytes, int64_t ws_max_points,
-                               float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids, int64_t* out_grid_ids,
-                               int64_t out_capacity, int emit_all, bnv_encode_counters_t* counters,
-                               int max_workgroups, bnv_stream_t stream_) {
-  return bnv_encode_finish_image_parts(input_pts, n_points, image_width, grid_host, pointnet_pack, ws_ptr, ws_bytes,
-                                       ws_max_points, out_feats, out_pcounts, out_flat_ids, out_grid_ids, out_capacity,
-                                       emit_all, counters, max_workgroups, 3, stream_);
-}
-
-int bnv_encode_finish_image_parts(const float* input_pts, int64_t n_points, int image_width,
-                                  const bnv_grid_t* grid_host, const float* pointnet_pack, void* ws_ptr,
-                                  size_t ws_bytes, int64_t ws_max_points, float* out_feats, int64_t* out_pcounts,
-                                  int64_t* out_flat_ids, int64_t* out_grid_ids, int64_t out_capacity, int emit_all,
-                                  bnv_encode_counters_t* counters, int max_workgroups, int parts,
-                                  bnv_stream_t stream_) {
+// finish = PointNet + scatter (parts & 1), then mean + min-points filter + ordered compaction (parts & 2)
+int bnv::encode_finish_parts(const float* input_pts, int64_t n_points, int image_width, const bnv_grid_t* grid_host,
+                             const float* pointnet_pack, void* ws_ptr, size_t ws_bytes, int64_t ws_max_points,
+                             float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids, int64_t* out_grid_ids,
+                             int64_t out_capacity, int emit_all, bnv_encode_counters_t* counters, int max_workgroups,
+                             int parts, bnv_stream_t stream_) {
   if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   if (image_width < 0 || max_workgroups < 0 || parts < 1 || parts > 3) return BNV_ERR_INVALID_ARGUMENT;
   if (!input_pts || !grid_host || !pointnet_pack || !ws_ptr || !counters || n_points < 0 ||
@@ -631,6 +530,75 @@ int bnv_encode_finish_image_parts(const float* input_pts, int64_t n_points, int 
   return BNV_OK;
 }
 
+// ==========================================================================================
+// C ABI
+// ==========================================================================================
+extern "C" {
+
+size_t bnv_pointnet_pack_floats(void) { return PN_PACK_FLOATS; }
+
+size_t bnv_encode_workspace_bytes(int64_t max_points, const int32_t n_xyz[3]) {
+  return encode_ws_layout(max_points, n_xyz, nullptr, nullptr);
+}
+
+size_t bnv_encode_shard_counts_offset(void) { return offsetof(EncCtl, shard_boundary); }
+
+// ---- encode in two halves.  begin = voxelise (bounds mask, 8 corner voxels, bitmap) + sorted-unique (rank);
+// finish = PointNet + scatter-mean + min-points filter + ordered compaction.  Everything between the two lives in
+// the workspace; bnv_encode_pointcloud is begin + finish.
+
+int bnv_encode_begin(const float* input_pts, int64_t n_points, const bnv_grid_t* grid_host, void* ws_ptr,
+                     size_t ws_bytes, int64_t ws_max_points, bnv_stream_t stream_) {
+  if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
+  if (!input_pts || !grid_host || !ws_ptr || n_points < 0 || n_points > (1 << 27) || ws_max_points < n_points)
+    return BNV_ERR_INVALID_ARGUMENT;
+  const bnv_grid_t g = *grid_host;
+  if (!grid_ok(g)) return BNV_ERR_INVALID_ARGUMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  EncodeWs ws;
+  // the layout is a function of the workspace's capacity, not of this frame's point count, so
+  // the scratch the previous frame left clean stays where this frame expects it
+  if (encode_ws_layout(ws_max_points, g.n_xyz, (char*)ws_ptr, &ws) > ws_bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  if (n_points == 0) return BNV_OK;
+  const int n = (int)n_points;
+  launch_mark_points(k_mark, n, ws, g, stream, input_pts, n);
+  BNV_LAUNCH_CHECK();
+  return encode_rank(ws, g, input_pts, n, stream);
+}
+
+int bnv_encode_begin_depth(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
+                           const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
+                           const bnv_grid_t* grid_host, void* ws_ptr, size_t ws_bytes, int64_t ws_max_points,
+                           float* out_pts, bnv_stream_t stream_) {
+  if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
+  if (!depth || !intr_host || !T_wc_host || !grid_host || !ws_ptr || !out_pts || H <= 0 || W <= 0 || depth_dtype < 0 ||
+      depth_dtype > 2 || (int64_t)H * W > (1 << 27) || ws_max_points < (int64_t)H * W ||
+      !front_conf_args_ok(conf, conf_level))
+    return BNV_ERR_INVALID_ARGUMENT;
+  const bnv_grid_t g = *grid_host;
+  if (!grid_ok(g)) return BNV_ERR_INVALID_ARGUMENT;
+  hipStream_t stream = (hipStream_t)stream_;
+  EncodeWs ws;
+  if (encode_ws_layout(ws_max_points, g.n_xyz, (char*)ws_ptr, &ws) > ws_bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
+  FrontArgs a;
+  front_args_fill(a, depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth);
+  a.conf = conf;
+  a.conf_level = conf_level;
+  const int64_t n = (int64_t)H * W;
+  launch_mark_points(k_front_mark, n, ws, g, stream, a, out_pts);
+  BNV_LAUNCH_CHECK();
+  return encode_rank(ws, g, out_pts, (int)n, stream);
+}
+
+int bnv_encode_finish(const float* input_pts, int64_t n_points, int image_width, const bnv_grid_t* grid_host,
+                      const float* pointnet_pack, void* ws_ptr, size_t ws_bytes, int64_t ws_max_points,
+                      float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids, int64_t* out_grid_ids,
+                      int64_t out_capacity, int emit_all, bnv_encode_counters_t* counters, bnv_stream_t stream) {
+  return encode_finish_parts(input_pts, n_points, image_width, grid_host, pointnet_pack, ws_ptr, ws_bytes,
+                             ws_max_points, out_feats, out_pcounts, out_flat_ids, out_grid_ids, out_capacity, emit_all,
+                             counters, 0, 3, stream);
+}
+
 int bnv_encode_pointcloud(const float* input_pts, int64_t n_points, const bnv_grid_t* grid_host,
                           const float* pointnet_pack, void* ws_ptr, size_t ws_bytes, int64_t ws_max_points,
                           float* out_feats,
@@ -640,7 +608,7 @@ int bnv_encode_pointcloud(const float* input_pts, int64_t n_points, const bnv_gr
   if (!pointnet_pack || !counters) return BNV_ERR_INVALID_ARGUMENT;
   const int rc = bnv_encode_begin(input_pts, n_points, grid_host, ws_ptr, ws_bytes, ws_max_points, stream);
   if (rc != BNV_OK) return rc;
-  return bnv_encode_finish(input_pts, n_points, grid_host, pointnet_pack, ws_ptr, ws_bytes, ws_max_points, out_feats,
+  return bnv_encode_finish(input_pts, n_points, 0, grid_host, pointnet_pack, ws_ptr, ws_bytes, ws_max_points, out_feats,
                            out_pcounts, out_flat_ids, out_grid_ids, out_capacity, emit_all, counters, stream);
 }
 

@@ -329,5 +329,15 @@ BNV_HIDDEN void launch_encoder_tcnn(bool blocks, int image_width, int grid, cons
 // shard.hip: first-touch ownership behind k_rank -- k_shard_assign, then k_shard_own on the frame's input_pts rows
 BNV_HIDDEN int launch_shard_own(const EncodeWs& ws, const bnv_grid_t& g, const float* pts, int n, int32_t* plist,
                                 hipStream_t stream);
+// encode.hip: bnv_encode_finish with the two staging knobs of the frame pipeline (pipeline.hip).  The persistent
+// point-encoder kernel runs on at most max_workgroups workgroups (one per CU; 0 = every CU): it fills a CU's LDS, so
+// the pipeline leaves a share of the CUs to the small kernels of its other streams this way.  parts & 1 = the
+// point-encoder MLP + scatter, parts & 2 = finalize (mean, filter, ordered compaction, counters, clean workspace); the
+// two may go to different streams (the caller orders them: part 2 behind part 1).  bnv_encode_finish is (0, 3).
+BNV_HIDDEN int encode_finish_parts(const float* input_pts, int64_t n_points, int image_width,
+                                   const bnv_grid_t* grid_host, const float* pointnet_pack, void* ws, size_t ws_bytes,
+                                   int64_t ws_max_points, float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids,
+                                   int64_t* out_grid_ids, int64_t out_capacity, int emit_all,
+                                   bnv_encode_counters_t* counters, int max_workgroups, int parts, bnv_stream_t stream);
 #undef BNV_HIDDEN
 }  // namespace bnv

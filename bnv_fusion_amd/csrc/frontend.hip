@@ -86,10 +86,9 @@ size_t bnv_depth_workspace_bytes(int H, int W) {
   return (size_t)(((n + kFrontTile - 1) / kFrontTile + 1) * 4 + 256);
 }
 
-static int depth_to_points_impl(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                                const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
-                                void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out, bool pad,
-                                bnv_stream_t stream_) {
+int bnv_depth_to_points(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
+                        const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level, int pad,
+                        void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out, bnv_stream_t stream_) {
   if (!depth || !intr_host || !T_wc_host || !ws || !out_pts || !n_out || H <= 0 || W <= 0 || depth_dtype < 0 ||
       depth_dtype > 2 || (int64_t)H * W >= (1LL << 31) || !front_conf_args_ok(conf, conf_level))
     return BNV_ERR_INVALID_ARGUMENT;
@@ -109,34 +108,6 @@ static int depth_to_points_impl(const void* depth, int depth_dtype, int H, int W
                      pad ? (const int32_t*)n_out : (const int32_t*)nullptr);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
-}
-
-int bnv_depth_to_points(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                        const double* T_wc_host, double max_depth, void* ws, size_t ws_bytes, float* out_pts,
-                        int32_t* n_out, bnv_stream_t stream) {
-  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, nullptr, 0, ws, ws_bytes,
-                              out_pts, n_out, false, stream);
-}
-
-int bnv_depth_to_points_padded(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                               const double* T_wc_host, double max_depth, void* ws, size_t ws_bytes, float* out_pts,
-                               int32_t* n_out, bnv_stream_t stream) {
-  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, nullptr, 0, ws, ws_bytes,
-                              out_pts, n_out, true, stream);
-}
-
-int bnv_depth_to_points_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                              const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level, void* ws,
-                              size_t ws_bytes, float* out_pts, int32_t* n_out, bnv_stream_t stream) {
-  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, conf, conf_level, ws,
-                              ws_bytes, out_pts, n_out, false, stream);
-}
-
-int bnv_depth_to_points_padded_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                                     const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
-                                     void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out, bnv_stream_t stream) {
-  return depth_to_points_impl(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, conf, conf_level, ws,
-                              ws_bytes, out_pts, n_out, true, stream);
 }
 
 }  // extern "C"

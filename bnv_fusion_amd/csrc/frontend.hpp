@@ -118,7 +118,7 @@ static inline void front_args_fill(FrontArgs& a, const void* depth, int depth_dt
   a.conf_level = 0;
 }
 
-// the confidence gate of the *_gated entries: a null map with a positive level is a caller error; a null map with
+// the confidence gate of the depth entries: a null map with a positive level is a caller error; a null map with
 // level 0 is the ungated front end
 static inline bool front_conf_args_ok(const uint8_t* conf, int conf_level) {
   return conf_level >= 0 && (conf || conf_level == 0);

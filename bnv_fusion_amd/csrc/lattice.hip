@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_lattice_neighbors(bnv_volume_t v, const
                                                            const int32_t* __restrict__ n_dev,
                                                            int32_t* __restrict__ ctl_clear) {
   if (n_dev) n = (int64_t)*n_dev < n ? (int64_t)*n_dev : n;  // count from device memory; n = grid capacity
-  // origins stamped by the frame's upsert (bnv_volume_integrate_frame): no k_lattice_stamp launch in front of this
+  // origins stamped by the frame's upsert (bnv_volume_integrate with extras): no k_lattice_stamp launch in front of this
   // one, so the control words of the stages behind are cleared here
   if (ctl_clear && blockIdx.x == 0 && threadIdx.x == 0) ctl_clear[1] = ctl_clear[2] = ctl_clear[3] = 0;
   // grid-stride: the launch is sized for the CAPACITY (the count is on the device) but capped, so a frame that holds
@@ -838,12 +838,14 @@ int bnv_lattice_blend(const bnv_volume_t* vol, const bnv_grid_t* grid, const int
   return BNV_OK;
 }
 
-static int decode_lattice_impl(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features,
+}  // extern "C"
+
+// stages: 1 = neighbour rows + live entries, 2 = table MLP, 4 = blend
+int bnv::decode_lattice_stages(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features,
                                const float* weights, int64_t row_limit, const float* sdfmlp_pack,
                                const int64_t* origins, int64_t n, const int32_t* n_dev, const bnv_sdf_delta_t* delta,
-                               void* ws_ptr, size_t ws_bytes, int32_t epoch, float* out_sdf, bool prestamped,
-                               bnv_stream_t stream, int stages = 7) {
-  // stages: 1 = neighbour rows + live entries, 2 = table MLP, 4 = blend
+                               void* ws_ptr, size_t ws_bytes, int32_t epoch, bool prestamped, float* out_sdf,
+                               int stages, bnv_stream_t stream) {
   if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   if (!features || !grid || n < 0 || ((stages & 2) && !sdfmlp_pack)) return BNV_ERR_INVALID_ARGUMENT;
   // persistent tables belong to the volume's own rows: have-bits set by a call that decodes other features would poison them
@@ -869,32 +871,15 @@ static int decode_lattice_impl(const bnv_volume_t* vol, const bnv_grid_t* grid, 
     }
   }
   if (stages & 2) BNV_TRY(lattice_table_impl(vol, grid, features, sdfmlp_pack, n, 1, ws_ptr, ws_bytes, 0, stream));
-  if (!(stages & 4) || !out_sdf) return BNV_OK;   // (the caller blends itself, bnv_decode_lattice_stamped_tables)
+  if (!(stages & 4) || !out_sdf) return BNV_OK;   // (the caller blends itself: the frame pipeline)
   return bnv_lattice_blend(vol, grid, origins, n, n_dev, delta, ws_ptr, ws_bytes, out_sdf, stream);
 }
 
-int bnv_decode_lattice(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features,
-                       const float* weights, int64_t row_limit, const float* sdfmlp_pack, const int64_t* origins,
-                       int64_t n, const int32_t* n_dev, const bnv_sdf_delta_t* delta, void* ws_ptr, size_t ws_bytes,
-                       int32_t epoch, float* out_sdf, bnv_stream_t stream) {
-  return decode_lattice_impl(vol, grid, features, weights, row_limit, sdfmlp_pack, origins, n, n_dev, delta, ws_ptr,
-                             ws_bytes, epoch, out_sdf, false, stream);
+extern "C" int bnv_decode_lattice(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features,
+                                  const float* weights, int64_t row_limit, const float* sdfmlp_pack,
+                                  const int64_t* origins, int64_t n, const int32_t* n_dev, const bnv_sdf_delta_t* delta,
+                                  void* ws_ptr, size_t ws_bytes, int32_t epoch, int prestamped, float* out_sdf,
+                                  bnv_stream_t stream) {
+  return decode_lattice_stages(vol, grid, features, weights, row_limit, sdfmlp_pack, origins, n, n_dev, delta, ws_ptr,
+                               ws_bytes, epoch, prestamped != 0, out_sdf, 7, stream);
 }
-
-int bnv_decode_lattice_stamped_tables(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features,
-                                      const float* weights, int64_t row_limit, const float* sdfmlp_pack,
-                                      const int64_t* origins, int64_t n, const int32_t* n_dev, void* ws_ptr,
-                                      size_t ws_bytes, int32_t epoch, bnv_stream_t stream) {
-  return decode_lattice_impl(vol, grid, features, weights, row_limit, sdfmlp_pack, origins, n, n_dev, nullptr, ws_ptr,
-                             ws_bytes, epoch, nullptr, true, stream, 3);
-}
-
-int bnv_decode_lattice_stamped(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* features,
-                               const float* weights, int64_t row_limit, const float* sdfmlp_pack,
-                               const int64_t* origins, int64_t n, const int32_t* n_dev, const bnv_sdf_delta_t* delta,
-                               void* ws_ptr, size_t ws_bytes, int32_t epoch, float* out_sdf, bnv_stream_t stream) {
-  return decode_lattice_impl(vol, grid, features, weights, row_limit, sdfmlp_pack, origins, n, n_dev, delta, ws_ptr,
-                             ws_bytes, epoch, out_sdf, true, stream);
-}
-
-}  // extern "C"

@@ -32,7 +32,9 @@
 #include <new>
 
 #include "bnv_common.hpp"
-#include "frontend.hpp"   // front_conf_args_ok
+#include "decode_host.hpp"   // decode_lattice_stages
+#include "encode.hpp"        // encode_finish_parts
+#include "frontend.hpp"      // front_conf_args_ok
 
 using namespace bnv;
 
@@ -243,15 +245,15 @@ static int begin_tail(bnv_frame_pipe* p, int slot, const float* pts, int64_t n, 
   const bnv_grid_t g = slot_grid(p, slot);
   // (with the timeline on, the two parts are enqueued separately so that a mark fits between them: the same launches)
   const bool two = p->tl_on;
-  int rc = bnv_encode_finish_image_parts(pts, n, image_width, &g, c.pointnet_pack, enc_ws, c.enc_ws_bytes,
-                                         c.enc_ws_max_points, b.feats, b.pcounts, b.flat_ids, b.grid_ids,
-                                         c.out_capacity, 0, b.counters, c.encoder_workgroups, two ? 1 : 3, p->E);
+  int rc = encode_finish_parts(pts, n, image_width, &g, c.pointnet_pack, enc_ws, c.enc_ws_bytes, c.enc_ws_max_points,
+                               b.feats, b.pcounts, b.flat_ids, b.grid_ids, c.out_capacity, 0, b.counters,
+                               c.encoder_workgroups, two ? 1 : 3, p->E);
   if (rc != BNV_OK) return rc;
   tl_mark(p, slot, 3, p->E);
   if (two) {
-    rc = bnv_encode_finish_image_parts(pts, n, image_width, &g, c.pointnet_pack, enc_ws, c.enc_ws_bytes,
-                                       c.enc_ws_max_points, b.feats, b.pcounts, b.flat_ids, b.grid_ids, c.out_capacity,
-                                       0, b.counters, c.encoder_workgroups, 2, p->E);
+    rc = encode_finish_parts(pts, n, image_width, &g, c.pointnet_pack, enc_ws, c.enc_ws_bytes, c.enc_ws_max_points,
+                             b.feats, b.pcounts, b.flat_ids, b.grid_ids, c.out_capacity, 0, b.counters,
+                             c.encoder_workgroups, 2, p->E);
     if (rc != BNV_OK) return rc;
   }
   tl_mark(p, slot, 4, p->E);
@@ -292,32 +294,21 @@ static int side_depth(bnv_frame_pipe* p, int slot, const void* depth, int depth_
     for (int i = 0; i < 9; ++i) K[i] = (float)intr_host[i];
     for (int i = 0; i < 16; ++i) T[i] = (float)T_wc_host[i];
     const int32_t* gate = &b.counters->n_valid_points;
-    int rc;
-    if (depth_dtype == 0)
-      rc = bnv_tsdf_integrate_u16(c.tsdf.tsdf, c.tsdf.weight, color_im ? c.tsdf.color : nullptr, c.tsdf.dim,
-                                  c.tsdf.origin, c.tsdf.voxel_size, c.tsdf.trunc_margin, (const uint16_t*)depth,
-                                  color_im, H, W, K, T, 1.0f, (float)c.max_depth, gate, p->E);
-    else
-      rc = bnv_tsdf_integrate(c.tsdf.tsdf, c.tsdf.weight, color_im ? c.tsdf.color : nullptr, c.tsdf.dim, c.tsdf.origin,
-                              c.tsdf.voxel_size, c.tsdf.trunc_margin, (const float*)depth, color_im, H, W, K, T, 1.0f,
-                              (float)c.max_depth, gate, p->E);
+    const int rc = bnv_tsdf_integrate(c.tsdf.tsdf, c.tsdf.weight, color_im ? c.tsdf.color : nullptr, c.tsdf.dim,
+                                      c.tsdf.origin, c.tsdf.voxel_size, c.tsdf.trunc_margin, depth, depth_dtype,
+                                      color_im, H, W, K, T, 1.0f, (float)c.max_depth, gate, p->E);
     if (rc != BNV_OK) return rc;
   }
   BNV_HIP_CHECK(hipEventRecord(p->ev_side[slot], p->E));
   return BNV_OK;
 }
 
-int bnv_frame_begin_depth(bnv_frame_pipe_t* p, int slot, const void* depth, int depth_dtype, int H, int W,
-                          const double* intr_host, const double* T_wc_host, const float* color_im) {
-  return bnv_frame_begin_depth_gated(p, slot, depth, depth_dtype, H, W, intr_host, T_wc_host, nullptr, 0, color_im);
-}
-
 // The confidence gate applies to the neural encode only: the TSDF side fusion reads the range-masked depth, as the
 // reference's does (run_e2e.py:99-109 fuses frame['rgbd'], which read_mask does not touch), and stays gated by the
 // frame's in-bounds point count, taken after the confidence gate.
-int bnv_frame_begin_depth_gated(bnv_frame_pipe_t* p, int slot, const void* depth, int depth_dtype, int H, int W,
-                                const double* intr_host, const double* T_wc_host, const uint8_t* conf, int conf_level,
-                                const float* color_im) {
+int bnv_frame_begin_depth(bnv_frame_pipe_t* p, int slot, const void* depth, int depth_dtype, int H, int W,
+                          const double* intr_host, const double* T_wc_host, const uint8_t* conf, int conf_level,
+                          const float* color_im) {
   if (!slot_ok(p, slot) || !front_conf_args_ok(conf, conf_level)) return BNV_ERR_INVALID_ARGUMENT;
   const bnv_frame_pipe_config_t& c = p->cfg;
   const bnv_frame_slot_t& b = c.slots[slot];
@@ -326,8 +317,8 @@ int bnv_frame_begin_depth_gated(bnv_frame_pipe_t* p, int slot, const void* depth
   int rc = begin_head(p, slot);
   if (rc != BNV_OK) return rc;
   const bnv_grid_t g = slot_grid(p, slot);
-  rc = bnv_encode_begin_depth_gated(depth, depth_dtype, H, W, intr_host, T_wc_host, c.max_depth, conf, conf_level, &g,
-                                    slot_encws(p, slot), c.enc_ws_bytes, c.enc_ws_max_points, b.input_pts, p->F);
+  rc = bnv_encode_begin_depth(depth, depth_dtype, H, W, intr_host, T_wc_host, c.max_depth, conf, conf_level, &g,
+                              slot_encws(p, slot), c.enc_ws_bytes, c.enc_ws_max_points, b.input_pts, p->F);
   if (rc != BNV_OK) return rc;
   rc = begin_tail(p, slot, b.input_pts, (int64_t)H * W, W);
   if (rc != BNV_OK) return rc;
@@ -407,8 +398,8 @@ int bnv_frame_upsert(bnv_frame_pipe_t* p, int slot, const bnv_volume_t* vol, voi
   }
   x.lattice_ws = lattice_ws;
   x.stamp_epoch = lattice_epoch;
-  const int rc = bnv_volume_integrate_frame(vol, b.grid_ids, b.feats, b.pcounts, c.out_capacity, &b.counters->n_out,
-                                            vol_ws, vol_ws_bytes, &x, p->M);
+  const int rc = bnv_volume_integrate(vol, b.grid_ids, b.feats, b.pcounts, c.out_capacity, &b.counters->n_out, vol_ws,
+                                      vol_ws_bytes, &x, p->M);
   if (rc != BNV_OK) return rc;
   tl_mark(p, slot, 6, p->M);
   p->state[slot] = 2;
@@ -466,7 +457,7 @@ int bnv_frame_finish(bnv_frame_pipe_t* p, int slot, const bnv_volume_t* vol, con
   int rc;
   tl_mark(p, slot, 7, p->M);
   if (c.grid.shard_world > 1 && blocks && block_capacity > 0) {
-    rc = bnv_shard_install_reset(vol, &c.grid, blocks, c.grid.shard_world, block_capacity, b.send_block, p->M);
+    rc = bnv_shard_install(vol, &c.grid, blocks, c.grid.shard_world, block_capacity, b.send_block, p->M);
     if (rc != BNV_OK) return rc;
   }
   tl_mark(p, slot, 8, p->M);
@@ -479,9 +470,9 @@ int bnv_frame_finish(bnv_frame_pipe_t* p, int slot, const bnv_volume_t* vol, con
       // decoded before it (blend stream) may still be reading
       BNV_HIP_CHECK(wait_event(p, p->M, p->ev_done[p->last_decoded]));
     p->last_decoded = slot;
-    rc = bnv_decode_lattice_stamped_tables(vol, &g, vol->features, vol->weights, vol->row_capacity, sdfmlp_pack,
-                                           b.grid_ids, c.out_capacity, &b.counters->n_out, lattice_ws,
-                                           lattice_ws_bytes, lattice_epoch, p->M);
+    rc = decode_lattice_stages(vol, &g, vol->features, vol->weights, vol->row_capacity, sdfmlp_pack, b.grid_ids,
+                               c.out_capacity, &b.counters->n_out, nullptr, lattice_ws, lattice_ws_bytes, lattice_epoch,
+                               true, nullptr, 1 | 2, p->M);
     if (rc != BNV_OK) return rc;
     tl_mark(p, slot, 9, p->M);
     if (p->B != p->M) {

@@ -251,8 +251,8 @@ int bnv_ray_samples(const float* uv, const float* gt_pts, const float* ray_mask,
   return BNV_OK;
 }
 
-int bnv_ray_loss_splits(const float* pred, const float* target, const float* weight, const float* n_valid, int64_t m,
-                        int64_t split_samples, float* loss, float* grad, bnv_stream_t stream) {
+int bnv_ray_loss(const float* pred, const float* target, const float* weight, const float* n_valid, int64_t m,
+                 int64_t split_samples, float* loss, float* grad, bnv_stream_t stream) {
   if (m < 0 || split_samples < 0 || (m > 0 && (!pred || !target || !weight || !n_valid || !loss || !grad)))
     return BNV_ERR_INVALID_ARGUMENT;
   if (m == 0) return BNV_OK;
@@ -260,11 +260,6 @@ int bnv_ray_loss_splits(const float* pred, const float* target, const float* wei
                      weight, n_valid, m, split_samples, loss, grad);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
-}
-
-int bnv_ray_loss(const float* pred, const float* target, const float* weight, const float* n_valid, int64_t m,
-                 float* loss, float* grad, bnv_stream_t stream) {
-  return bnv_ray_loss_splits(pred, target, weight, n_valid, m, 0, loss, grad, stream);
 }
 
 int bnv_volume_count_optim_splits(const bnv_volume_t* vol, const bnv_grid_t* grid, const float* pts, int64_t m,

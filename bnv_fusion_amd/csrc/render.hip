@@ -570,7 +570,7 @@ int bnv_render_depth(const bnv_volume_t* vol, const bnv_grid_t* grid, const floa
     samples += h.n_samples;
     if (h.n_samples > 0) {
       const int rc = bnv_decode_pts(vol, grid, features, weights, row_limit, sdfmlp_pack, w.pts, h.n_samples, 0, delta,
-                                    w.vals, stream);
+                                    nullptr, 0, w.vals, stream);
       if (rc != BNV_OK) return rc;
     }
     hipLaunchKernelGGL(k_render_resolve, dim3(blocks_for(n_act, kRenderThreads)), dim3(kRenderThreads), 0, s, cam, w, cur, n_act,
@@ -589,7 +589,7 @@ int bnv_render_depth(const bnv_volume_t* vol, const bnv_grid_t* grid, const floa
   }
   if (normals_out && n_hits > 0) {
     const int rc = bnv_decode_pts(vol, grid, features, weights, row_limit, sdfmlp_pack, w.pts, (int64_t)n_hits * 6, 0,
-                                  delta, w.vals, stream);
+                                  delta, nullptr, 0, w.vals, stream);
     if (rc != BNV_OK) return rc;
     hipLaunchKernelGGL(k_render_normals, dim3(blocks_for(n_hits, kRenderThreads)), dim3(kRenderThreads), 0, s, w, n_hits, normals_out);
     BNV_LAUNCH_CHECK();

@@ -102,7 +102,7 @@ struct DecodeArgs {
   float* nf_out;     // optional [n, 8]: the features the evaluation used
   int32_t* status;   // optional: [1] = 5 when a feature leaves the certified range of the split arithmetic
   int32_t half_tail; // k_lattice_table_x: hand the last partial round out as 64-evaluation tiles
-  // PTS, several ray splits of an optimiser step in ONE call (bnv_optim_step, bnv_decode_pts_splits): query q belongs
+  // PTS, several ray splits of an optimiser step in ONE call (bnv_optim_step, bnv_decode_pts with a split_mask): query q belongs
   // to split q / split_samples; bit s of split_mask[row] = split s touches the row (bnv_volume_count_optim_splits).
   // The weight the mask decision of a split-s query sees is weights[row] + 1 for every split <= s that touches the
   // row -- count_optim (sparse_volume.py:602-622) called split by split, render_utils.py:491-497.  Null: plain weights.

@@ -509,8 +509,8 @@ int bnv_shard_pack(const bnv_volume_t* vol, const bnv_grid_t* grid, const int64_
   return BNV_OK;
 }
 
-int bnv_shard_install_reset(const bnv_volume_t* vol, const bnv_grid_t* grid, const void* blocks, int world,
-                            int64_t capacity, void* own_send_block, bnv_stream_t stream_) {
+int bnv_shard_install(const bnv_volume_t* vol, const bnv_grid_t* grid, const void* blocks, int world,
+                      int64_t capacity, void* own_send_block, bnv_stream_t stream_) {
   if (!shard_vol_ok(vol) || !grid || !blocks || world < 1 || world != grid->shard_world || capacity < 0)
     return BNV_ERR_INVALID_ARGUMENT;
   if (capacity == 0 || world == 1) return BNV_OK;
@@ -519,11 +519,6 @@ int bnv_shard_install_reset(const bnv_volume_t* vol, const bnv_grid_t* grid, con
                      *grid, (const ShardRec*)blocks, world, capacity, vol->n_rows + 1, (ShardRec*)own_send_block);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
-}
-
-int bnv_shard_install(const bnv_volume_t* vol, const bnv_grid_t* grid, const void* blocks, int world,
-                      int64_t capacity, bnv_stream_t stream) {
-  return bnv_shard_install_reset(vol, grid, blocks, world, capacity, nullptr, stream);
 }
 
 }  // extern "C"

@@ -148,13 +148,13 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate_batch(TsdfBatchArgs a) {
 
 using namespace bnv;
 
-static int tsdf_integrate_impl(float* tsdf, float* weight, float* color, const int32_t dim_host[3],
+extern "C" int bnv_tsdf_integrate(float* tsdf, float* weight, float* color, const int32_t dim_host[3],
                                   const float origin_host[3], float voxel_size, float trunc_margin,
-                                  const float* depth_im, const uint16_t* depth_mm, const float* color_im, int im_h, int im_w,
+                                  const void* depth, int depth_dtype, const float* color_im, int im_h, int im_w,
                                   const float intr_host[9], const float pose_host[16], float obs_weight,
                                   float max_depth, const int32_t* gate, bnv_stream_t stream) {
-  if (!tsdf || !weight || !dim_host || !origin_host || (!depth_im && !depth_mm) || !intr_host || !pose_host || im_h <= 0 ||
-      im_w <= 0)
+  if (!tsdf || !weight || !dim_host || !origin_host || !depth || depth_dtype < 0 || depth_dtype > 1 || !intr_host ||
+      !pose_host || im_h <= 0 || im_w <= 0)
     return BNV_ERR_INVALID_ARGUMENT;
   TsdfArgs a;
   a.tsdf = tsdf;
@@ -172,8 +172,8 @@ static int tsdf_integrate_impl(float* tsdf, float* weight, float* color, const i
   a.im_h = im_h;
   a.im_w = im_w;
   a.color_im = color_im;
-  a.depth_im = depth_im;
-  a.depth_mm = depth_mm;
+  a.depth_im = depth_dtype == 1 ? (const float*)depth : nullptr;
+  a.depth_mm = depth_dtype == 0 ? (const uint16_t*)depth : nullptr;
   a.max_depth = max_depth;
   a.gate = gate;
   const int64_t n = (int64_t)a.dim[0] * a.dim[1] * a.dim[2];
@@ -181,24 +181,6 @@ static int tsdf_integrate_impl(float* tsdf, float* weight, float* color, const i
   hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
-}
-
-extern "C" int bnv_tsdf_integrate(float* tsdf, float* weight, float* color, const int32_t dim_host[3],
-                                  const float origin_host[3], float voxel_size, float trunc_margin,
-                                  const float* depth_im, const float* color_im, int im_h, int im_w,
-                                  const float intr_host[9], const float pose_host[16], float obs_weight,
-                                  float max_depth, const int32_t* gate, bnv_stream_t stream) {
-  return tsdf_integrate_impl(tsdf, weight, color, dim_host, origin_host, voxel_size, trunc_margin, depth_im, nullptr,
-                             color_im, im_h, im_w, intr_host, pose_host, obs_weight, max_depth, gate, stream);
-}
-
-extern "C" int bnv_tsdf_integrate_u16(float* tsdf, float* weight, float* color, const int32_t dim_host[3],
-                                      const float origin_host[3], float voxel_size, float trunc_margin,
-                                      const uint16_t* depth_mm, const float* color_im, int im_h, int im_w,
-                                      const float intr_host[9], const float pose_host[16], float obs_weight,
-                                      float max_depth, const int32_t* gate, bnv_stream_t stream) {
-  return tsdf_integrate_impl(tsdf, weight, color, dim_host, origin_host, voxel_size, trunc_margin, nullptr, depth_mm,
-                             color_im, im_h, im_w, intr_host, pose_host, obs_weight, max_depth, gate, stream);
 }
 
 extern "C" int bnv_tsdf_integrate_batch_u16(float* tsdf, float* weight, float* color, const int32_t dim_host[3],

@@ -189,7 +189,7 @@ __global__ void k_vol_commit(int32_t* __restrict__ n_rows, const int32_t* __rest
 // commits the new count), creates the rows and applies the running average.  Keys are unique within a batch, so a
 // slot / row is touched by exactly one thread; the look-back state is epoch-tagged and needs no clearing.
 //
-// FRAME (bnv_volume_integrate_frame, the per-frame pipeline): the same launch also does what used to be two more --
+// FRAME (bnv_volume_integrate with extras, the per-frame pipeline): the same launch also does what used to be two more --
 //  * the rows it touches are the ORIGINS of the frame's lattice decode: origin_stamp[row] = stamp_epoch
 //    (k_lattice_stamp's job; the decode then starts at k_lattice_neighbors);
 //  * sharded volume: the boundary voxels among them leave as 48-byte records {x, y, z, weight, features} with the
@@ -629,34 +629,18 @@ int bnv_volume_rehash(const bnv_volume_t* vol, bnv_stream_t stream) {
 
 int bnv_volume_integrate(const bnv_volume_t* vol, const int64_t* coords, const float* feats,
                          const int64_t* pcounts, int64_t n, const int32_t* n_dev, void* ws_ptr, size_t ws_bytes,
-                         bnv_stream_t stream_) {
+                         const bnv_integrate_extras_t* extras, bnv_stream_t stream_) {
   if (!vol_ok(vol) || n < 0) return BNV_ERR_INVALID_ARGUMENT;
   if (n == 0) return BNV_OK;
   if (!coords || !feats || !pcounts || !ws_ptr) return BNV_ERR_INVALID_ARGUMENT;
-  VolWs ws;
-  if (vol_ws_layout(n, (char*)ws_ptr, ws_bytes, &ws) > ws_bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  ws.error = vol->n_rows + 1;
-  hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(k_vol_integrate<false>, dim3(blocks_for(n, kIntThreads)), dim3(kIntThreads), 0, stream, *vol, coords, feats, pcounts, n, n_dev,
-                     ws.tile_state, next_epoch(), ws.error, IntegrateExtras{});
-  BNV_LAUNCH_CHECK();
-  return BNV_OK;
-}
-
-int bnv_volume_integrate_frame(const bnv_volume_t* vol, const int64_t* coords, const float* feats,
-                               const int64_t* pcounts, int64_t n, const int32_t* n_dev, void* ws_ptr, size_t ws_bytes,
-                               const bnv_integrate_extras_t* extras, bnv_stream_t stream_) {
-  if (!vol_ok(vol) || n < 0 || !extras) return BNV_ERR_INVALID_ARGUMENT;
-  if (n == 0) return BNV_OK;
-  if (!coords || !feats || !pcounts || !ws_ptr) return BNV_ERR_INVALID_ARGUMENT;
   IntegrateExtras X = {};
-  if (extras->shard_block) {
+  if (extras && extras->shard_block) {
     if (!extras->grid_host || extras->shard_block_capacity < 0) return BNV_ERR_INVALID_ARGUMENT;
     X.block = (ShardRec*)extras->shard_block;
     X.block_capacity = extras->shard_block_capacity;
     X.grid = *extras->grid_host;
   }
-  if (extras->lattice_ws) {
+  if (extras && extras->lattice_ws) {
     if (extras->stamp_epoch == 0) return BNV_ERR_INVALID_ARGUMENT;
     lattice_ws_frame_words(extras->lattice_ws, vol->row_capacity, &X.origin_stamp, &X.lattice_ctl);
     X.stamp_epoch = extras->stamp_epoch;
@@ -665,7 +649,9 @@ int bnv_volume_integrate_frame(const bnv_volume_t* vol, const int64_t* coords, c
   if (vol_ws_layout(n, (char*)ws_ptr, ws_bytes, &ws) > ws_bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
   ws.error = vol->n_rows + 1;
   hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(k_vol_integrate<true>, dim3(blocks_for(n, kIntThreads)), dim3(kIntThreads), 0, stream, *vol, coords, feats, pcounts, n, n_dev,
+  // (no extras: the instantiation without the stamp and record code)
+  auto kernel = !extras ? k_vol_integrate<false> : k_vol_integrate<true>;
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(n, kIntThreads)), dim3(kIntThreads), 0, stream, *vol, coords, feats, pcounts, n, n_dev,
                      ws.tile_state, next_epoch(), ws.error, X);
   BNV_LAUNCH_CHECK();
   return BNV_OK;

@@ -16,8 +16,8 @@ DEPTH_DTYPES = {torch.uint16: 0, torch.int16: 0, torch.float32: 1, torch.float64
 
 
 def conf_arg(conf, conf_level, shape, device, what):
-    """The (pointer, level) pair of a *_gated entry for a confidence map [H, W] (uint8 on the depth's device) or None.
-    Returns (tensor kept alive by the caller or None, pointer, level)."""
+    """The (conf, conf_level) pair of a depth entry for a confidence map [H, W] (uint8 on the depth's device) or None
+    (a NULL pointer: with level 0, no gate).  Returns (tensor kept alive by the caller or None, pointer, level)."""
     level = int(conf_level)
     if conf is None:
         return None, None, level            # level > 0 without a map: the entry refuses it (BNV_ERR_INVALID_ARGUMENT)
@@ -51,14 +51,10 @@ def depth_to_input_pts(depth, intr_mat, T_wc, max_depth=10.0, compact=True, conf
     ws = torch.empty(int(lib.bnv_depth_workspace_bytes(H, W)), dtype=torch.uint8, device=d.device)
     out = torch.empty((H * W, 6), dtype=torch.float32, device=d.device)
     n = torch.empty(1, dtype=torch.int32, device=d.device)           # written by the scan kernel
-    if c_ptr is None and level == 0:
-        fn = lib.bnv_depth_to_points if compact else lib.bnv_depth_to_points_padded   # padded: NaN rows behind n
-        _lib.check(fn(_lib.ptr(d), dt, H, W, K, T, float(max_depth), _lib.ptr(ws), ws.numel(),
-                                           _lib.ptr(out), _lib.ptr(n), _lib.stream_ptr()), "bnv_depth_to_points")
-    else:
-        fn = lib.bnv_depth_to_points_gated if compact else lib.bnv_depth_to_points_padded_gated
-        _lib.check(fn(_lib.ptr(d), dt, H, W, K, T, float(max_depth), c_ptr, level, _lib.ptr(ws), ws.numel(),
-                      _lib.ptr(out), _lib.ptr(n), _lib.stream_ptr()), "bnv_depth_to_points_gated")
+    # compact=False: NaN rows behind n (pad)
+    _lib.check(lib.bnv_depth_to_points(_lib.ptr(d), dt, H, W, K, T, float(max_depth), c_ptr, level, 0 if compact else 1,
+                                       _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.ptr(n), _lib.stream_ptr()),
+               "bnv_depth_to_points")
     if not compact:
         return out.unsqueeze(0), n
     return out[: int(n.item())].unsqueeze(0)

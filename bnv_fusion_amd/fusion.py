@@ -293,7 +293,7 @@ class LitFusionPointNet(nn.Module):
         _lib.check(lib.bnv_encode_begin(_lib.ptr(pts), n, C.byref(grid), *ws, _lib.stream_ptr()), "bnv_encode_begin")
         if between is not None:
             between()
-        _lib.check(lib.bnv_encode_finish(_lib.ptr(pts), n, C.byref(grid), _lib.ptr(self.pointnet_pack), *ws,
+        _lib.check(lib.bnv_encode_finish(_lib.ptr(pts), n, 0, C.byref(grid), _lib.ptr(self.pointnet_pack), *ws,
                                          _lib.ptr(feats), _lib.ptr(pcounts), _lib.ptr(flat_ids), _lib.ptr(grid_ids),
                                          cap, 1 if emit_all else 0, _lib.ptr(counters), _lib.stream_ptr()),
                    "bnv_encode_finish")
@@ -322,21 +322,15 @@ class LitFusionPointNet(nn.Module):
         T = (C.c_double * 16)(*np.asarray(T_wc, dtype=np.float64).reshape(-1))
         ws = (_lib.ptr(self._enc_ws), self._enc_ws.numel(), self._enc_ws_points)
         c, c_ptr, level = conf_arg(conf, conf_level, (H, W), d.device, "encode_depth_async")
-        if c_ptr is None and level == 0:
-            _lib.check(lib.bnv_encode_begin_depth(_lib.ptr(d), DEPTH_DTYPES[d.dtype], H, W, K, T, float(max_depth),
-                                                  C.byref(grid), *ws, _lib.ptr(pts), _lib.stream_ptr()),
-                       "bnv_encode_begin_depth")
-        else:
-            _lib.check(lib.bnv_encode_begin_depth_gated(_lib.ptr(d), DEPTH_DTYPES[d.dtype], H, W, K, T,
-                                                        float(max_depth), c_ptr, level, C.byref(grid), *ws,
-                                                        _lib.ptr(pts), _lib.stream_ptr()),
-                       "bnv_encode_begin_depth_gated")
+        _lib.check(lib.bnv_encode_begin_depth(_lib.ptr(d), DEPTH_DTYPES[d.dtype], H, W, K, T, float(max_depth), c_ptr,
+                                              level, C.byref(grid), *ws, _lib.ptr(pts), _lib.stream_ptr()),
+                   "bnv_encode_begin_depth")
         if between is not None:
             between()
-        _lib.check(lib.bnv_encode_finish_image(_lib.ptr(pts), n, W, C.byref(grid), _lib.ptr(self.pointnet_pack), *ws,
-                                               _lib.ptr(feats), _lib.ptr(pcounts), _lib.ptr(flat_ids),
-                                               _lib.ptr(grid_ids), cap, 0, _lib.ptr(counters), _lib.stream_ptr()),
-                   "bnv_encode_finish_image")
+        _lib.check(lib.bnv_encode_finish(_lib.ptr(pts), n, W, C.byref(grid), _lib.ptr(self.pointnet_pack), *ws,
+                                         _lib.ptr(feats), _lib.ptr(pcounts), _lib.ptr(flat_ids), _lib.ptr(grid_ids),
+                                         cap, 0, _lib.ptr(counters), _lib.stream_ptr()),
+                   "bnv_encode_finish")
         return feats, pcounts, flat_ids, grid_ids, counters, cap, pts.unsqueeze(0)
 
     def encode_pointcloud(self, input_pts, n_xyz, bound_min, bound_max, voxel_size, return_dense=True):
@@ -412,11 +406,10 @@ class LitFusionPointNet(nn.Module):
         variant = 2 if global_coords else (0 if self.interpolate_decode else 1)
         nf1 = torch.empty((n, 8), dtype=torch.float32, device=q.device) if variant else None
         status = torch.zeros(2, dtype=torch.int32, device=q.device)
-        _lib.check(lib.bnv_decode_dense_mode(_lib.ptr(fg), _lib.ptr(pw), dims, float(np.float32(voxel_size)),
-                                             self.min_pts_in_grid, _lib.ptr(self.nerf.sdf_pack), _lib.ptr(q), n, variant,
-                                             _lib.model_mode(self) + 1, _lib.ptr(out),
-                                             _lib.ptr(nf1) if variant else None, _lib.ptr(status),
-                                             _lib.stream_ptr()), "bnv_decode_dense_mode")
+        _lib.check(lib.bnv_decode_dense(_lib.ptr(fg), _lib.ptr(pw), dims, float(np.float32(voxel_size)),
+                                        self.min_pts_in_grid, _lib.ptr(self.nerf.sdf_pack), _lib.ptr(q), n, variant,
+                                        _lib.model_mode(self) + 1, _lib.ptr(out), _lib.ptr(nf1) if variant else None,
+                                        _lib.ptr(status), _lib.stream_ptr()), "bnv_decode_dense")
         if int(status[1]) == 5:
             raise RuntimeError("decode_feature_grid_w_pts: a feature is outside the range the split-f16 MLP arithmetic "
                                "is certified for (or not finite); call bnv_set_mlp_mode(0) (exact fp32) for this grid")

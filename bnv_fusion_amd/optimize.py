@@ -77,7 +77,7 @@ def _ray_loss(pred, target, weight, n_valid):
     loss = torch.zeros(1, dtype=torch.float32, device=pred.device)
     g = torch.empty_like(pred)
     _lib.check(_lib.load().bnv_ray_loss(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(n_valid),
-                                        int(pred.numel()), _lib.ptr(loss), _lib.ptr(g), _lib.stream_ptr()),
+                                        int(pred.numel()), 0, _lib.ptr(loss), _lib.ptr(g), _lib.stream_ptr()),
                "bnv_ray_loss")
     return loss, g
 
@@ -254,9 +254,9 @@ def ray_batch_step(volume, rays, nerf, truncated_units, truncated_dist, ray_max_
             # tiny-cuda-nn decoder: its own forward / backward kernels, all splits per launch
             p = volume.decode_pts_splits(pts, nerf, sdf_delta, split_samples)
             g = torch.empty_like(p)
-            _lib.check(_lib.load().bnv_ray_loss_splits(
+            _lib.check(_lib.load().bnv_ray_loss(
                 _lib.ptr(p), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(n_valid), n * S, split_samples,
-                _lib.ptr(loss2), _lib.ptr(g), _lib.stream_ptr()), "bnv_ray_loss_splits")
+                _lib.ptr(loss2), _lib.ptr(g), _lib.stream_ptr()), "bnv_ray_loss")
             volume.decode_pts_backward_splits(pts, nerf, g, grad, split_samples)
             if pred is not None:
                 pred.copy_(p.view(n, S))

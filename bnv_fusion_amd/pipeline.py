@@ -247,13 +247,8 @@ class FramePipe:
             K = (C.c_double * 9)(*np.asarray(frame["intr_mat"], dtype=np.float64)[:3, :3].reshape(-1))
             T = (C.c_double * 16)(*np.asarray(frame["T_wc"], dtype=np.float64).reshape(-1))
             self._keep[s] = (d, col, conf)
-            if conf_ptr is None and conf_level == 0:
-                _lib.check(lib.bnv_frame_begin_depth(self._h, s, _lib.ptr(d), self._dtypes[d.dtype], H, W, K, T,
-                                                     _lib.ptr(col)), "bnv_frame_begin_depth")
-            else:
-                _lib.check(lib.bnv_frame_begin_depth_gated(self._h, s, _lib.ptr(d), self._dtypes[d.dtype], H, W, K, T,
-                                                           conf_ptr, conf_level, _lib.ptr(col)),
-                           "bnv_frame_begin_depth_gated")
+            _lib.check(lib.bnv_frame_begin_depth(self._h, s, _lib.ptr(d), self._dtypes[d.dtype], H, W, K, T, conf_ptr,
+                                                 conf_level, _lib.ptr(col)), "bnv_frame_begin_depth")
         self._busy[s] = True
         self._slot_mode[s] = mode
         self._next = (s + 1) % self.n_slots

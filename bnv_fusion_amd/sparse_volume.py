@@ -310,20 +310,18 @@ class SparseVolume:
         pcounts = pcounts.reshape(-1).long().contiguous()
         self._reserve(n)
         ws = self._workspace(n)
+        ex = None
         if stamp_origins:
             lws, epoch = self._lattice_workspace(n)          # (behind _reserve: growth re-makes this workspace)
             ex = _lib.IntegrateExtras()
             ex.lattice_ws = lws.data_ptr()
             ex.stamp_epoch = epoch
-            _lib.check(self._lib.bnv_volume_integrate_frame(C.byref(self._struct()), _lib.ptr(coords), _lib.ptr(feats),
-                                                            _lib.ptr(pcounts), n, _lib.ptr(n_dev), _lib.ptr(ws),
-                                                            ws.numel(), C.byref(ex), _lib.stream_ptr()),
-                       "bnv_volume_integrate_frame")
+        _lib.check(self._lib.bnv_volume_integrate(C.byref(self._struct()), _lib.ptr(coords), _lib.ptr(feats),
+                                                  _lib.ptr(pcounts), n, _lib.ptr(n_dev), _lib.ptr(ws), ws.numel(),
+                                                  C.byref(ex) if stamp_origins else None, _lib.stream_ptr()),
+                   "bnv_volume_integrate")
+        if stamp_origins:
             self._stamped = (epoch, coords.data_ptr(), n)
-        else:
-            _lib.check(self._lib.bnv_volume_integrate(C.byref(self._struct()), _lib.ptr(coords), _lib.ptr(feats),
-                                                      _lib.ptr(pcounts), n, _lib.ptr(n_dev), _lib.ptr(ws), ws.numel(),
-                                                      _lib.stream_ptr()), "bnv_volume_integrate")
         self._rows_upper += n
         if n_dev is not None:
             self._inflight += n
@@ -488,10 +486,10 @@ class SparseVolume:
         f, w, _, lim = self._snapshot()
         d, keep = self._delta(sdf_delta)
         out = torch.empty(int(c.shape[0]), dtype=torch.float32, device=self._dev)
-        _lib.check(self._lib.bnv_decode_pts_splits(
+        _lib.check(self._lib.bnv_decode_pts(
             C.byref(self._struct()), C.byref(grid), _lib.ptr(f), _lib.ptr(w), int(lim), _lib.ptr(nerf.sdf_pack),
             _lib.ptr(c), int(c.shape[0]), 0, C.byref(d), _lib.ptr(self._split_mask()), int(split_samples),
-            _lib.ptr(out), _lib.stream_ptr()), "bnv_decode_pts_splits")
+            _lib.ptr(out), _lib.stream_ptr()), "bnv_decode_pts")
         return out
 
     def decode_pts_backward_splits(self, pts, nerf, grad_sdf, grad_features, split_samples):
@@ -500,11 +498,11 @@ class SparseVolume:
         c = pts.detach().reshape(-1, 3).float().contiguous()
         g = grad_sdf.detach().reshape(-1).float().contiguous()
         assert grad_features.shape == f.shape and grad_features.is_contiguous()
-        _lib.check(self._lib.bnv_decode_pts_backward_splits(
+        _lib.check(self._lib.bnv_decode_pts_backward(
             C.byref(self._struct()), C.byref(grid), _lib.ptr(f), _lib.ptr(w), int(lim), _lib.ptr(nerf.sdf_pack),
             _lib.ptr(nerf.sdf_bwd_pack), _lib.ptr(c), int(c.shape[0]), 0, _lib.ptr(self._split_mask()),
             int(split_samples), _lib.ptr(g), _lib.ptr(grad_features), _lib.stream_ptr()),
-            "bnv_decode_pts_backward_splits")
+            "bnv_decode_pts_backward")
 
     def decode_pts_backward(self, coords, nerf, grad_sdf, grad_features, is_coords=False):
         """Accumulates d(sum(grad_sdf * decode_pts(coords))) / d features into ``grad_features`` [M, 8] (the
@@ -519,7 +517,8 @@ class SparseVolume:
         _lib.check(self._lib.bnv_decode_pts_backward(
             C.byref(self._struct()), C.byref(grid), _lib.ptr(f), _lib.ptr(w), int(lim),
             _lib.ptr(nerf.sdf_pack), _lib.ptr(nerf.sdf_bwd_pack), _lib.ptr(c), int(c.shape[0]),
-            1 if is_coords else 0, _lib.ptr(g), _lib.ptr(grad_features), _lib.stream_ptr()), "bnv_decode_pts_backward")
+            1 if is_coords else 0, None, 0, _lib.ptr(g), _lib.ptr(grad_features), _lib.stream_ptr()),
+            "bnv_decode_pts_backward")
 
     # ---- decode ------------------------------------------------------------------------------------
     def _delta(self, sdf_delta):
@@ -566,8 +565,8 @@ class SparseVolume:
         out = torch.empty(n, dtype=torch.float32, device=self._dev)
         _lib.check(self._lib.bnv_decode_pts(C.byref(self._struct()), C.byref(grid), _lib.ptr(f), _lib.ptr(w),
                                             int(lim), _lib.ptr(nerf.sdf_pack), _lib.ptr(c), n,
-                                            1 if is_coords else 0, C.byref(d), _lib.ptr(out), _lib.stream_ptr()),
-                   "bnv_decode_pts")
+                                            1 if is_coords else 0, C.byref(d), None, 0, _lib.ptr(out),
+                                            _lib.stream_ptr()), "bnv_decode_pts")
         return out.reshape(shape[:-1] + [1])
 
     def decode_lattice(self, origins, nerf, sdf_delta=None, query_tensor=True, n_dev=None, prestamped=False):
@@ -588,18 +587,13 @@ class SparseVolume:
             if stamped != (self._lattice_epoch, o.data_ptr(), n) or self._lattice_ws is None:
                 raise _lib.BnvError("decode_lattice(prestamped=True) needs the origins of the integrate(..., "
                                     "stamp_origins=True) right before it")
-            _lib.check(self._lib.bnv_decode_lattice_stamped(
-                C.byref(self._struct()), C.byref(grid), _lib.ptr(f), _lib.ptr(w), int(lim),
-                _lib.ptr(nerf.sdf_pack), _lib.ptr(o), n, _lib.ptr(n_dev), C.byref(d), _lib.ptr(self._lattice_ws),
-                self._lattice_ws.numel(), self._lattice_epoch, _lib.ptr(out), _lib.stream_ptr()),
-                "bnv_decode_lattice_stamped")
-            return out
-        self._lattice_workspace(n)
+        else:
+            self._lattice_workspace(n)
         _lib.check(self._lib.bnv_decode_lattice(C.byref(self._struct()), C.byref(grid), _lib.ptr(f),
                                                 _lib.ptr(w), int(lim), _lib.ptr(nerf.sdf_pack), _lib.ptr(o), n,
                                                 _lib.ptr(n_dev), C.byref(d), _lib.ptr(self._lattice_ws),
-                                                self._lattice_ws.numel(),
-                                                self._lattice_epoch, _lib.ptr(out), _lib.stream_ptr()),
+                                                self._lattice_ws.numel(), self._lattice_epoch, 1 if prestamped else 0,
+                                                _lib.ptr(out), _lib.stream_ptr()),
                    "bnv_decode_lattice")
         return out
 
@@ -783,7 +777,8 @@ class _DecodePts(torch.autograd.Function):
         _lib.check(volume._lib.bnv_decode_pts_backward(
             C.byref(volume._struct()), C.byref(grid), _lib.ptr(f), _lib.ptr(w), int(lim),
             _lib.ptr(nerf.sdf_pack), _lib.ptr(nerf.sdf_bwd_pack), _lib.ptr(c), int(c.shape[0]),
-            1 if ctx.is_coords else 0, _lib.ptr(g), _lib.ptr(grad_f), _lib.stream_ptr()), "bnv_decode_pts_backward")
+            1 if ctx.is_coords else 0, None, 0, _lib.ptr(g), _lib.ptr(grad_f), _lib.stream_ptr()),
+            "bnv_decode_pts_backward")
         return grad_f, None, None, None, None, None
 
 

@@ -47,11 +47,11 @@ class TSDFVolume:
         org = (C.c_float * 3)(*self._vol_origin.tolist())
         intr = (C.c_float * 9)(*np.asarray(cam_intr, dtype=np.float64)[:3, :3].reshape(-1).astype(np.float32).tolist())
         pose = (C.c_float * 16)(*np.asarray(cam_pose, dtype=np.float64).reshape(-1).astype(np.float32).tolist())
-        fn = self._lib.bnv_tsdf_integrate_u16 if u16 else self._lib.bnv_tsdf_integrate
-        _lib.check(fn(
+        _lib.check(self._lib.bnv_tsdf_integrate(
             _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color if col is not None else None), dim, org,
-            np.float32(self._voxel_size), np.float32(self._trunc_margin), _lib.ptr(depth), _lib.ptr(col), im_h, im_w,
-            intr, pose, float(obs_weight), float(max_depth or 0.0), _lib.ptr(gate), _lib.stream_ptr()), "bnv_tsdf_integrate")
+            np.float32(self._voxel_size), np.float32(self._trunc_margin), _lib.ptr(depth), 0 if u16 else 1,
+            _lib.ptr(col), im_h, im_w, intr, pose, float(obs_weight), float(max_depth or 0.0), _lib.ptr(gate),
+            _lib.stream_ptr()), "bnv_tsdf_integrate")
 
     def _fold_color(self, color_im):
         """[H, W, 3] colour in [0, 255] -> the folded b*65536 + g*256 + r image of fusion.py:223-224 (or None)."""

@@ -1,7 +1,7 @@
 // capi_host.cpp -- the hot path driven from a plain C++ host through include/bnv_fusion.h: no Python, no PyTorch.
 // Memory comes from hipMalloc, the stream is a hipStream_t, the weights are the packed arrays the Python side also
 // uploads (written to a directory by `python -m bnv_fusion_amd.export_packs`).  Per frame: uint16 depth image ->
-// bnv_encode_begin_depth + bnv_encode_finish_image -> bnv_volume_integrate -> bnv_decode_lattice; one line per frame
+// bnv_encode_begin_depth + bnv_encode_finish -> bnv_volume_integrate -> bnv_decode_lattice; one line per frame
 // with the counters and order-sensitive checksums of the outputs (tests/test_gpu_capi_host.py compares them with the
 // Python path on the same frames).
 //
@@ -167,12 +167,13 @@ int main(int argc, char** argv) {
     HIP_OK(hipMemcpyAsync(depth, d.data(), d.size(), hipMemcpyHostToDevice, stream));
     // front end + voxelisation + sorted-unique | point encoder + per-voxel mean + filter + repack
     BNV_OK_OR_DIE(bnv_encode_begin_depth(depth, /*uint16 millimetres*/ 0, m.H, m.W, m.K, poses + 16 * k, m.max_depth,
-                                         &m.grid, enc_ws, enc_ws_bytes, n_pts, pts, stream));
-    BNV_OK_OR_DIE(bnv_encode_finish_image(pts, n_pts, m.W, &m.grid, pointnet_pack, enc_ws, enc_ws_bytes, n_pts, feats,
-                                          pcounts, flat_ids, grid_ids, out_cap, 0, counters, stream));
+                                         /*no confidence map*/ nullptr, 0, &m.grid, enc_ws, enc_ws_bytes, n_pts, pts,
+                                         stream));
+    BNV_OK_OR_DIE(bnv_encode_finish(pts, n_pts, m.W, &m.grid, pointnet_pack, enc_ws, enc_ws_bytes, n_pts, feats, pcounts,
+                                    flat_ids, grid_ids, out_cap, 0, counters, stream));
     // running-average upsert of the frame's voxels; the count stays on the device
     BNV_OK_OR_DIE(bnv_volume_integrate(&vol, grid_ids, feats, pcounts, out_cap, &counters->n_out, vol_ws, vol_ws_bytes,
-                                       stream));
+                                       /*extras*/ nullptr, stream));
     bnv_encode_counters_t c;
     HIP_OK(hipMemcpyAsync(&c, counters, sizeof(c), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
@@ -184,7 +185,8 @@ int main(int argc, char** argv) {
     if (c.n_out > 0) {
       // the 3x3x3 SDF lattice of every voxel the frame touched
       BNV_OK_OR_DIE(bnv_decode_lattice(&vol, &m.grid, vol.features, vol.weights, vol.row_capacity, sdfmlp_pack, grid_ids,
-                                       c.n_out, nullptr, nullptr, lat_ws, lat_ws_bytes, ++epoch, sdf, stream));
+                                       c.n_out, nullptr, nullptr, lat_ws, lat_ws_bytes, ++epoch, /*prestamped*/ 0, sdf,
+                                       stream));
       std::vector<int64_t> ids_h((size_t)c.n_out * 3);
       std::vector<float> sdf_h((size_t)c.n_out * 27);
       HIP_OK(hipMemcpyAsync(ids_h.data(), grid_ids, ids_h.size() * 8, hipMemcpyDeviceToHost, stream));

@@ -222,30 +222,21 @@ int bnv_probe_spin(int n_blocks, int64_t cycles, void* stream);
  * arithmetic in the reference's order, rounded once to float32; out_pts [n_out, 6] holds the valid
  * pixels (0 < depth < max_depth) in row-major order, capacity H*W rows; n_out is a device int32. */
 size_t bnv_depth_workspace_bytes(int H, int W);
+/* pad != 0: the rows [n_out, H*W) of out_pts are set to NaN by the same launch (a caller that hands the whole
+ * H*W-row buffer on without reading n_out -- the encoder's bounds mask drops NaN rows -- needs no separate fill).
+ * Depth-confidence gate (FusionInferenceDatasetARKit, fusion_inference_dataset.py:242-306): conf [H,W] uint8 on the
+ * device (ARKit: 0 / 1 / 2); a pixel is a row when 0 < depth < max_depth AND conf >= conf_level.  The confidence
+ * removes rows only: the normals' Sobel stencil still reads the depth of rejected neighbours.  conf NULL with
+ * conf_level 0: no gate; conf NULL with conf_level > 0 (or conf_level < 0) is BNV_ERR_INVALID_ARGUMENT. */
 int bnv_depth_to_points(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                        const double* T_wc_host, double max_depth, void* ws, size_t ws_bytes,
-                        float* out_pts, int32_t* n_out, bnv_stream_t stream);
-/* The same, and the rows [n_out, H*W) of out_pts are set to NaN by the same launch (a caller that hands the whole
- * H*W-row buffer on without reading n_out -- the encoder's bounds mask drops NaN rows -- needs no separate fill). */
-int bnv_depth_to_points_padded(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                               const double* T_wc_host, double max_depth, void* ws, size_t ws_bytes,
-                               float* out_pts, int32_t* n_out, bnv_stream_t stream);
-/* Both with a depth-confidence gate (FusionInferenceDatasetARKit, fusion_inference_dataset.py:242-306): conf [H,W]
- * uint8 on the device (ARKit: 0 / 1 / 2); a pixel is a row when 0 < depth < max_depth AND conf >= conf_level.  The
- * confidence removes rows only: the normals' Sobel stencil still reads the depth of rejected neighbours.  conf NULL
- * with conf_level 0 is the ungated entry; conf NULL with conf_level > 0 (or conf_level < 0) is
- * BNV_ERR_INVALID_ARGUMENT. */
-int bnv_depth_to_points_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                              const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
-                              void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out, bnv_stream_t stream);
-int bnv_depth_to_points_padded_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                                     const double* T_wc_host, double max_depth, const uint8_t* conf,
-                                     int conf_level, void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out,
-                                     bnv_stream_t stream);
+                        const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level, int pad,
+                        void* ws, size_t ws_bytes, float* out_pts, int32_t* n_out, bnv_stream_t stream);
 
 /* ---- TSDF side fusion: TSDFVolume.integrate (third_parties/fusion.py:68-141, called per frame from
- * run_e2e.py:99-109).  tsdf / weight / color [dx,dy,dz] f32 (color may be NULL); depth_im [h,w] f32 metres
- * (0 = invalid); color_im [h,w] f32 folded b*65536+g*256+r or NULL; intr 3x3 and pose 4x4 row-major f32 on
+ * run_e2e.py:99-109).  tsdf / weight / color [dx,dy,dz] f32 (color may be NULL); depth [h,w] (0 = invalid) with the
+ * front end's dtype codes: 1 = float32 metres, 0 = uint16 millimetres as the dataset stores them, converted per sample
+ * as depth_mm / 1000 (common.py:93) inside the kernel -- no float copy of the frame; any other depth_dtype is
+ * BNV_ERR_INVALID_ARGUMENT; color_im [h,w] f32 folded b*65536+g*256+r or NULL; intr 3x3 and pose 4x4 row-major f32 on
  * the HOST; trunc_margin = 5 * voxel_size in the reference.  max_depth > 0: samples with depth >= max_depth are
  * invalid too -- the reference's loader zeroes them before the frame reaches either fusion (common.py:110-113 with
  * max_depth = model.ray_tracer.ray_max_dist, fusion_inference_dataset.py:28); <= 0: no cut.  gate: device int32 or
@@ -253,18 +244,11 @@ int bnv_depth_to_points_padded_gated(const void* depth, int depth_dtype, int H, 
  * encode found no in-bounds point (run_e2e.py:91-92), and the pipelined host does not know that count yet. */
 int bnv_tsdf_integrate(float* tsdf, float* weight, float* color, const int32_t dim_host[3],
                        const float origin_host[3], float voxel_size, float trunc_margin,
-                       const float* depth_im, const float* color_im, int im_h, int im_w,
-                       const float intr_host[9], const float pose_host[16], float obs_weight,
-                       float max_depth, const int32_t* gate, bnv_stream_t stream);
-/* The same with the depth image as the dataset stores it: uint16 millimetres, converted per sample as
- * depth_mm / 1000 (common.py:93) inside the kernel -- no float copy of the frame. */
-int bnv_tsdf_integrate_u16(float* tsdf, float* weight, float* color, const int32_t dim_host[3],
-                       const float origin_host[3], float voxel_size, float trunc_margin,
-                       const uint16_t* depth_mm, const float* color_im, int im_h, int im_w,
+                       const void* depth, int depth_dtype, const float* color_im, int im_h, int im_w,
                        const float intr_host[9], const float pose_host[16], float obs_weight,
                        float max_depth, const int32_t* gate, bnv_stream_t stream);
 /* n_frames (<= BNV_TSDF_BATCH_MAX) consecutive uint16 depth frames in ONE launch: identical to n_frames calls of
- * bnv_tsdf_integrate_u16 in order.  depth_mm: HOST array of device pointers; color / color_im: the colour volume and a
+ * bnv_tsdf_integrate (depth_dtype 0) in order.  depth_mm: HOST array of device pointers; color / color_im: the colour volume and a
  * HOST array of device pointers to the frames' folded colour images (entries may be NULL), or both NULL;
  * intr_host [n_frames, 9] and pose_host [n_frames, 16] row-major f32 on the host. */
 #define BNV_TSDF_BATCH_MAX 8
@@ -284,16 +268,14 @@ int bnv_tsdf_integrate_batch_u16(float* tsdf, float* weight, float* color, const
  *                      from the volume AFTER the frame's upsert; capacity >= the bound bnv_encode_begin leaves in the
  *                      workspace for this rank;
  *   bnv_shard_install  blocks = world blocks back to back (the all-gather's output); the own block is skipped; a
- *                      sender's overflow flag sets the volume's sticky error word to 4. */
+ *                      sender's overflow flag sets the volume's sticky error word to 4.  The header count of
+ *                      own_send_block (the block this rank contributed to `blocks`; NULL: none) is set back to 0: the
+ *                      block is then ready for the records bnv_volume_integrate appends for the next frame. */
 #define BNV_SHARD_RECORD_BYTES 48
 int bnv_shard_pack(const bnv_volume_t* vol, const bnv_grid_t* grid, const int64_t* coords, int64_t n,
                    const int32_t* n_dev, void* block, int64_t capacity, bnv_stream_t stream);
 int bnv_shard_install(const bnv_volume_t* vol, const bnv_grid_t* grid, const void* blocks, int world,
-                      int64_t capacity, bnv_stream_t stream);
-/* The same, and the header count of own_send_block (the block this rank contributed to `blocks`; may be NULL) is set
- * back to 0: the block is then ready for the records bnv_volume_integrate_frame appends for the next frame. */
-int bnv_shard_install_reset(const bnv_volume_t* vol, const bnv_grid_t* grid, const void* blocks, int world,
-                            int64_t capacity, void* own_send_block, bnv_stream_t stream);
+                      int64_t capacity, void* own_send_block, bnv_stream_t stream);
 
 /* ---- encode: LitFusionPointNet.encode_pointcloud (local_point_fusion.py:81-165) ------------ */
 
@@ -305,8 +287,6 @@ int bnv_shard_install_reset(const bnv_volume_t* vol, const bnv_grid_t* grid, con
  * (about 1290^3).  The reference's torch.unique is O(points) with int64 ids (local_point_fusion.py:116-119) and has
  * no such bound; every BASELINE configuration (<= 512^3) is far inside it. */
 size_t bnv_encode_workspace_bytes(int64_t max_points, const int32_t n_xyz[3]);
-/* Zero the scratch (once after allocation; encode leaves it clean for the next frame). */
-int bnv_encode_workspace_reset(void* ws, size_t ws_bytes, bnv_stream_t stream);
 
 /* Packed-weight sizes (floats) of the fp32 point encoder / SDF decoder; layouts in DESIGN.md. */
 size_t bnv_pointnet_pack_floats(void);
@@ -317,10 +297,15 @@ size_t bnv_sdfmlp_pack_floats(void);
  *   begin   bounds mask (local_point_fusion.py:94-104), 8-corner voxelisation (:153-165, modules.py:586-655) into a
  *           grid bitmap, sorted-unique of the touched voxels by bitmap rank (torch.unique, :118-119);
  *   finish  the point encoder on every (point, corner) pair, per-voxel mean, min-points filter, ordered repack.
- * bnv_encode_begin_depth fuses the depth front end in front of `begin` (depth arguments as bnv_depth_to_points): it
- * writes input_pts rows IN PIXEL ORDER into out_pts [H*W, 6] (NaN rows for invalid pixels -- nothing is compacted; the
- * bounds mask drops NaN rows wherever they are) and marks the voxels from registers; n_points of the matching
- * finish call is H*W.
+ * bnv_encode_begin_depth fuses the depth front end in front of `begin` (depth, conf and conf_level as for
+ * bnv_depth_to_points; conf NULL with conf_level 0: no gate): it writes input_pts rows IN PIXEL ORDER into out_pts
+ * [H*W, 6] (NaN rows for invalid or rejected pixels -- nothing is compacted; the bounds mask drops NaN rows wherever
+ * they are) and marks the voxels from registers; n_points of the matching finish call is H*W.
+ * bnv_encode_finish, image_width: > 0 with n_points a multiple of it says that the points are the pixels of an image in
+ * row-major order (the out_pts of bnv_encode_begin_depth) and lets the encoder work on 2-D pixel patches (the
+ * tiny-cuda-nn encoder accumulates a patch's per-voxel sums on chip before touching the global accumulators:
+ * neighbouring pixels in BOTH directions share voxels); 0 = no such structure.  Results are identical either way
+ * (integer sums).
  * With spatial sharding (grid.shard_world > 1) `begin` also leaves, at byte offset bnv_encode_shard_counts_offset()
  * of the workspace, int32[shard_world]: the number of touched BOUNDARY voxels each rank owns (voxels with a foreign
  * voxel in their 3x3x3 neighbourhood).  The voxelisation is replicated, so every rank holds the same numbers: an
@@ -329,43 +314,13 @@ size_t bnv_sdfmlp_pack_floats(void);
 int bnv_encode_begin(const float* input_pts, int64_t n_points, const bnv_grid_t* grid_host, void* ws, size_t ws_bytes,
                      int64_t ws_max_points, bnv_stream_t stream);
 int bnv_encode_begin_depth(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                           const double* T_wc_host, double max_depth, const bnv_grid_t* grid_host, void* ws,
-                           size_t ws_bytes, int64_t ws_max_points, float* out_pts, bnv_stream_t stream);
-/* bnv_encode_begin_depth with the confidence gate of bnv_depth_to_points_gated (a rejected pixel is a NaN row). */
-int bnv_encode_begin_depth_gated(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
-                                 const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
-                                 const bnv_grid_t* grid_host, void* ws, size_t ws_bytes, int64_t ws_max_points,
-                                 float* out_pts, bnv_stream_t stream);
-int bnv_encode_finish(const float* input_pts, int64_t n_points, const bnv_grid_t* grid_host,
+                           const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level,
+                           const bnv_grid_t* grid_host, void* ws, size_t ws_bytes, int64_t ws_max_points,
+                           float* out_pts, bnv_stream_t stream);
+int bnv_encode_finish(const float* input_pts, int64_t n_points, int image_width, const bnv_grid_t* grid_host,
                       const float* pointnet_pack, void* ws, size_t ws_bytes, int64_t ws_max_points,
                       float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids, int64_t* out_grid_ids,
                       int64_t out_capacity, int emit_all, bnv_encode_counters_t* counters, bnv_stream_t stream);
-/* bnv_encode_finish for a frame whose points are the pixels of an image in row-major order (the out_pts of
- * bnv_encode_begin_depth): image_width > 0 with n_points a multiple of it lets the encoder work on 2-D pixel patches
- * (the tiny-cuda-nn encoder accumulates a patch's per-voxel sums on chip before touching the global accumulators:
- * neighbouring pixels in BOTH directions share voxels); 0 = no such structure (bnv_encode_finish).  Results are
- * identical either way (integer sums). */
-int bnv_encode_finish_image(const float* input_pts, int64_t n_points, int image_width, const bnv_grid_t* grid_host,
-                            const float* pointnet_pack, void* ws, size_t ws_bytes, int64_t ws_max_points,
-                            float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids, int64_t* out_grid_ids,
-                            int64_t out_capacity, int emit_all, bnv_encode_counters_t* counters, bnv_stream_t stream);
-/* The same with the persistent point-encoder kernel launched on at most max_workgroups workgroups (one per CU;
- * 0 = every CU).  The encoder and the SDF-decoder kernels each fill a CU's LDS, so nothing else runs on a CU one of
- * them holds; the frame pipeline leaves a share of the CUs to the small kernels of the other streams this way. */
-int bnv_encode_finish_image_wg(const float* input_pts, int64_t n_points, int image_width, const bnv_grid_t* grid_host,
-                               const float* pointnet_pack, void* ws, size_t ws_bytes, int64_t ws_max_points,
-                               float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids, int64_t* out_grid_ids,
-                               int64_t out_capacity, int emit_all, bnv_encode_counters_t* counters,
-                               int max_workgroups, bnv_stream_t stream);
-/* The same in two parts that may go to different streams (the caller orders them: part 2 behind part 1):
- * parts & 1 = the point-encoder MLP + scatter, parts & 2 = finalize (mean, filter, ordered compaction, counters, clean
- * workspace); parts = 3 is bnv_encode_finish_image_wg.  The frame pipeline with CU-masked streams keeps only the
- * persistent MLP kernel on the encoder's share of the CUs. */
-int bnv_encode_finish_image_parts(const float* input_pts, int64_t n_points, int image_width,
-                                  const bnv_grid_t* grid_host, const float* pointnet_pack, void* ws, size_t ws_bytes,
-                                  int64_t ws_max_points, float* out_feats, int64_t* out_pcounts, int64_t* out_flat_ids,
-                                  int64_t* out_grid_ids, int64_t out_capacity, int emit_all,
-                                  bnv_encode_counters_t* counters, int max_workgroups, int parts, bnv_stream_t stream);
 size_t bnv_encode_shard_counts_offset(void);
 
 /* input_pts [n_points, 6] f32 (world xyz, world normal).
@@ -403,16 +358,13 @@ size_t bnv_volume_workspace_bytes(int64_t max_keys);
  * feats [n,8], pcounts [n] i64.  If n_dev (a device int32, e.g. &counters->n_out of the encode that
  * produced the inputs) is not NULL the element count is read on the device and n is only the
  * capacity the launch is sized for -- no host synchronisation between encode and integrate. */
-int bnv_volume_integrate(const bnv_volume_t* vol_host, const int64_t* coords, const float* feats,
-                         const int64_t* pcounts, int64_t n, const int32_t* n_dev, void* ws,
-                         size_t ws_bytes, bnv_stream_t stream);
-
-/* bnv_volume_integrate for the per-frame pipeline: the same single launch also (a) marks the rows it touches as the
- * ORIGINS of the frame's lattice decode in `lattice_ws` (the workspace bnv_decode_lattice_stamped is then called with,
- * same stamp_epoch != 0; NULL: no stamps) and (b) with a sharded volume appends the boundary voxels among the
- * upserted keys -- with the values just written -- to shard_block as bnv_shard_pack would (header count must be 0 or
- * hold the records of this frame so far: bnv_shard_install_reset leaves it so; NULL: no records).  Replaces the launches
- * of k_lattice_stamp and bnv_shard_pack (local_point_fusion.py:647-673 has no counterpart of either: new design). */
+/* extras_host (NULL: none of this) serves the per-frame pipeline: the same single launch then also (a) marks the rows
+ * it touches as the ORIGINS of the frame's lattice decode in `lattice_ws` (the workspace bnv_decode_lattice is then
+ * called with, prestamped and with the same stamp_epoch != 0; NULL: no stamps) and (b) with a sharded volume appends
+ * the boundary voxels among the upserted keys -- with the values just written -- to shard_block as bnv_shard_pack would
+ * (header count must be 0 or hold the records of this frame so far: bnv_shard_install leaves it so; NULL: no records).
+ * Replaces the launches of k_lattice_stamp and bnv_shard_pack (local_point_fusion.py:647-673 has no counterpart of
+ * either: new design). */
 typedef struct bnv_integrate_extras {
   void* shard_block;             /* (1 + shard_block_capacity) records of BNV_SHARD_RECORD_BYTES, or NULL */
   int64_t shard_block_capacity;
@@ -420,9 +372,9 @@ typedef struct bnv_integrate_extras {
   void* lattice_ws;              /* lattice-decode workspace sized for vol->row_capacity, or NULL */
   int32_t stamp_epoch;
 } bnv_integrate_extras_t;
-int bnv_volume_integrate_frame(const bnv_volume_t* vol_host, const int64_t* coords, const float* feats,
-                               const int64_t* pcounts, int64_t n, const int32_t* n_dev, void* ws, size_t ws_bytes,
-                               const bnv_integrate_extras_t* extras_host, bnv_stream_t stream);
+int bnv_volume_integrate(const bnv_volume_t* vol_host, const int64_t* coords, const float* feats,
+                         const int64_t* pcounts, int64_t n, const int32_t* n_dev, void* ws, size_t ws_bytes,
+                         const bnv_integrate_extras_t* extras_host, bnv_stream_t stream);
 
 /* The same for up to BNV_VOLUME_BATCH_MAX consecutive frames in ONE call (4 launches): the result -- row order, row
  * count, features, weights -- is identical to calling bnv_volume_integrate once per frame in order (the replay loop of
@@ -462,11 +414,12 @@ typedef struct bnv_sdf_delta {
 } bnv_sdf_delta_t;
 
 /* SparseVolume.decode_pts (sparse_volume.py:768-833) at arbitrary points: coords [n,3] f32,
- * voxel units if is_coords else world; out [n] f32. */
+ * voxel units if is_coords else world; out [n] f32.  split_mask NULL: one split, the plain weights (split_samples is
+ * then ignored); else the ray splits of an optimiser step, see bnv_volume_count_optim_splits below. */
 int bnv_decode_pts(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host, const float* features,
-                   const float* weights, int64_t row_limit, const float* sdfmlp_pack,
-                   const float* coords, int64_t n, int is_coords, const bnv_sdf_delta_t* delta_host,
-                   float* out_sdf, bnv_stream_t stream);
+                   const float* weights, int64_t row_limit, const float* sdfmlp_pack, const float* coords,
+                   int64_t n, int is_coords, const bnv_sdf_delta_t* delta_host, const uint32_t* split_mask,
+                   int64_t split_samples, float* out_sdf, bnv_stream_t stream);
 
 /* Backward of bnv_decode_pts with respect to the volume features -- the autograd edge the global
  * optimiser relies on: run_e2e.py:111-162 turns volume.features into an nn.Parameter and
@@ -475,14 +428,15 @@ int bnv_decode_pts(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host, co
  * ACCUMULATED into (the caller zeroes it).  The decoder weights are frozen and the points are data, so
  * nothing else receives gradient; sdf_delta is additive and does not enter.  sdfmlp_bwd_pack holds the
  * transposed layers: bnv_sdfmlp_bwd_pack_floats() floats for the fp32 decoder (weights.py: pack_sdf_mlp_bwd),
- * bnv_sdfmlp_tcnn_bwd_pack_floats() for the tiny-cuda-nn decoder of MLP mode 2 (pack_sdf_tcnn_bwd). */
+ * bnv_sdfmlp_tcnn_bwd_pack_floats() for the tiny-cuda-nn decoder of MLP mode 2 (pack_sdf_tcnn_bwd).  split_mask /
+ * split_samples as for bnv_decode_pts. */
 size_t bnv_sdfmlp_bwd_pack_floats(void);
 size_t bnv_sdfmlp_tcnn_bwd_pack_floats(void);
 int bnv_decode_pts_backward(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host,
                             const float* features, const float* weights, int64_t row_limit,
                             const float* sdfmlp_pack, const float* sdfmlp_bwd_pack, const float* coords,
-                            int64_t n, int is_coords, const float* grad_sdf, float* grad_features,
-                            bnv_stream_t stream);
+                            int64_t n, int is_coords, const uint32_t* split_mask, int64_t split_samples,
+                            const float* grad_sdf, float* grad_features, bnv_stream_t stream);
 
 /* ---- dataset formats (host only) ----------------------------------------------------------------- */
 
@@ -505,9 +459,10 @@ int bnv_ray_samples(const float* uv, const float* gt_pts, const float* ray_mask,
                     const float* u_fine, const float* u_coarse, int n, int n_fine, int n_coarse,
                     float truncated_dist, float* pts, float* target, float* weight, bnv_stream_t stream);
 /* loss += sum_i weight_i |pred_i - target_i| / *n_valid (device scalars; loss is accumulated atomically)
- * and grad_i = d loss / d pred_i. */
-int bnv_ray_loss(const float* pred, const float* target, const float* weight, const float* n_valid,
-                 int64_t m, float* loss, float* grad, bnv_stream_t stream);
+ * and grad_i = d loss / d pred_i.  split_samples 0: one split; > 0: sample i belongs to split i / split_samples and
+ * n_valid holds one scalar per split. */
+int bnv_ray_loss(const float* pred, const float* target, const float* weight, const float* n_valid, int64_t m,
+                 int64_t split_samples, float* loss, float* grad, bnv_stream_t stream);
 /* SparseVolume.count_optim on the 8 corner voxels of m sample points (render_utils.py:491-493,
  * sparse_volume.py:602-622): weights[row] += 1 once per distinct row. */
 int bnv_volume_count_optim_pts(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host, const float* pts,
@@ -522,9 +477,9 @@ int bnv_volume_count_optim_pts(const bnv_volume_t* vol_host, const bnv_grid_t* g
  * q / split_samples (at most 31 splits);
  *   bnv_volume_count_optim_splits  bit s of split_mask[row] (uint32 per row of the to_tensor() snapshot, zeroed once by
  *                                  the caller) = split s touches the row; weights are NOT changed yet;
- *   bnv_decode_pts_splits / bnv_decode_pts_backward_splits   bnv_decode_pts / _backward whose corner weights are
+ *   bnv_decode_pts / bnv_decode_pts_backward   with that split_mask, the corner weights are
  *                                  weights[row] + 1 per split <= the query's that touches the row (exact fp32 adds);
- *   bnv_ray_loss_splits            bnv_ray_loss with one n_valid per split;
+ *   bnv_ray_loss                   with split_samples, one n_valid per split;
  *   bnv_optim_step                 forward + loss + backward of all samples in ONE kernel (fp32 decoder, split-f16
  *                                  arithmetic as bnv_decode_pts_backward): the L1 loss is elementwise, so a query's
  *                                  gradient is known in the tile that computes its value.  loss_and_counter: float[2],
@@ -537,17 +492,6 @@ int bnv_volume_count_optim_splits(const bnv_volume_t* vol_host, const bnv_grid_t
                                   int is_coords, int64_t row_limit, int64_t split_samples, uint32_t* split_mask,
                                   bnv_stream_t stream);
 int bnv_volume_apply_split_counts(float* weights, uint32_t* split_mask, int64_t n_rows, bnv_stream_t stream);
-int bnv_decode_pts_splits(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host, const float* features,
-                          const float* weights, int64_t row_limit, const float* sdfmlp_pack, const float* coords,
-                          int64_t n, int is_coords, const bnv_sdf_delta_t* delta_host, const uint32_t* split_mask,
-                          int64_t split_samples, float* out_sdf, bnv_stream_t stream);
-int bnv_decode_pts_backward_splits(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host, const float* features,
-                                   const float* weights, int64_t row_limit, const float* sdfmlp_pack,
-                                   const float* sdfmlp_bwd_pack, const float* coords, int64_t n, int is_coords,
-                                   const uint32_t* split_mask, int64_t split_samples, const float* grad_sdf,
-                                   float* grad_features, bnv_stream_t stream);
-int bnv_ray_loss_splits(const float* pred, const float* target, const float* weight, const float* n_valid, int64_t m,
-                        int64_t split_samples, float* loss, float* grad, bnv_stream_t stream);
 int bnv_optim_step(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host, const float* features,
                    const float* weights, int64_t row_limit, const float* sdfmlp_pack, const float* sdfmlp_bwd_pack,
                    const float* pts, int64_t n, int is_coords, const bnv_sdf_delta_t* delta_host,
@@ -619,30 +563,14 @@ size_t bnv_decode_lattice_count_offset(int64_t row_capacity);
 /* The same decode for the 3x3x3 lattice {-0.5,0,0.5}^3 around n integer voxel origins
  * (SparseVolume.meshlize's decode_pts call, sparse_volume.py:717-738): out [n,27] f32.
  * Evaluates the MLP once per (corner voxel, local offset) instead of 8x per lattice point.
- * n_dev: optional device-side count as in bnv_volume_integrate (n = capacity). */
+ * n_dev: optional device-side count as in bnv_volume_integrate (n = capacity).
+ * prestamped != 0: bnv_volume_integrate (extras->lattice_ws, stamp_epoch) has already stamped the origins in `ws` with
+ * this `epoch` (the origins are exactly the keys of that upsert): one launch less.  0: the call stamps them itself. */
 int bnv_decode_lattice(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host,
                        const float* features, const float* weights, int64_t row_limit,
                        const float* sdfmlp_pack, const int64_t* origins, int64_t n, const int32_t* n_dev,
                        const bnv_sdf_delta_t* delta_host, void* ws, size_t ws_bytes, int32_t epoch,
-                       float* out_sdf, bnv_stream_t stream);
-
-/* bnv_decode_lattice for origins that bnv_volume_integrate_frame has already stamped in `ws` with this `epoch` (the
- * origins are exactly the keys of that upsert): one launch less. */
-int bnv_decode_lattice_stamped(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host,
-                               const float* features, const float* weights, int64_t row_limit,
-                               const float* sdfmlp_pack, const int64_t* origins, int64_t n, const int32_t* n_dev,
-                               const bnv_sdf_delta_t* delta_host, void* ws, size_t ws_bytes, int32_t epoch,
-                               float* out_sdf, bnv_stream_t stream);
-
-/* bnv_decode_lattice_stamped without its last stage: neighbour rows, live entries and the table MLP on `stream`; the
- * caller finishes with bnv_lattice_blend(vol, grid, origins, n, n_dev, delta, ws, ws_bytes, out_sdf, other_stream)
- * behind an event -- the blend reads nothing but `ws`, so on a stream of its own it leaves `stream` free for the next
- * frame's upsert (the frame pipeline does this; that next frame must then decode into another workspace). */
-int bnv_decode_lattice_stamped_tables(const bnv_volume_t* vol_host, const bnv_grid_t* grid_host,
-                                      const float* features, const float* weights, int64_t row_limit,
-                                      const float* sdfmlp_pack, const int64_t* origins, int64_t n,
-                                      const int32_t* n_dev, void* ws, size_t ws_bytes, int32_t epoch,
-                                      bnv_stream_t stream);
+                       int prestamped, float* out_sdf, bnv_stream_t stream);
 
 /* The three stages of bnv_decode_lattice, callable separately so that a sharded volume can exchange
  * corner-voxel tables between them (bnv_fusion_amd/distributed.py).  They share one workspace:
@@ -683,18 +611,14 @@ size_t bnv_decode_lattice_list_offset(int64_t n_voxels, int64_t row_capacity);
  * out_feats (optional, NEAREST / GLOBAL) [n,8]: the features the evaluation used (the reference's second return value).
  * status (optional, device int32[2]): status[1] = 5 when a feature leaves the certified range of the split arithmetic
  * (the range guard of bnv_decode_pts, which reports through the volume's error word).
+ * mlp_mode: the arithmetic mode of the call in the bnv_grid_t.mlp_mode encoding (0 = process default,
+ * BNV_GRID_MLP_MODE(m) = mode m).
  * gradient=True is not offered: the reference's branch (:367-369) reads an undefined name and cannot run. */
 enum { BNV_DENSE_CORNERS = 0, BNV_DENSE_NEAREST = 1, BNV_DENSE_GLOBAL = 2 };
 int bnv_decode_dense(const float* feat_grid, const float* pts_weight, const int32_t dims_host[3],
                      float voxel_size, int32_t min_pts_in_grid, const float* sdfmlp_pack,
-                     const float* voxel_coords, int64_t n, int32_t variant, float* out_sdf, float* out_feats,
-                     int32_t* status, bnv_stream_t stream);
-/* The same with the arithmetic mode stated per call (bnv_grid_t.mlp_mode encoding: 0 = process default,
- * BNV_GRID_MLP_MODE(m) = mode m); bnv_decode_dense = mlp_mode 0. */
-int bnv_decode_dense_mode(const float* feat_grid, const float* pts_weight, const int32_t dims_host[3],
-                          float voxel_size, int32_t min_pts_in_grid, const float* sdfmlp_pack,
-                          const float* voxel_coords, int64_t n, int32_t variant, int32_t mlp_mode, float* out_sdf,
-                          float* out_feats, int32_t* status, bnv_stream_t stream);
+                     const float* voxel_coords, int64_t n, int32_t variant, int32_t mlp_mode, float* out_sdf,
+                     float* out_feats, int32_t* status, bnv_stream_t stream);
 
 /* ---- the per-frame chain as one object: NeuralMap.integrate (run_e2e.py:78-109: encode_pointcloud -> track_n_pts ->
  * _integrate -> TSDF side fusion) followed by the lattice decode of the frame's voxels (sparse_volume.py:697-738),
@@ -792,16 +716,14 @@ int bnv_frame_pipe_destroy(bnv_frame_pipe_t* pipe);
  * was begun with through its decode.  The mode config.grid carried at creation applies until this is called. */
 int bnv_frame_pipe_set_mlp_mode(bnv_frame_pipe_t* pipe, int32_t grid_mlp_mode);
 /* depth as bnv_encode_begin_depth (dtype 0 = uint16 mm, 1 = float32 m); color_im: folded colour image or NULL.  The
- * device buffers of a frame (depth, color_im, input_pts) are read by kernels enqueued up to the frame's bnv_frame_upsert
- * (the TSDF side fusion): they must stay valid until the frame's result is in. */
+ * device buffers of a frame (depth, conf, color_im, input_pts) are read by kernels enqueued up to the frame's
+ * bnv_frame_upsert (the TSDF side fusion): they must stay valid until the frame's result is in.
+ * conf / conf_level: the confidence gate of bnv_encode_begin_depth (conf NULL with conf_level 0: no gate).  The TSDF
+ * side fusion ignores the confidence, as the reference's does; it still runs only when the frame keeps an in-bounds
+ * point after the gate. */
 int bnv_frame_begin_depth(bnv_frame_pipe_t* pipe, int slot, const void* depth, int depth_dtype, int H, int W,
-                          const double* intr_host, const double* T_wc_host, const float* color_im);
-/* bnv_frame_begin_depth with the confidence gate of bnv_encode_begin_depth_gated (conf: a device buffer under the same
- * lifetime rule as depth).  The TSDF side fusion ignores the confidence, as the reference's does; it still runs only
- * when the frame keeps an in-bounds point after the gate. */
-int bnv_frame_begin_depth_gated(bnv_frame_pipe_t* pipe, int slot, const void* depth, int depth_dtype, int H, int W,
-                                const double* intr_host, const double* T_wc_host, const uint8_t* conf,
-                                int conf_level, const float* color_im);
+                          const double* intr_host, const double* T_wc_host, const uint8_t* conf, int conf_level,
+                          const float* color_im);
 int bnv_frame_begin_points(bnv_frame_pipe_t* pipe, int slot, const float* input_pts, int64_t n_points);
 /* The TSDF side fusion (run_e2e.py:99-109) of a frame begun with bnv_frame_begin_points that ALSO carries its depth
  * image -- the reference dataset's frames hold input_pts, rgbd, intr_mat and T_wc together (run_e2e.py:78-109) -- gated
@@ -1246,7 +1168,7 @@ int bnv_icp_align(const void* depth, int depth_dtype, int32_t H, int32_t W, cons
  * Sobel makes poor normals of such a staircase.  A bilateral filter whose spatial and range kernels are Tukey
  * biweights: float64 arithmetic in the order below, no transcendental function, one rounding to float32 at the end.
  *
- * depth [H, W] / depth_dtype / max_depth / conf / conf_level as for bnv_depth_to_points_gated.  z(q) is the depth of
+ * depth [H, W] / depth_dtype / max_depth / conf / conf_level as for bnv_depth_to_points.  z(q) is the depth of
  * pixel q in metres as a double (uint16: (double)u / 1000.0); q is valid when 0 < z(q) < max_depth (NaN and inf are
  * not) and, with a confidence map, conf[q] >= conf_level.  Spatial weight of the offset (dy, dx), r = radius:
  * a = 1.0 - (double)(dy dy + dx dx) / (double)((r + 1) (r + 1)), wa = a a; taps with a <= 0 are skipped.  For a valid
@@ -1291,7 +1213,7 @@ int bnv_depth_filter(const void* depth, int depth_dtype, int H, int W, double ma
  * normals f32 [V, 3] (bnv_mesh_vertex_normals' output or the caller's own, unit length or zero).
  * A frame (bnv_mesh_color_frame_t, host memory; the images are device memory and only read): depth [height, width],
  * depth_dtype 0 = uint16 millimetres (d = (double)mm / 1000.0) or 1 = float32 metres; conf uint8 [height, width] or
- * NULL with conf_level as for bnv_depth_to_points_gated (a pixel is kept when conf >= conf_level; a level without a
+ * NULL with conf_level as for bnv_depth_to_points (a pixel is kept when conf >= conf_level; a level without a
  * map is refused); rgb uint8 [color_height, color_width, 3]; K = (fx, fy, cx, cy) of the depth image and K_color of
  * the colour image (the same pose); T_cw float64 [12]: rows 0..2 of the WORLD-TO-CAMERA matrix, inverted by the caller
  * in float64; center: the camera centre in the world (the translation of T_wc).  Integer pixel coordinates are pixel
@@ -1346,8 +1268,8 @@ int bnv_mesh_color_resolve(const void* workspace, int64_t ws_bytes, int64_t n_ve
 
 /* ---- Volume planning (bnv_fusion_amd/csrc/plan.hip; bnv_fusion_amd/plan.py: VolumePlanner, plan_volume): the extent
  * of the scene and the per-frame voxel statistics of candidate voxel sizes, from the depth frames themselves and before
- * anything is fused.  Both passes read a frame exactly as bnv_encode_begin_depth_gated does: depth / depth_dtype /
- * max_depth / conf / conf_level as for bnv_depth_to_points_gated, a pixel is valid when 0 < z < max_depth and (with a
+ * anything is fused.  Both passes read a frame exactly as bnv_encode_begin_depth does: depth / depth_dtype /
+ * max_depth / conf / conf_level as for bnv_depth_to_points, a pixel is valid when 0 < z < max_depth and (with a
  * map) conf >= conf_level, and its world point p is the front end's float32 point (float32 pixel rays, float64
  * products with T_wc in the written order, one rounding).  Everything is integer counting: any schedule gives the same
  * numbers; tests/plan_restatement.py restates both passes in numpy.

@@ -160,11 +160,11 @@ def test_gated_entries_refuse_a_level_without_a_map():
     K = (C.c_double * 9)(*np.eye(3).reshape(-1))
     T = (C.c_double * 16)(*np.eye(4).reshape(-1))
     fake = C.c_void_p(256)
-    for fn in (lib.bnv_depth_to_points_gated, lib.bnv_depth_to_points_padded_gated):
+    for pad in (0, 1):
         for conf, level in ((None, 2), (None, 1), (fake, -1)):
-            rc = fn(fake, 0, 8, 8, K, T, 3.0, conf, level, fake, 1 << 20, fake, fake, None)
-            assert rc == INVALID_ARGUMENT, (conf, level, rc)
+            rc = lib.bnv_depth_to_points(fake, 0, 8, 8, K, T, 3.0, conf, level, pad, fake, 1 << 20, fake, fake, None)
+            assert rc == INVALID_ARGUMENT, (pad, conf, level, rc)
     g = _lib.Grid()
-    rc = lib.bnv_encode_begin_depth_gated(fake, 0, 8, 8, K, T, 3.0, None, 2, C.byref(g), fake, 1 << 20, 64, fake, None)
+    rc = lib.bnv_encode_begin_depth(fake, 0, 8, 8, K, T, 3.0, None, 2, C.byref(g), fake, 1 << 20, 64, fake, None)
     assert rc != 0      # (without bnv_init: BNV_ERR_NOT_INITIALISED comes first)
-    assert lib.bnv_frame_begin_depth_gated(None, 0, fake, 0, 8, 8, K, T, None, 2, None) == INVALID_ARGUMENT
+    assert lib.bnv_frame_begin_depth(None, 0, fake, 0, 8, 8, K, T, None, 2, None) == INVALID_ARGUMENT

@@ -38,6 +38,27 @@ def test_library_exports_every_symbol():
     assert rc != 0
 
 
+RETIRED = [
+    "bnv_depth_to_points_padded", "bnv_depth_to_points_gated", "bnv_depth_to_points_padded_gated",
+    "bnv_encode_begin_depth_gated", "bnv_frame_begin_depth_gated", "bnv_encode_finish_image",
+    "bnv_encode_finish_image_wg", "bnv_encode_finish_image_parts", "bnv_decode_lattice_stamped",
+    "bnv_decode_lattice_stamped_tables", "bnv_decode_dense_mode", "bnv_tsdf_integrate_u16", "bnv_shard_install_reset",
+    "bnv_volume_integrate_frame", "bnv_decode_pts_splits", "bnv_decode_pts_backward_splits", "bnv_ray_loss_splits",
+    "bnv_encode_workspace_reset",
+]
+
+
+def test_retired_entries_are_gone():
+    """One entry per operation: the suffixed variants folded into their base entries are neither declared nor exported."""
+    from bnv_fusion_amd import _lib
+    assert len(RETIRED) == len(set(RETIRED)) == 18
+    declared = _declared()
+    lib = _lib.load()
+    for name in RETIRED:
+        assert name not in declared, name
+        assert not hasattr(lib, name), name
+
+
 def test_product_has_no_cpu_fallback():
     """The product path must fail loudly off-GPU, not compute on the CPU."""
     import torch
@@ -66,15 +87,33 @@ def test_argument_validation_without_a_gpu():
     lib = _lib.load()
     INVALID = -1
     v = _lib.Volume()                                   # all-null volume
-    assert lib.bnv_volume_integrate(C.byref(v), None, None, None, 4, None, None, 0, None) == INVALID
+    assert lib.bnv_volume_integrate(C.byref(v), None, None, None, 4, None, None, 0, C.byref(_lib.IntegrateExtras()),
+                                    None) == INVALID
+    assert lib.bnv_volume_integrate(C.byref(v), None, None, None, 4, None, None, 0, None, None) == INVALID   # NULL extras
     assert lib.bnv_volume_integrate_batch(C.byref(v), 1, None, None, None, None, None, None, None, None, 0, None) == INVALID
     assert lib.bnv_volume_clear(C.byref(v), None) == INVALID
-    assert lib.bnv_tsdf_integrate_u16(None, None, None, None, None, 0.025, 0.125, None, None, 480, 640, None, None, 1.0,
-                                      3.0, None, None) == INVALID
+    for dtype in (0, 1):
+        assert lib.bnv_tsdf_integrate(None, None, None, None, None, 0.025, 0.125, None, dtype, None, 480, 640, None, None,
+                                      1.0, 3.0, None, None) == INVALID
+    p8 = C.c_void_p(8)                                  # a non-null pointer no refused call dereferences
+    assert lib.bnv_tsdf_integrate(p8, p8, None, (C.c_int32 * 3)(4, 4, 4), (C.c_float * 3)(), 0.025, 0.125, p8, 2, None, 4,
+                                  4, (C.c_float * 9)(), (C.c_float * 16)(), 1.0, 3.0, None, None) == INVALID   # float64
     assert lib.bnv_tsdf_integrate_batch_u16(C.c_void_p(8), C.c_void_p(8), None, (C.c_int32 * 3)(4, 4, 4),
                                             (C.c_float * 3)(), 0.025, 0.125, 9, C.c_void_p(8), None, 4, 4,
                                             (C.c_float * 9)(), (C.c_float * 16)(), 1.0, 3.0, None) == INVALID   # > 8 frames
-    assert lib.bnv_depth_to_points(None, 0, 480, 640, None, None, 10.0, None, 0, None, None, None) == INVALID
+    for pad in (0, 1):
+        assert lib.bnv_depth_to_points(None, 0, 480, 640, None, None, 10.0, None, 0, pad, None, 0, None, None,
+                                       None) == INVALID
+    # a split mask with 32 splits (31 at most) on an otherwise well-formed call: invalid.  This entry asks for bnv_init
+    # first, so a process that has not initialised a device is told that instead -- refused either way, before any launch
+    ok =_lib.Volume(slot_keys=8, slot_rows=8, n_slots=16, n_feats=8)
+    for n, split_samples, refused in ((32, 1, True), (32, 0, True), (0, 1, False)):
+        rc = lib.bnv_decode_pts(C.byref(ok), C.byref(_lib.Grid()), p8, p8, 1, p8, p8, n, 1, None, p8, split_samples, p8,
+                                None)
+        if lib.bnv_num_compute_units() <= 0:
+            assert rc == -4                             # BNV_ERR_NOT_INITIALISED
+        else:
+            assert rc == (INVALID if refused else 0)    # (n = 0 returns before anything is read)
     assert lib.bnv_png_unfilter(None, 1, 1, 2, None) != 0
     assert lib.bnv_set_option(b"no_such_option", 1) == INVALID
     assert lib.bnv_set_mlp_mode(7) == INVALID

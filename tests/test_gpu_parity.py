@@ -1333,8 +1333,9 @@ def test_decode_pts_ragged_sizes_and_all_masked_vs_oracle(bnv, model, golden_vol
 
 
 def test_tsdf_uint16_depth_equals_float_metres(bnv):
-    """bnv_tsdf_integrate_u16 converts the dataset's millimetres inside the kernel (correctly rounded / 1000, what
-    cv2.imread(...) / 1000. -> float32 gives in the reference): same volume as feeding float32 metres."""
+    """bnv_tsdf_integrate with depth_dtype 0 (uint16) converts the dataset's millimetres inside the kernel (correctly
+    rounded / 1000, what cv2.imread(...) / 1000. -> float32 gives in the reference): same volume as feeding float32
+    metres."""
     from bnv_fusion_amd import synthetic
     from bnv_fusion_amd.tsdf import TSDFVolume
     bounds = np.array([[-1.27, 1.27]] * 3)
@@ -1349,7 +1350,7 @@ def test_tsdf_uint16_depth_equals_float_metres(bnv):
 
 
 def test_tsdf_batch_equals_frame_by_frame(bnv):
-    """bnv_tsdf_integrate_batch_u16: 11 frames (two launches) against one bnv_tsdf_integrate_u16 per frame, bit
+    """bnv_tsdf_integrate_batch_u16: 11 frames (two launches) against one uint16 bnv_tsdf_integrate per frame, bit
     for bit; an all-zero depth frame in the middle."""
     from bnv_fusion_amd import synthetic
     from bnv_fusion_amd.tsdf import TSDFVolume

@@ -1,5 +1,5 @@
 """The per-frame chain behind the C object of csrc/pipeline.hip (FramePipe) and the kernels folded for it
-(bnv_volume_integrate_frame, bnv_decode_lattice_stamped, bnv_shard_install_reset); the volume workspace's look-back
+(bnv_volume_integrate with extras, bnv_decode_lattice prestamped, bnv_shard_install); the volume workspace's look-back
 words; the volume without its dense row index.  Everything is compared bit for bit (torch.equal) with the per-stage
 path the other GPU tests pin against the reference's goldens.  Needs a real MI355X: run with  -m gpu."""
 import os
@@ -127,7 +127,7 @@ def test_frame_pipe_grows_the_volume_mid_stream(bnv):
 
 
 def test_integrate_frame_packs_the_records_bnv_shard_pack_does(bnv):
-    """bnv_volume_integrate_frame on a sharded grid: the records it appends are the ones bnv_shard_pack lists for the
+    """bnv_volume_integrate with extras on a sharded grid: the records it appends are the ones bnv_shard_pack lists for the
     same keys after a plain upsert (as sets; record order is free), rows / values equal the plain upsert's."""
     import ctypes as C
     from bnv_fusion_amd import _lib, distributed as D
@@ -160,9 +160,9 @@ def test_integrate_frame_packs_the_records_bnv_shard_pack_does(bnv):
         x = _lib.IntegrateExtras()
         x.shard_block, x.shard_block_capacity, x.grid_host = blk_b.data_ptr(), m, C.pointer(b._grid)
         x.lattice_ws, x.stamp_epoch = lws.data_ptr(), ep
-        _lib.check(lib.bnv_volume_integrate_frame(C.byref(b._struct()), _lib.ptr(g), _lib.ptr(f), _lib.ptr(c), m, None,
-                                                  _lib.ptr(ws), ws.numel(), C.byref(x), _lib.stream_ptr()),
-                   "bnv_volume_integrate_frame")
+        _lib.check(lib.bnv_volume_integrate(C.byref(b._struct()), _lib.ptr(g), _lib.ptr(f), _lib.ptr(c), m, None,
+                                            _lib.ptr(ws), ws.numel(), C.byref(x), _lib.stream_ptr()),
+                   "bnv_volume_integrate")
         b._rows_upper += m
         ra = blk_a.view(m + 1, D.REC_WORDS).cpu().numpy()
         rb = blk_b.view(m + 1, D.REC_WORDS).cpu().numpy()
@@ -177,10 +177,10 @@ def test_integrate_frame_packs_the_records_bnv_shard_pack_does(bnv):
         sa = a.decode_lattice(g, model.nerf, query_tensor=False)
         sb = torch.empty((m, 27), dtype=torch.float32, device=DEV)
         d, _ = b._delta(None)
-        _lib.check(lib.bnv_decode_lattice_stamped(C.byref(b._struct()), C.byref(b._grid), _lib.ptr(b._features),
-                                                  _lib.ptr(b._weights), b._row_capacity, _lib.ptr(model.nerf.sdf_pack),
-                                                  _lib.ptr(g), m, None, C.byref(d), _lib.ptr(lws), lws.numel(), ep,
-                                                  _lib.ptr(sb), _lib.stream_ptr()), "bnv_decode_lattice_stamped")
+        _lib.check(lib.bnv_decode_lattice(C.byref(b._struct()), C.byref(b._grid), _lib.ptr(b._features),
+                                          _lib.ptr(b._weights), b._row_capacity, _lib.ptr(model.nerf.sdf_pack),
+                                          _lib.ptr(g), m, None, C.byref(d), _lib.ptr(lws), lws.numel(), ep, 1,
+                                          _lib.ptr(sb), _lib.stream_ptr()), "bnv_decode_lattice")
         assert torch.equal(sa, sb), k
 
 

@@ -303,8 +303,8 @@ def test_encode_pointcloud_vs_float64(bnv, model, orc, sd64, name):
 
 
 def test_encode_depth_vs_float64(bnv, model, orc, sd64):
-    """The depth entry (front end fused into the voxelisation, bnv_encode_finish_image) against the float64 encoder
-    run on the points that front end produced."""
+    """The depth entry (front end fused into the voxelisation, bnv_encode_finish with an image width) against the
+    float64 encoder run on the points that front end produced."""
     from bnv_fusion_amd import synthetic
     from bnv_fusion_amd.frontend import depth_to_input_pts
     dims, voxel = synthetic.GRID_DIMS[128]
@@ -331,8 +331,8 @@ def test_encode_depth_vs_float64(bnv, model, orc, sd64):
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", [1, 3])
 def test_frame_pipe_lattice_vs_float64(bnv, model, orc, sd64, mode):
-    """A NeuralMap frame through the frame pipe (bnv_decode_lattice_stamped_tables + a blend on a side stream)
-    against a float64 decode of the very volume the frame decoded."""
+    """A NeuralMap frame through the frame pipe (the prestamped lattice decode without its blend + a blend on a side
+    stream) against a float64 decode of the very volume the frame decoded."""
     from bnv_fusion_amd import synthetic
     dims = np.array([1.24] * 3)
     frames = []
