@@ -5,6 +5,11 @@
 // and each voxel is read-modified-written once: HBM-bound, 24 B per touched voxel (13.5 MB at the
 // reference's fixed 0.025 m grid over a 2.54 m volume -> microseconds).  fp32 arithmetic in the
 // reference kernel's order (compiled with -ffp-contract=off; nvcc would fuse some mul+add pairs).
+// Pinned: weight, tsdf and the folded colour volume of both kernels equal, bit for bit, the numpy float32
+// restatement of the CUDA kernel (oracle tsdf_integrate; tests/test_gpu_tsdf_fusion.py), whose CPU-fallback
+// flavour reproduces volumes captured from the reference (tests/golden/tsdf_color.npz).  The colour channels
+// round half away from zero (roundf) as the CUDA kernel does; the reference's CPU fallback rounds half to even.
+// Not pinned: a voxel with camera z == 0 exactly (non-finite pixel coordinate -> integer conversion).
 #include "bnv_common.hpp"
 
 namespace bnv {

@@ -521,19 +521,66 @@ def depth_to_input_pts(depth, intr, T_wc, max_depth=10.0):
     return out[mask.reshape(-1)]
 
 
-def tsdf_integrate(tsdf, weight, vol_origin, voxel_size, depth_im, cam_intr, cam_pose, obs_weight=1.0,
-                   cpu_path=False):
-    """TSDFVolume.integrate (third_parties/fusion.py).  tsdf / weight [X, Y, Z] float32 are updated in place;
-    colour is not restated.
+def _roundf(a):
+    """C's roundf on a float32 array: half away from zero (np.round is half to even).  |a| + 0.5 is exact below 2^23."""
+    return np.sign(a) * np.floor(np.abs(a) + np.float32(0.5))
 
-    Default: as the inline CUDA kernel computes it (:68-126) -- float32 throughout, un-fused multiply-adds,
-    transposed rotation, ``roundf`` (half away from zero) for the pixel; this is what the reference runs on a GPU
-    box and what csrc/tsdf.hip follows.  ``cpu_path=True``: as the reference's CPU fallback computes it
-    (:283-305) -- camera points through ``np.linalg.inv(cam_pose)`` in float64, ``np.round`` (half to even).
-    PIN: tests/golden/tsdf_40.npz was captured from that CPU fallback (make_golden_tsdf.py; numba shimmed as plain
-    Python); ``cpu_path=True`` reproduces it, and the default differs from it only in the ~1 % of voxels whose
-    projection falls within rounding distance of a pixel boundary."""
+
+def tsdf_fold_color(color_im):
+    """[H, W, 3] r, g, b in [0, 255] -> the folded single-channel float32 image floor(b*65536 + g*256 + r) that
+    TSDFVolume.integrate hands to either flavour (third_parties/fusion.py:222-223)."""
+    c = np.asarray(color_im).astype(np.float32)
+    return np.floor(c[..., 2] * np.float32(65536) + c[..., 1] * np.float32(256) + c[..., 0])
+
+
+def tsdf_unfold_color(color):
+    """Folded colour -> (b, g, r) float32, with ``floor`` as fusion.py:130-132 / :284-286."""
     f = np.float32
+    b = np.floor(color / f(65536))
+    g = np.floor((color - b * f(65536)) / f(256))
+    return b, g, color - b * f(65536) - g * f(256)
+
+
+def _tsdf_fuse_color(color, ok, folded_px, w_old, w_new, obs_weight, rnd):
+    """The running colour average of the voxels ``ok`` (fusion.py:129-140 / :283-294), float32 in both flavours:
+    per channel min(rnd((old * w_old + obs_weight * new) / w_new), 255), refolded.  ``w_old`` is the weight before
+    this frame's update."""
+    f = np.float32
+    old = tsdf_unfold_color(color[ok])
+    new = tsdf_unfold_color(folded_px)
+    b, g, r = (np.minimum(rnd((o * w_old + f(obs_weight) * n) / w_new), f(255.0)) for o, n in zip(old, new))
+    color[ok] = b * f(65536) + g * f(256) + r
+
+
+def tsdf_integrate(tsdf, weight, vol_origin, voxel_size, depth_im, cam_intr, cam_pose, obs_weight=1.0,
+                   cpu_path=False, color=None, color_im=None, max_depth=None, stats=None):
+    """TSDFVolume.integrate (third_parties/fusion.py).  tsdf / weight [X, Y, Z] float32 are updated in place, and so
+    is ``color`` [X, Y, Z] float32 (folded b*65536 + g*256 + r) when it is given together with ``color_im``
+    [H, W, 3]; without them colour is left alone.  ``max_depth``: samples at or beyond it are zeroed before use, as
+    the loader does before the frame reaches the reference's integrate (common.py:110-113).  ``stats`` (default
+    flavour): a dict that receives, added up over calls, how many voxels were behind the camera (``behind``), had
+    camera z exactly 0 (``cam_z_zero``), projected onto a zero sample (``zero_depth``), onto one that ``max_depth``
+    cut (``max_depth``) or lay beyond the truncation band (``truncated``): what a test's inputs exercise.
+
+    Default: as the inline CUDA kernel computes it (:68-141) -- float32 throughout, un-fused multiply-adds,
+    transposed rotation, ``roundf`` (half away from zero) for the pixel and for the colour channels; this is what
+    the reference runs on a GPU box and what csrc/tsdf.hip follows.  ``cpu_path=True``: as the reference's CPU
+    fallback computes it (:251-294) -- camera points through ``np.linalg.inv(cam_pose)`` in float64, ``np.round``
+    (half to even) for the pixel and for the colour channels.
+    PIN: tests/golden/tsdf_40.npz and tsdf_color.npz were captured from that CPU fallback (make_golden_tsdf.py; numba
+    shimmed as plain Python); ``cpu_path=True`` reproduces them, weight and colour exactly.  The default differs
+    from tsdf_40 only in the ~1 % of voxels whose projection falls within rounding distance of a pixel boundary, and
+    from tsdf_color's colour in the half of the observed voxels where a channel average ends in .5 (integer
+    channels, small weights).  The colour block of the default is the same float32 expression with ``roundf`` for
+    ``np.round``; no CUDA capture of it exists."""
+    f = np.float32
+    raw_depth_im = depth_im
+    if max_depth is not None:
+        depth_im = np.asarray(depth_im)
+        # the CUDA flavour tests the float32 sample the kernel receives, the fallback the loader's own array
+        depth_im = depth_im * (depth_im < max_depth) if cpu_path else \
+            depth_im.astype(f) * (depth_im.astype(f) < f(max_depth))
+    folded = tsdf_fold_color(color_im) if (color is not None and color_im is not None) else None
     X, Y, Z = tsdf.shape
     vx, vy, vz = np.meshgrid(np.arange(X), np.arange(Y), np.arange(Z), indexing="ij")
     org = np.asarray(vol_origin, dtype=f)
@@ -564,6 +611,8 @@ def tsdf_integrate(tsdf, weight, vol_origin, voxel_size, depth_im, cam_intr, cam
         w_new = (w_old + f(obs_weight)).astype(f)
         tsdf[ok] = ((w_old * tsdf[ok] + f(obs_weight) * dist[ok].astype(f)) / w_new).astype(f)
         weight[ok] = w_new
+        if folded is not None:
+            _tsdf_fuse_color(color, ok, folded[py[ok], px[ok]], w_old, w_new, obs_weight, np.round)
         return tsdf, weight
     t = [pt[i] - P[i, 3] for i in range(3)]
     cam = [(P[0, i] * t[0] + P[1, i] * t[1]) + P[2, i] * t[2] for i in range(3)]
@@ -576,6 +625,13 @@ def tsdf_integrate(tsdf, weight, vol_origin, voxel_size, depth_im, cam_intr, cam
     ok = (px >= 0) & (px < W) & (py >= 0) & (py < H) & ~(cam[2] < 0)
     d = np.zeros_like(cam[2])
     d[ok] = np.asarray(depth_im, dtype=f)[py[ok], px[ok]]
+    if stats is not None:       # why voxels were left out, summed over the calls that share ``stats``
+        raw = np.zeros_like(d)
+        raw[ok] = np.asarray(raw_depth_im, dtype=f)[py[ok], px[ok]]
+        cut = ok & (d == 0)
+        for key, n in (("behind", cam[2] < 0), ("cam_z_zero", cam[2] == 0), ("zero_depth", cut & (raw == 0)),
+                       ("max_depth", cut & (raw != 0)), ("truncated", ok & (d != 0) & (d - cam[2] < -trunc))):
+            stats[key] = stats.get(key, 0) + int(n.sum())
     ok &= d != 0
     diff = d - cam[2]
     ok &= ~(diff < -trunc)
@@ -584,6 +640,8 @@ def tsdf_integrate(tsdf, weight, vol_origin, voxel_size, depth_im, cam_intr, cam
     w_new = w_old + f(obs_weight)
     weight[ok] = w_new
     tsdf[ok] = (tsdf[ok] * w_old + f(obs_weight) * dist[ok]) / w_new
+    if folded is not None:
+        _tsdf_fuse_color(color, ok, folded[py[ok], px[ok]], w_old, w_new, obs_weight, _roundf)
     return tsdf, weight
 
 

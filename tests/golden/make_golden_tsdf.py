@@ -13,7 +13,15 @@ the transposed rotation in float32 and rounds half away from zero (roundf).  The
 tests compare against these goldens with a small tolerance and allow the handful of voxels whose projection lands
 exactly between two pixels.
 
-Only DATA is written (tests/golden/tsdf_40.npz).
+tsdf_color.npz is a second capture from the same fallback, for the colour volume and the options: a non-cubic
+15 x 17 x 20 volume at 0.04 m (5,100 voxels: 19 blocks of 256 threads and a partial one) with the camera INSIDE it, so
+some voxels lie behind the camera; six 24 x 32 frames of uint16-millimetre depth with a zeroed patch, random 8-bit
+colour from a seeded generator, ``obs_weight`` 2.5, generic (non-axis-aligned) poses so that no projection ties
+between two pixels.  The fallback rounds channel averages half to even (np.round), the CUDA kernel half away from
+zero (roundf): integer channels and small weights make exact .5 averages common, so the two differ in about half of
+the observed voxels -- which is what lets a test tell the two roundings apart.
+
+Only DATA is written (tests/golden/tsdf_40.npz, tests/golden/tsdf_color.npz).
 """
 import os
 import sys
@@ -27,6 +35,45 @@ sys.path.insert(0, os.path.join(HERE, "..", ".."))
 import ref_shims  # noqa: E402
 
 
+def _rodrigues(r):
+    """Rotation matrix of the axis-angle vector r."""
+    a = float(np.linalg.norm(r))
+    k = r / a
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
+
+
+def color_capture(ref_fusion):
+    bounds = np.array([[-0.30, 0.27], [-0.35, 0.33], [-0.2, 0.6]])
+    voxel, H, W, obs_weight = 0.04, 24, 32, 2.5
+    vol = ref_fusion.TSDFVolume(bounds.copy(), voxel_size=voxel, use_gpu=False)
+    assert tuple(vol._vol_dim) == (15, 17, 20)
+    rng = np.random.default_rng(2024)
+    intr = np.array([[27.3, 0.0, 15.37], [0.0, 26.9, 11.61], [0.0, 0.0, 1.0]])
+    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    depths_mm, colors, poses = [], [], []
+    for t in range(6):
+        T = np.eye(4)
+        T[:3, :3] = _rodrigues(rng.uniform(-0.12, 0.12, 3))
+        T[:3, 3] = np.array([0.013, -0.021, -0.047]) + rng.uniform(-0.03, 0.03, 3)      # inside the volume
+        mm = np.round(1000.0 * (0.34 + 0.07 * np.sin(u / 5.0 + 0.4 * t) * np.cos(v / 4.0) + 0.01 * t)).astype(np.uint16)
+        mm[5 + t:10 + t, 8:15] = 0                                                       # invalid patch
+        rgb = rng.integers(0, 256, size=(H, W, 3), dtype=np.uint8)
+        d = mm.astype(np.float32) / np.float32(1000)          # the float32 metres the HIP kernel makes of the uint16
+        vol.integrate(rgb, d, intr, T, obs_weight=obs_weight)
+        depths_mm.append(mm)
+        colors.append(rgb)
+        poses.append(T)
+    tsdf, color = vol.get_volume()
+    assert tsdf.dtype == np.float32 and color.dtype == np.float32 and vol._weight_vol_cpu.dtype == np.float32
+    np.savez_compressed(os.path.join(HERE, "tsdf_color.npz"), bounds=bounds, voxel_size=voxel, intr=intr,
+                        poses=np.stack(poses), depths_mm=np.stack(depths_mm), colors=np.stack(colors),
+                        obs_weight=obs_weight, tsdf=tsdf, weight=vol._weight_vol_cpu, color=color,
+                        origin=vol._vol_origin)
+    print("tsdf_color:", tsdf.shape, "observed voxels", int((vol._weight_vol_cpu > 0).sum()),
+          "weights up to", float(vol._weight_vol_cpu.max()))
+
+
 def main():
     ref_shims.install()
     nb = types.ModuleType("numba")
@@ -37,6 +84,7 @@ def main():
     from third_parties import fusion as ref_fusion
     assert ref_fusion.FUSION_GPU_MODE == 0
     from oracle import bnv_oracle as orc
+    color_capture(ref_fusion)
 
     bounds = np.array([[-0.5, 0.5], [-0.5, 0.5], [-0.5, 0.5]])
     vol = ref_fusion.TSDFVolume(bounds.copy(), voxel_size=0.025, use_gpu=False)
