@@ -122,12 +122,12 @@ def geo_forward(sd, x, num_layers=4):
     return F.linear(x, sd["nerf.fc_alpha.weight"], sd["nerf.fc_alpha.bias"])
 
 
-def forward_with_mask(sd, input_feats, mask):
-    """modules.py:774-783 -- MLP on the masked rows only, zeros elsewhere."""
+def forward_with_mask(sd, input_feats, mask, geo=None):
+    """modules.py:774-783 -- MLP on the masked rows only, zeros elsewhere.  ``geo``: as in decode_pts."""
     shapes = list(input_feats.shape)
     mask = mask.reshape(-1)
     flat = input_feats.reshape(-1, shapes[-1])
-    alpha = geo_forward(sd, flat[mask])
+    alpha = geo_forward(sd, flat[mask]) if geo is None else geo(flat[mask])
     out = torch.zeros_like(flat[:, :1], dtype=alpha.dtype)
     out[mask] = alpha
     return out.reshape(shapes[:-1] + [1])
@@ -322,10 +322,18 @@ def integrate(volume, fine_coords, fine_feats, fine_weights):
 # --------------------------------------------------------------------------- #
 
 
+def _scale_geo(alpha, voxel_size):
+    """Output of a ``geo`` callable times the voxel size: in fp16 for the fp16 network, in float64 for a reference."""
+    if alpha.dtype == torch.float64:
+        return alpha * voxel_size
+    return (alpha.half() * voxel_size).float()
+
+
 def decode_pts(volume, coords, sd, sdf_delta=None, is_coords=False, query_tensor=True, geo=None):
     """SparseVolume.decode_pts, sparse_volume.py:768-833.  coords [1, B, S, 3] -> [1, B, S, 1].
     ``geo``: alternative nerf.geo_forward (tcnn variant); its fp16 output keeps ``alpha * voxel_size`` in
-    fp16 as torch does for a half tensor times a python float."""
+    fp16 as torch does for a half tensor times a python float.  A ``geo`` that returns float64 is a precision
+    reference (tests/tcnn_restatement.py): its output is scaled in float64 and never rounded."""
     if not is_coords:
         coords = (coords - volume.min_coords) / volume.voxel_size
     neighbor_coords = get_neighbors(coords)                      # float corners [1, 8, B, S, 3]
@@ -342,7 +350,7 @@ def decode_pts(volume, coords, sd, sdf_delta=None, is_coords=False, query_tensor
         alpha = geo_forward(sd, nerf_in)
         alpha = alpha * volume.voxel_size
     else:
-        alpha = (geo(nerf_in).half() * volume.voxel_size).float()
+        alpha = _scale_geo(geo(nerf_in), volume.voxel_size)
     normalizer = torch.sum(weights_unmasked, dim=1, keepdim=True)
     weights_unmasked = weights_unmasked / normalizer
     alpha = torch.sum(alpha * weights_unmasked, dim=1)
@@ -368,13 +376,15 @@ def lattice_coords(origins, step_size=0.5):
 
 
 def decode_feature_grid_w_pts(sd, voxel_coords, feat_grid, pts_weight, voxel_size, min_pts_in_grid=8,
-                              global_coords=False, interpolate_decode=True):
+                              global_coords=False, interpolate_decode=True, geo=None):
     """LitFusionPointNet.decode_feature_grid_w_pts, local_point_fusion.py:265-367 (+ decode_implicit :372-379,
     LocalNeRFModel.forward(test=True) modules.py:941-960).  voxel_coords [1, Q, 3] -> sdf [1, Q], neighbor_feats.
     Defaults = the yaml configuration (global_coords=False, interpolate_decode=True, :281-329); the other two
     branches: nearest voxel (:288-292, 331-343) and global coordinates (:345-367, the signature default).
     Grids of another dtype than the float32 coordinates (float64 features: the precision reference) are sampled
-    with the sampling grid cast to theirs."""
+    with the sampling grid cast to theirs.  ``geo``: alternative nerf.geo_forward, scaled as in decode_pts (the global
+    branch returns its output unscaled)."""
+    scaled = (lambda a: a * voxel_size) if geo is None else (lambda a: _scale_geo(a, voxel_size))
     h, w, d = feat_grid.shape[-3:]
     res = torch.tensor([h, w, d])
     if global_coords:
@@ -385,7 +395,8 @@ def decode_feature_grid_w_pts(sd, voxel_coords, feat_grid, pts_weight, voxel_siz
         pw = F.grid_sample(pts_weight, g.to(pts_weight.dtype), mode="nearest", padding_mode="zeros", align_corners=True)
         pw = pw.squeeze(2).squeeze(2).permute(0, 2, 1)[..., 0]             # [1, Q]
         pts = voxel_coords / (res - 1)                                     # decode_implicit(normalize=False)
-        sdf = geo_forward(sd, torch.cat([xyz_encoding(pts[..., :3]), nf], dim=-1))[..., 0]
+        geo_in = torch.cat([xyz_encoding(pts[..., :3]), nf], dim=-1)
+        sdf = (geo_forward(sd, geo_in) if geo is None else geo(geo_in))[..., 0]
         sdf = torch.where(pw >= min_pts_in_grid, sdf, torch.ones_like(sdf) * voxel_size)
         return sdf, nf
     if not interpolate_decode:
@@ -400,7 +411,7 @@ def decode_feature_grid_w_pts(sd, voxel_coords, feat_grid, pts_weight, voxel_siz
         rel_xyz = (voxel_coords - nc) * voxel_size
         pts = rel_xyz / voxel_size                                         # decode_implicit(normalize=True)
         geo_in = torch.cat([xyz_encoding(pts[..., :3]), nf], dim=-1)
-        sdf = (forward_with_mask(sd, geo_in, pw >= min_pts_in_grid) * voxel_size)[..., 0]
+        sdf = scaled(forward_with_mask(sd, geo_in, pw >= min_pts_in_grid, geo))[..., 0]
         sdf = torch.where(pw > 0, sdf, torch.ones_like(sdf) * voxel_size)
         return sdf, nf
     neighbor_coords = get_neighbors(voxel_coords.unsqueeze(1), as_int=True).squeeze(2)  # [1, 8, Q, 3] i32
@@ -417,7 +428,7 @@ def decode_feature_grid_w_pts(sd, voxel_coords, feat_grid, pts_weight, voxel_siz
     rel_xyz = rel * voxel_size
     pts = rel_xyz / voxel_size                       # decode_implicit(normalize=True)
     geo_in = torch.cat([xyz_encoding(pts[..., :3]), nf], dim=-1)
-    sdf = forward_with_mask(sd, geo_in, pw >= min_pts_in_grid) * voxel_size
+    sdf = scaled(forward_with_mask(sd, geo_in, pw >= min_pts_in_grid, geo))
     sdf = torch.sum(sdf[..., 0] * bw, dim=1)
     valid = torch.sum(pw, dim=1) > 0
     sdf = torch.where(valid, sdf, torch.ones_like(sdf) * voxel_size)

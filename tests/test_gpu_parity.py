@@ -754,7 +754,10 @@ def test_neural_map_depth_frames_with_tsdf_prior(bnv, tmp_path):
 # ---------------------------------------------------------------------------------------------
 # tiny-cuda-nn checkpoint (the reference's default configuration).  PARITY UNPINNED against the
 # reference itself (its fp16 CUDA kernels cannot run here): checked against the oracle's fp16
-# restatement of the FullyFusedMLP layout, at fp16-level tolerances.
+# restatement of the FullyFusedMLP layout, at fp16-level tolerances.  The plumbing of every mode-2 kernel
+# (inputs and padding, fragment mapping, ragged tails, LDS tables, work lists, blends, backward) is held
+# to a float64 run of the same network, at bars derived from seeded defects, in
+# tests/test_gpu_precision_tcnn.py (bars: tests/tcnn_restatement.py, tests/test_tcnn_envelope_cpu.py).
 # ---------------------------------------------------------------------------------------------
 def test_tcnn_checkpoint_encode_decode_vs_oracle(bnv, orc):
     from conftest import WEIGHTS_TCNN
