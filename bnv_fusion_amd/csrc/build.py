@@ -17,7 +17,7 @@ SOURCES = ["runtime.hip", "encode.hip", "encode_mlp.hip", "encode_tcnn.hip", "vo
            "render.hip", "meshpost.hip", "train.hip", "train_tcnn.hip", "meshsdf.hip", "meshray.hip",
            "track.hip", "depth_filter.hip", "meshcolor.hip", "plan.hip"]
 HEADERS = ["bnv_common.hpp", "encode.hpp", "frontend.hpp", "tcnn_mlp.hpp", "sdf_mlp.hpp", "decode_host.hpp", "cell_grid.hpp", "meshsdf.hpp",
-           "workspace.hpp", "scan.hpp", "shard.hpp", "volume_keys.hpp",
+           "workspace.hpp", "scan.hpp", "shard.hpp", "volume_keys.hpp", "train_common.hpp",
            os.path.join("..", "..", "include", "bnv_fusion.h")]
 OUT = os.path.join(HERE, "..", "libbnv_fusion_hip.so")
 STAMP = OUT + ".sha256"

@@ -12,15 +12,14 @@
 #include <math.h>
 
 #include "bnv_common.hpp"
+#include "train_common.hpp"
 #include "workspace.hpp"
 
 namespace bnv {
 namespace train {
 
-constexpr int kNin = 6, kC = 128, kF = 8, kDin = 17, kH = 256;
-constexpr int kMaxN = 64;
+constexpr int kNin = 6, kC = 128, kDin = 17, kH = 256;
 constexpr float kBnEps = 1e-5f, kBnMomentum = 0.1f;
-constexpr float kW_L1 = 1.0f, kW_Reg = 0.001f;   // fusion_pointnet_model.yaml:36-38
 
 // ---- flat parameter layout (state_dict order, running stats and num_batches_tracked excluded) ----
 struct Layout {
@@ -118,15 +117,6 @@ __global__ void __launch_bounds__(kGemmThreads) k_gemm(GemmArgs g) {
   }
 }
 
-// out[i] = sum over s ascending of P[s * count + i]
-__global__ void k_sum_partials(const float* __restrict__ P, int64_t S, int64_t count, float* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  float s = 0.0f;
-  for (int64_t z = 0; z < S; ++z) s += P[z * count + i];
-  out[i] = s;
-}
-
 // Column partials of X [R, C] (row stride ldx) over row chunk blockIdx.x:
 //   mode 0: sum x;  mode 1: sum (x - mean[c])^2;  mode 2: sum dy (P) and sum dy * xhat (P2), X = dy, Y = xhat.
 __global__ void k_col_partials(const float* __restrict__ X, const float* __restrict__ Y, int64_t R, int C,
@@ -192,17 +182,6 @@ __global__ void k_bn_apply(float* __restrict__ Z, int64_t R, int C, const float*
   out[i] = relu ? relu_bits(y) : y;
 }
 
-// feats[b, c] = mean over the n rows of patch b of Y [B * n, 8]
-__global__ void k_patch_mean(const float* __restrict__ Y, int64_t B, int n, float* __restrict__ feats) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * kF) return;
-  const int64_t b = i / kF;
-  const int c = (int)(i % kF);
-  float s = 0.0f;
-  for (int j = 0; j < n; ++j) s += Y[(b * n + j) * kF + c];
-  feats[i] = s / (float)n;
-}
-
 // encoder input rows: X0[b * n + j] = input_pts[b, j, :6]
 __global__ void k_gather_input(const float* __restrict__ pts, int64_t B, int n, float* __restrict__ X0) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -230,7 +209,6 @@ __global__ void k_decoder_input(const float* __restrict__ xyz, const float* __re
 
 // Loss (one workgroup, fixed reduction order): l1 = mean |pred - gt|, reg = mean_b |feats_b|_2,
 // loss = {w_l1 l1 + w_reg reg, l1, reg}; dpred = w_l1 sign(pred - gt) / (B M) (train: with_grad)
-constexpr int kLossThreads = 1024;
 __global__ void __launch_bounds__(kLossThreads) k_loss(const float* __restrict__ pred, const float* __restrict__ gt,
                                                        int64_t R, const float* __restrict__ feats, int64_t B,
                                                        int with_grad, float* __restrict__ dpred,
@@ -244,22 +222,10 @@ __global__ void __launch_bounds__(kLossThreads) k_loss(const float* __restrict__
     a += fabsf(d);
     if (with_grad) dpred[r] = d > 0.0f ? g : (d < 0.0f ? -g : 0.0f);
   }
-  float q = 0.0f;
-  for (int64_t b = t; b < B; b += kLossThreads) {
-    float ss = 0.0f;
-    for (int c = 0; c < kF; ++c) ss += feats[b * kF + c] * feats[b * kF + c];
-    q += sqrtf(ss);
-  }
   s1[t] = a;
-  s2[t] = q;
+  s2[t] = loss_feat_norms(feats, B, t);
   __syncthreads();
-  for (int w = kLossThreads / 2; w > 0; w >>= 1) {
-    if (t < w) {
-      s1[t] += s1[t + w];
-      s2[t] += s2[t + w];
-    }
-    __syncthreads();
-  }
+  loss_tree_sums(s1, s2, t);
   if (t == 0) {
     const float l1 = s1[0] / (float)R, reg = s2[0] / (float)B;
     loss[0] = with_grad ? kW_L1 * l1 + kW_Reg * reg : l1;
@@ -274,12 +240,8 @@ __global__ void k_dfeats(const float* __restrict__ dfrows, const float* __restri
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * kF) return;
   const int64_t b = i / kF;
-  const int c = (int)(i % kF);
-  float s = 0.0f;
-  for (int64_t m = 0; m < M; ++m) s += dfrows[(b * M + m) * kF + c];
-  float ss = 0.0f;
-  for (int k = 0; k < kF; ++k) ss += feats[b * kF + k] * feats[b * kF + k];
-  const float nrm = sqrtf(ss);
+  const float s = dfrows_patch_sum(dfrows, b, M, (int)(i % kF));
+  const float nrm = feat_norm(feats, b);
   const float reg = nrm > 0.0f ? (kW_Reg / (float)B) * (feats[i] / nrm) : 0.0f;
   dfeats[i] = s + reg;
 }
@@ -304,23 +266,16 @@ __global__ void k_bn_backward(const float* __restrict__ dy, const float* __restr
   dz[i] = (dy[i] - sum_dy[c] / r - xh[i] * (sum_dyxh[c] / r)) * (rstd[c] * gamma[c]);
 }
 
-// Adam, torch's single-tensor form: m.lerp_(g, 1 - b1); v = v b2 + (1 - b2) g g; p -= step_size m / (sqrt(v) / bc2s + eps)
+// Adam (train_common.hpp: adam_update) with the host's step size and bias correction
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                        float* __restrict__ v, int64_t P, float beta1, float beta2, float eps, float step_size,
                        float bc2_sqrt) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
-  const float gi = g[i];
-  const float mi = m[i] + (1.0f - beta1) * (gi - m[i]);
-  const float vi = v[i] * beta2 + (1.0f - beta2) * (gi * gi);
-  m[i] = mi;
-  v[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] = p[i] + (-step_size) * (mi / denom);
+  adam_update(p, g, m, v, i, beta1, beta2, eps, step_size, bc2_sqrt);
 }
 
 // ---- host side ----
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 constexpr int64_t kMaxSplits = 64;
 constexpr int64_t kMinChunkRows = 256;
 constexpr int64_t kColChunkRows = 128;   // rows per workgroup of the column sums
@@ -376,8 +331,7 @@ static size_t layout_ws(int64_t B, int n, int64_t M, char* base, Ws* w) {
 }
 
 static bool shape_ok(int64_t B, int64_t n, int64_t M) {
-  return B >= 1 && n >= 1 && n <= kMaxN && B * n >= 2 && M >= 1 && B <= (1LL << 24) && M <= (1LL << 24) &&
-         B * M <= (1LL << 24);
+  return train_shape_ok(B, n, M) && B * n >= 2;   // train-mode BatchNorm: the batch statistics need two rows
 }
 
 // C(m, n) over operands A, B (see GemmArgs); a reduction over K is split in row chunks and summed in order
@@ -397,7 +351,7 @@ static int gemm_dw(hipStream_t s, const float* dZ, int64_t N_out, const float* X
   GemmArgs g{dZ, 1, N_out, X, K_in, 1, part, K_in, N_out, K_in, R, rows, nullptr, nullptr, 0, 0};
   dim3 grid((unsigned)cdiv(N_out, TM), (unsigned)cdiv(K_in, TN), (unsigned)S);
   k_gemm<<<grid, kGemmThreads, 0, s>>>(g);
-  k_sum_partials<<<blocks_for(N_out * K_in, 256), 256, 0, s>>>(part, S, N_out * K_in, out);
+  k_sum_partials<<<blocks_for(N_out * K_in, 256), 256, 0, s>>>(part, S, N_out * K_in, 1.0f, out);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -407,8 +361,8 @@ static int colsum(hipStream_t s, const float* X, const float* Y, int64_t R, int 
   const int64_t rows = kColChunkRows, S = cdiv(R, rows);
   float* p2 = part + S * C;
   k_col_partials<<<(unsigned)S, 256, 0, s>>>(X, Y, R, C, C, rows, mean, mode, part, p2);
-  k_sum_partials<<<blocks_for(C, 256), 256, 0, s>>>(part, S, C, out);
-  if (mode == 2) k_sum_partials<<<blocks_for(C, 256), 256, 0, s>>>(p2, S, C, out2);
+  k_sum_partials<<<blocks_for(C, 256), 256, 0, s>>>(part, S, C, 1.0f, out);
+  if (mode == 2) k_sum_partials<<<blocks_for(C, 256), 256, 0, s>>>(p2, S, C, 1.0f, out2);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -442,7 +396,7 @@ static int forward(hipStream_t s, const Layout& L, const float* params, float* r
                                                  l < 3, out);
     X = out;
   }
-  k_patch_mean<<<blocks_for(B * kF, 256), 256, 0, s>>>(w.Y4, B, n, w.feats);
+  k_patch_mean<false><<<blocks_for(B * kF, 256), 256, 0, s>>>(w.Y4, B, n, w.feats);
   k_decoder_input<<<blocks_for(Rd, 256), 256, 0, s>>>(training_pts, w.feats, B, M, w.D0);
   const float* H = w.D0;
   int64_t din = kDin;
@@ -511,6 +465,7 @@ static int backward(hipStream_t s, const Layout& L, const float* params, float* 
 }  // namespace train
 }  // namespace bnv
 
+using namespace bnv;
 using namespace bnv::train;
 
 extern "C" {
@@ -527,22 +482,20 @@ int bnv_train_step(float* params, float* grads, float* adam_m, float* adam_v, fl
                    const float* training_pts, const float* gt, int64_t B, int32_t n, int64_t M, float lr, float beta1,
                    float beta2, float eps, int64_t adam_step, float* loss_out, void* workspace, size_t ws_bytes,
                    bnv_stream_t stream) {
-  if (!shape_ok(B, n, M) || adam_step < 1 || !(lr >= 0.0f) || !(beta1 >= 0.0f && beta1 < 1.0f) ||
-      !(beta2 >= 0.0f && beta2 < 1.0f) || !(eps >= 0.0f))
-    return BNV_ERR_INVALID_ARGUMENT;
+  if (!shape_ok(B, n, M) || adam_step < 1 || !adam_args_ok(lr, beta1, beta2, eps)) return BNV_ERR_INVALID_ARGUMENT;
   if (!params || !grads || !adam_m || !adam_v || !running || !input_pts || !training_pts || !gt || !loss_out)
     return BNV_ERR_INVALID_ARGUMENT;
   Ws w;
   if (!workspace || ws_bytes < layout_ws(B, n, M, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  if (bnv::g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
+  if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   hipStream_t s = (hipStream_t)stream;
   const Layout L = make_layout();
   BNV_TRY(forward(s, L, params, running, input_pts, training_pts, gt, B, n, M, 1, w, loss_out));
   BNV_TRY(backward(s, L, params, grads, B, n, M, w));
-  // bias corrections in double on the host, like torch's python-float step_size / bias_correction2 ** 0.5
-  const double bc1 = 1.0 - pow((double)beta1, (double)adam_step), bc2 = 1.0 - pow((double)beta2, (double)adam_step);
-  k_adam<<<bnv::blocks_for(L.total, 256), 256, 0, s>>>(params, grads, adam_m, adam_v, L.total, beta1, beta2, eps,
-                                            (float)((double)lr / bc1), (float)sqrt(bc2));
+  float step_size, bc2_sqrt;   // formed on the host
+  adam_bias_corrections(lr, beta1, beta2, adam_step, &step_size, &bc2_sqrt);
+  k_adam<<<blocks_for(L.total, 256), 256, 0, s>>>(params, grads, adam_m, adam_v, L.total, beta1, beta2, eps, step_size,
+                                                  bc2_sqrt);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -554,7 +507,7 @@ int bnv_train_eval_loss(const float* params, const float* running, const float* 
   if (!params || !running || !input_pts || !training_pts || !gt || !loss_out) return BNV_ERR_INVALID_ARGUMENT;
   Ws w;
   if (!workspace || ws_bytes < layout_ws(B, n, M, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
-  if (bnv::g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
+  if (g_num_cus <= 0) return BNV_ERR_NOT_INITIALISED;
   return forward((hipStream_t)stream, make_layout(), params, const_cast<float*>(running), input_pts, training_pts, gt,
                  B, n, M, 0, w, loss_out);
 }

@@ -22,12 +22,14 @@
 //
 // One step is a fixed chain of launches on the caller's stream, with no allocation, synchronisation or host read:
 //   k_tcnn_pack (f16 MFMA fragment images of W and W^T, both networks)
-//   -> k_tcnn_tile<enc, fwd> (point outputs) -> k_tcnn_patch_mean (feats, f16)
+//   -> k_tcnn_tile<enc, fwd> (point outputs) -> k_patch_mean<f16> (feats, f16)
 //   -> k_tcnn_tile<dec, train> (forward, |pred - gt| per tile, backward to the input; activation and gradient
-//      images for the weight gradients) -> k_tcnn_dw + k_tcnn_sum (decoder dW)
+//      images for the weight gradients) -> k_tcnn_dw + k_sum_partials (decoder dW)
 //   -> k_tcnn_dfeats (d feats: sum over M, + the reg term)
-//   -> k_tcnn_tile<enc, train> (forward RECOMPUTED, backward) -> k_tcnn_dw + k_tcnn_sum (encoder dW)
+//   -> k_tcnn_tile<enc, train> (forward RECOMPUTED, backward) -> k_tcnn_dw + k_sum_partials (encoder dW)
 //   -> k_tcnn_loss (loss terms, finite check, device-side Adam step count) -> k_tcnn_adam.
+// k_patch_mean, k_sum_partials, Adam's update and the tail of the loss reduction are the fp32 trainer's, too
+// (train_common.hpp).
 // One wave runs all layers of a 32-row tile with the activations in registers (32x32x16 f16 MFMA; the layer output
 // tile feeds the next MFMA as its B operand with no data movement, tcnn_mlp.hpp).  Weight fragments
 // are read from the f16 images in global memory (45 KB per network, cache-resident), as the inference decoder does.
@@ -39,18 +41,18 @@
 #include <math.h>
 
 #include "bnv_common.hpp"
+#include "train_common.hpp"
 #include "workspace.hpp"
 #include "tcnn_mlp.hpp"
 
 namespace bnv {
 namespace train_tcnn {
 
-constexpr int kMaxN = 64, kF = 8, kW = 64;
+constexpr int kW = 64;
 constexpr int64_t kEncParams = 16 * 64 + 64 * 64 * 2 + 64 * 16;   // 10,240
 constexpr int64_t kDecParams = 32 * 64 + 64 * 64 * 2 + 64 * 16;   // 11,264
 constexpr int64_t kParams = kEncParams + kDecParams;
-constexpr float kW_L1 = 1.0f, kW_Reg = 0.001f;                   // fusion_pointnet_model.yaml:36-38
-constexpr int kMaxChunks = 64;                                   // row chunks of the weight-gradient partials
+constexpr int kMaxChunks = 64;                                  // row chunks of the weight-gradient partials
 
 // fragment images (halves): forward = the inference pack (tcnn_mlp.hpp: TcnnPack), transposed the same with the roles
 // swapped
@@ -303,17 +305,6 @@ __global__ __launch_bounds__(256) void k_tcnn_tile(TileArgs a) {
   }
 }
 
-// feats[b, c] = f16(mean over the n rows of patch b of Y), summed in row order
-__global__ void k_tcnn_patch_mean(const float* __restrict__ Y, int64_t B, int n, float* __restrict__ feats) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * kF) return;
-  const int64_t b = i / kF;
-  const int c = (int)(i % kF);
-  float s = 0.0f;
-  for (int j = 0; j < n; ++j) s += Y[(b * n + j) * kF + c];
-  feats[i] = (float)(_Float16)(s / (float)n);
-}
-
 // egrad[b, c] = (sum over patch b's M rows of dfrows) / M + w_reg feats_b / |feats_b|  (= d feats_b * B; the encoder
 // row gradient d feats_b / n scaled by B n)
 __global__ void k_tcnn_dfeats(const float* __restrict__ dfrows, const float* __restrict__ feats, int64_t B, int64_t M,
@@ -321,11 +312,8 @@ __global__ void k_tcnn_dfeats(const float* __restrict__ dfrows, const float* __r
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * kF) return;
   const int64_t b = i / kF;
-  float s = 0.0f;
-  for (int64_t m = 0; m < M; ++m) s += dfrows[(b * M + m) * kF + (i % kF)];
-  float ss = 0.0f;
-  for (int k = 0; k < kF; ++k) ss += feats[b * kF + k] * feats[b * kF + k];
-  const float nrm = sqrtf(ss);
+  const float s = dfrows_patch_sum(dfrows, b, M, (int)(i % kF));
+  const float nrm = feat_norm(feats, b);
   egrad[i] = s / (float)M + (nrm > 0.0f ? kW_Reg * (feats[i] / nrm) : 0.0f);
 }
 
@@ -376,19 +364,9 @@ __global__ __launch_bounds__(64) void k_tcnn_dw(DwArgs a) {
   }
 }
 
-// out[i] = scale * sum over chunks c ascending of part[c * P + i]
-__global__ void k_tcnn_sum(const float* __restrict__ part, int64_t S, int64_t P, float scale, float* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  float s = 0.0f;
-  for (int64_t c = 0; c < S; ++c) s += part[c * P + i];
-  out[i] = s * scale;
-}
-
 // Loss (one workgroup, fixed order): l1 = sum of the tile partials / (B M), reg = mean_b |feats_b|;
 // loss_out = {l1 + w_reg reg, l1, reg} (+ [3] = skipped, train).  Train: a non-finite loss or gradient marks the step
 // skipped; otherwise the device step count advances and Adam's step size and bias correction are formed for it.
-constexpr int kLossThreads = 1024;
 __global__ __launch_bounds__(kLossThreads) void k_tcnn_loss(const float* __restrict__ ltile, int64_t T, int64_t R,
                                                             const float* __restrict__ feats, int64_t B,
                                                             const float* __restrict__ grads, int train, float lr,
@@ -398,27 +376,16 @@ __global__ __launch_bounds__(kLossThreads) void k_tcnn_loss(const float* __restr
   __shared__ int bad_any;
   const int t = threadIdx.x;
   if (t == 0) bad_any = 0;
-  float a = 0.0f, q = 0.0f;
+  float a = 0.0f;
   for (int64_t i = t; i < T; i += kLossThreads) a += ltile[i];
-  for (int64_t b = t; b < B; b += kLossThreads) {
-    float ss = 0.0f;
-    for (int c = 0; c < kF; ++c) ss += feats[b * kF + c] * feats[b * kF + c];
-    q += sqrtf(ss);
-  }
   bool bad = false;
   if (train)
     for (int64_t i = t; i < kParams; i += kLossThreads) bad = bad || !isfinite(grads[i]);
   s1[t] = a;
-  s2[t] = q;
+  s2[t] = loss_feat_norms(feats, B, t);
   __syncthreads();
-  if (bad) bad_any = 1;   // every writer stores the same value
-  for (int w = kLossThreads / 2; w > 0; w >>= 1) {
-    if (t < w) {
-      s1[t] += s1[t + w];
-      s2[t] += s2[t + w];
-    }
-    __syncthreads();
-  }
+  if (bad) bad_any = 1;   // every writer stores the same value; the barriers of the tree order it before the read
+  loss_tree_sums(s1, s2, t);
   if (t == 0) {
     const float l1 = s1[0] / (float)R, reg = s2[0] / (float)B;
     const float total = kW_L1 * l1 + kW_Reg * reg;
@@ -432,37 +399,23 @@ __global__ __launch_bounds__(kLossThreads) void k_tcnn_loss(const float* __restr
       if (!skip) {
         const int64_t step = *adam_step + 1;
         *adam_step = step;
-        // bias corrections in double, like torch's python-float step_size / bias_correction2 ** 0.5
-        const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-        st[1] = (float)((double)lr / bc1);
-        st[2] = (float)sqrt(bc2);
+        adam_bias_corrections(lr, beta1, beta2, step, &st[1], &st[2]);   // formed on the device
       }
     }
   }
 }
 
-// Adam, torch's single-tensor form (train.hip k_adam), unless the step is marked skipped
+// Adam (train_common.hpp: adam_update) with k_tcnn_loss's step size and bias correction, unless the step is marked
+// skipped
 __global__ void k_tcnn_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, int64_t P, float beta1, float beta2, float eps,
                             const float* __restrict__ st) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P || st[0] != 0.0f) return;
-  const float step_size = st[1], bc2_sqrt = st[2];
-  const float gi = g[i];
-  const float mi = m[i] + (1.0f - beta1) * (gi - m[i]);
-  const float vi = v[i] * beta2 + (1.0f - beta2) * (gi * gi);
-  m[i] = mi;
-  v[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] = p[i] + (-step_size) * (mi / denom);
+  adam_update(p, g, m, v, i, beta1, beta2, eps, st[1], st[2]);
 }
 
 // ---- host side ----
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-static bool shape_ok(int64_t B, int64_t n, int64_t M) {
-  return B >= 1 && n >= 1 && n <= kMaxN && M >= 1 && B <= (1LL << 24) && M <= (1LL << 24) && B * M <= (1LL << 24);
-}
 
 // per network: feature widths of the layer inputs (X) and outputs (dZ)
 struct Net {
@@ -574,7 +527,7 @@ static int weight_grads(hipStream_t s, const Ws& w, int nin0, int64_t T, float s
   d.P = N.P;
   const int64_t S = cdiv(T, d.tpc);
   k_tcnn_dw<<<dim3((unsigned)nb, (unsigned)S), 64, 0, s>>>(d);
-  k_tcnn_sum<<<blocks_for(N.P, 256), 256, 0, s>>>(w.part, S, N.P, scale, grads);
+  k_sum_partials<<<blocks_for(N.P, 256), 256, 0, s>>>(w.part, S, N.P, scale, grads);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -585,7 +538,7 @@ static int encode(hipStream_t s, const float* params, const float* input_pts, in
   k_tcnn_pack<<<blocks_for(tot, 256), 256, 0, s>>>(params, w.img_e, w.img_d);
   const TileArgs a = tile_args(w, 0, B * n, input_pts, n, nullptr, nullptr, 0);
   k_tcnn_tile<0, 0><<<blocks_for(a.T, 4), 256, 0, s>>>(a);
-  k_tcnn_patch_mean<<<blocks_for(B * kF, 256), 256, 0, s>>>(w.Y, B, n, w.feats);
+  k_patch_mean<true><<<blocks_for(B * kF, 256), 256, 0, s>>>(w.Y, B, n, w.feats);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -593,6 +546,7 @@ static int encode(hipStream_t s, const float* params, const float* input_pts, in
 }  // namespace train_tcnn
 }  // namespace bnv
 
+using namespace bnv;
 using namespace bnv::train_tcnn;
 
 extern "C" {
@@ -600,7 +554,7 @@ extern "C" {
 int64_t bnv_train_tcnn_param_floats(void) { return kParams; }
 
 size_t bnv_train_tcnn_workspace_bytes(int64_t B, int32_t n, int64_t M) {
-  if (!shape_ok(B, n, M)) return 0;
+  if (!train_shape_ok(B, n, M)) return 0;
   return layout_ws(B, n, M, nullptr, nullptr);
 }
 
@@ -608,9 +562,7 @@ int bnv_train_tcnn_step(float* params, float* grads, float* adam_m, float* adam_
                         const float* input_pts, const float* training_pts, const float* gt, int64_t B, int32_t n,
                         int64_t M, float lr, float beta1, float beta2, float eps, float* loss_out, void* workspace,
                         size_t ws_bytes, bnv_stream_t stream) {
-  if (!shape_ok(B, n, M) || !(lr >= 0.0f) || !(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f) ||
-      !(eps >= 0.0f))
-    return BNV_ERR_INVALID_ARGUMENT;
+  if (!train_shape_ok(B, n, M) || !adam_args_ok(lr, beta1, beta2, eps)) return BNV_ERR_INVALID_ARGUMENT;
   if (!params || !grads || !adam_m || !adam_v || !adam_step || !input_pts || !training_pts || !gt || !loss_out)
     return BNV_ERR_INVALID_ARGUMENT;
   Ws w;
@@ -641,7 +593,7 @@ int bnv_train_tcnn_step(float* params, float* grads, float* adam_m, float* adam_
 int bnv_train_tcnn_eval_loss(const float* params, const float* input_pts, const float* training_pts, const float* gt,
                              int64_t B, int32_t n, int64_t M, float* loss_out, void* workspace, size_t ws_bytes,
                              bnv_stream_t stream) {
-  if (!shape_ok(B, n, M)) return BNV_ERR_INVALID_ARGUMENT;
+  if (!train_shape_ok(B, n, M)) return BNV_ERR_INVALID_ARGUMENT;
   if (!params || !input_pts || !training_pts || !gt || !loss_out) return BNV_ERR_INVALID_ARGUMENT;
   Ws w;
   if (!workspace || ws_bytes < layout_ws(B, n, M, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
@@ -660,7 +612,7 @@ int bnv_train_tcnn_eval_loss(const float* params, const float* input_pts, const 
 int bnv_train_tcnn_forward(const float* params, const float* input_pts, const float* training_pts, int64_t B,
                            int32_t n, int64_t M, float* feats, float* pred, void* workspace, size_t ws_bytes,
                            bnv_stream_t stream) {
-  if (!shape_ok(B, n, M)) return BNV_ERR_INVALID_ARGUMENT;
+  if (!train_shape_ok(B, n, M)) return BNV_ERR_INVALID_ARGUMENT;
   if (!params || !input_pts || !training_pts || !feats || !pred) return BNV_ERR_INVALID_ARGUMENT;
   Ws w;
   if (!workspace || ws_bytes < layout_ws(B, n, M, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;

@@ -86,11 +86,13 @@ def _np(v):
     return v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
 
 
-def check_shapes(input_pts, training_pts, gt, n):
-    """ValueError unless input_pts [B, 64, 6], training_pts [B, M, 3], gt [B, M] (or [B, M, 1]), 1 <= n <= 64 and
-    B n >= 2 (the batch statistics need two rows)."""
-    if input_pts.dim() != 3 or input_pts.shape[1] != N_LOCAL_SAMPLES or input_pts.shape[2] != 6:
-        raise ValueError(f"input_pts must be [B, {N_LOCAL_SAMPLES}, 6], got {tuple(input_pts.shape)}")
+def _check_shapes(input_pts, training_pts, gt, n, batchnorm):
+    """The shape guard of both trainers.  ``batchnorm``: the fp32 networks (B n >= 2); else the tiny-cuda-nn ones
+    (B >= 1, B M <= 2^24)."""
+    if input_pts.dim() != 3 or input_pts.shape[1] != N_LOCAL_SAMPLES or input_pts.shape[2] != 6 or \
+            (not batchnorm and input_pts.shape[0] < 1):
+        raise ValueError(f"input_pts must be [{'B' if batchnorm else 'B >= 1'}, {N_LOCAL_SAMPLES}, 6], "
+                         f"got {tuple(input_pts.shape)}")
     B = input_pts.shape[0]
     if training_pts.dim() != 3 or training_pts.shape[0] != B or training_pts.shape[2] != 3:
         raise ValueError(f"training_pts must be [B={B}, M, 3], got {tuple(training_pts.shape)}")
@@ -99,46 +101,59 @@ def check_shapes(input_pts, training_pts, gt, n):
         raise ValueError(f"gt must be [B={B}, M={M}], got {tuple(gt.shape)}")
     if not 1 <= n <= N_LOCAL_SAMPLES:
         raise ValueError(f"n={n}: 1 .. {N_LOCAL_SAMPLES} input points per patch")
-    if B * n < 2:
+    if batchnorm and B * n < 2:
         raise ValueError(f"B * n = {B * n}: train-mode BatchNorm needs at least two rows")
-    if M < 1:
+    if batchnorm and M < 1:
         raise ValueError("M must be >= 1")
+    if not batchnorm and (M < 1 or B * M > (1 << 24)):
+        raise ValueError(f"B * M = {B * M}: 1 .. 2^24 query points")
     return B, M
 
 
-class EmbeddingTrainer:
-    """Trains the point encoder and SDF decoder with Adam (torch defaults, ``lr``) and an epoch-wise StepLR
-    (step 20000, gamma 0.5), batch after batch, on ``device``.
+def check_shapes(input_pts, training_pts, gt, n):
+    """ValueError unless input_pts [B, 64, 6], training_pts [B, M, 3], gt [B, M] (or [B, M, 1]), 1 <= n <= 64 and
+    B n >= 2 (the batch statistics need two rows)."""
+    return _check_shapes(input_pts, training_pts, gt, n, batchnorm=True)
 
-    ``state_dict``: initial weights in the reference's key layout (``weights.load_npz``, a checkpoint's
-    ``state_dict``); None: PyTorch's default initialisation from ``seed``.  ``seed`` also seeds the draw of ``n``."""
 
-    def __init__(self, state_dict=None, seed=0, lr=1e-3, device="cuda:0", betas=(0.9, 0.999), eps=1e-8):
+def _require(sd, keys, shapes):
+    """ValueError unless the initial weights ``sd`` hold every key of ``keys``, and ``shapes`` [(name, shape)] fit."""
+    missing = [k for k in keys if k not in sd]
+    if missing:
+        raise ValueError(f"state_dict lacks {missing}")
+    for k, shape in shapes:
+        if tuple(np.shape(sd[k])) != shape:
+            raise ValueError(f"{k}: shape {np.shape(sd[k])}, expected {shape}")
+
+
+def _views(buf, shapes):
+    """name -> view of a flat buffer (device tensor or numpy array) cut into ``shapes`` [(name, shape)], in order."""
+    out, o = {}, 0
+    for k, shape in shapes:
+        size = int(np.prod(shape))
+        out[k] = buf[o: o + size].reshape(shape)
+        o += size
+    return out
+
+
+class _Trainer:
+    """What the two trainers share: the flat device buffers of the weights and of Adam's state, the schedule, the
+    draw of ``n``, the workspace and the call into the library.  A trainer names its tensors (``SHAPES``), its shape
+    guard (``BATCHNORM``) and its entries (``ENTRY``: bnv_<ENTRY>_step and so on)."""
+    SHAPES, BATCHNORM, ENTRY = None, None, None
+
+    def __init__(self, sd, seed, lr, device, betas, eps):
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise ValueError("EmbeddingTrainer runs on the GPU (device='cuda:<i>')")
+            raise ValueError(f"{type(self).__name__} runs on the GPU (device='cuda:<i>')")
         self.lib = _lib.require_device(self.device.index or 0)
-        sd = default_state_dict(seed) if state_dict is None else {k: _np(v) for k, v in state_dict.items()}
-        missing = [k for k in state_dict_keys() if k not in sd]
-        if missing:
-            raise ValueError(f"state_dict lacks {missing}")
-        for k, shape in PARAM_SHAPES + RUNNING_SHAPES:
-            if tuple(np.shape(sd[k])) != shape:
-                raise ValueError(f"{k}: shape {np.shape(sd[k])}, expected {shape}")
-        n_par = int(self.lib.bnv_train_param_floats())
-        n_run = int(self.lib.bnv_train_running_floats())
-        flat = np.concatenate([np.asarray(sd[k], np.float32).ravel() for k, _ in PARAM_SHAPES])
-        run = np.concatenate([np.asarray(sd[k], np.float32).ravel() for k, _ in RUNNING_SHAPES])
-        assert flat.size == n_par and run.size == n_run, (flat.size, n_par, run.size, n_run)
+        flat =np.concatenate([np.asarray(sd[k], np.float32).ravel() for k, _ in self.SHAPES])
+        assert flat.size == int(getattr(self.lib, f"bnv_{self.ENTRY}_param_floats")())
         self.params = torch.from_numpy(flat).to(self.device)
-        self.running = torch.from_numpy(run).to(self.device)
         self.grads = torch.zeros_like(self.params)
         self.exp_avg = torch.zeros_like(self.params)
         self.exp_avg_sq = torch.zeros_like(self.params)
-        self.num_batches_tracked = [int(np.asarray(sd[f"pointnet_backbone.bn{i + 1}.num_batches_tracked"]))
-                                    for i in range(4)]
         self.base_lr, self.betas, self.eps = float(lr), tuple(float(b) for b in betas), float(eps)
-        self.adam_step = 0
         self.epoch = 0
         self.rng = np.random.default_rng(seed)
         self._ws = {}
@@ -152,104 +167,104 @@ class EmbeddingTrainer:
     def end_epoch(self):
         self.epoch += 1
 
-    # ---- steps ----
-    def _workspace(self, B, n, M):
-        key = (B, M)
-        ws = self._ws.get(key)
-        nbytes = int(self.lib.bnv_train_workspace_bytes(B, N_LOCAL_SAMPLES, M))   # the largest n: one per (B, M)
-        if ws is None:
-            if nbytes == 0:
-                raise ValueError(f"shape B={B}, M={M} out of range")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws = {key: ws}
-        return ws
-
-    def _inputs(self, input_pts, training_pts, gt):
-        f = [torch.as_tensor(t).to(self.device, torch.float32).contiguous() for t in (input_pts, training_pts, gt)]
-        return f[0], f[1], f[2]
-
     def draw_n(self):
         """n = randint(min_pts_in_grid / 2, n_local_samples), drawn once per step (local_point_fusion.py:411-415)."""
         return int(self.rng.integers(MIN_PTS_IN_GRID // 2, N_LOCAL_SAMPLES))
+
+    # ---- calls ----
+    def _workspace(self, B, M):
+        """The workspace of the last (B, M), sized for the largest n; the library is asked on a miss only."""
+        ws = self._ws.get((B, M))
+        if ws is None:
+            nbytes = int(getattr(self.lib, f"bnv_{self.ENTRY}_workspace_bytes")(B, N_LOCAL_SAMPLES, M))
+            if nbytes == 0:
+                raise ValueError(f"shape B={B}, M={M} out of range")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ws = {(B, M): ws}
+        return ws
+
+    def _inputs(self, input_pts, training_pts, gt, n):
+        """The three inputs as contiguous fp32 device tensors, B, M and the workspace."""
+        x, p, g = (torch.as_tensor(t).to(self.device, torch.float32).contiguous()
+                   for t in (input_pts, training_pts, gt))
+        B, M = _check_shapes(x, p, g, n, self.BATCHNORM)
+        return x, p, g, B, M, self._workspace(B, M)
+
+    def _call(self, what, *args):
+        """bnv_<ENTRY>_<what>(tensors as pointers, scalars as they are, ..., stream) on this device; raises unless it
+        succeeds."""
+        name = f"bnv_{self.ENTRY}_{what}"
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, name)(*[_lib.ptr(a) if torch.is_tensor(a) else a for a in args],
+                                         _lib.stream_ptr())
+        _lib.check(rc, name)
+
+    def _adam_args(self):
+        return [C.c_float(v) for v in (self.lr, self.betas[0], self.betas[1], self.eps)]
+
+    # ---- weights out ----
+    def parameters(self):
+        """name -> device tensor view into the flat parameter buffer, in state_dict shapes."""
+        return _views(self.params, self.SHAPES)
+
+    def gradients(self):
+        """name -> device tensor view of the last step's gradients."""
+        return _views(self.grads, self.SHAPES)
+
+    def save_npz(self, path):
+        """Writes ``state_dict()`` in the layout of the shipped weights/pointnet_*.npz (``load_pretrained(path=...)``
+        reads it; with ``tiny_cuda=True`` for the tiny-cuda-nn networks)."""
+        with open(path, "wb") as fh:
+            np.savez(fh, **self.state_dict())
+
+
+class EmbeddingTrainer(_Trainer):
+    """Trains the point encoder and SDF decoder with Adam (torch defaults, ``lr``) and an epoch-wise StepLR
+    (step 20000, gamma 0.5), batch after batch, on ``device``.
+
+    ``state_dict``: initial weights in the reference's key layout (``weights.load_npz``, a checkpoint's
+    ``state_dict``); None: PyTorch's default initialisation from ``seed``.  ``seed`` also seeds the draw of ``n``."""
+    SHAPES, BATCHNORM, ENTRY = PARAM_SHAPES, True, "train"
+
+    def __init__(self, state_dict=None, seed=0, lr=1e-3, device="cuda:0", betas=(0.9, 0.999), eps=1e-8):
+        sd = default_state_dict(seed) if state_dict is None else {k: _np(v) for k, v in state_dict.items()}
+        _require(sd, state_dict_keys(), PARAM_SHAPES + RUNNING_SHAPES)
+        super().__init__(sd, seed, lr, device, betas, eps)
+        run = np.concatenate([np.asarray(sd[k], np.float32).ravel() for k, _ in RUNNING_SHAPES])
+        assert run.size == int(self.lib.bnv_train_running_floats())
+        self.running = torch.from_numpy(run).to(self.device)
+        self.num_batches_tracked = [int(np.asarray(sd[f"pointnet_backbone.bn{i + 1}.num_batches_tracked"]))
+                                    for i in range(4)]
+        self.adam_step = 0
 
     def step(self, input_pts, training_pts, gt, n=None):
         """One training step on a batch: input_pts [B, 64, 6], training_pts [B, M, 3], gt [B, M].  The first ``n``
         points of every patch feed the encoder (None: drawn).  Returns the loss terms as device tensors
         ({"loss", "bce_loss", "reg_loss"}); nothing synchronises."""
-        if n is None:
-            n = self.draw_n()
-        n = int(n)
-        x, p, g = self._inputs(input_pts, training_pts, gt)
-        B, M = check_shapes(x, p, g, n)
-        ws = self._workspace(B, n, M)
+        n = self.draw_n() if n is None else int(n)
+        x, p, g, B, M, ws = self._inputs(input_pts, training_pts, gt, n)
         loss = torch.empty(3, dtype=torch.float32, device=self.device)
-        self.adam_step += 1
-        with torch.cuda.device(self.device):
-            rc = self.lib.bnv_train_step(
-                _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                _lib.ptr(self.running), _lib.ptr(x), _lib.ptr(p), _lib.ptr(g), B, n, M, C.c_float(self.lr),
-                C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.adam_step,
-                _lib.ptr(loss), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-        if rc != 0:
-            self.adam_step -= 1
-        _lib.check(rc, "bnv_train_step")
+        self._call("step", self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.running, x, p, g, B, n, M,
+                   *self._adam_args(), self.adam_step + 1, loss, ws, ws.numel())
+        self.adam_step += 1      # a failed call has raised: the step count stays as it was
         self.num_batches_tracked = [v + 1 for v in self.num_batches_tracked]
         return {"loss": loss[0], "bce_loss": loss[1], "reg_loss": loss[2]}
 
     def eval_loss(self, batch, n=N_LOCAL_SAMPLES):
         """Validation loss (local_point_fusion.py:462-480): eval-mode BatchNorm, all 64 points; returns the L1 term
         (``val_loss``) as a device scalar.  ``batch``: a dict with input_pts, training_pts, gt."""
-        x, p, g = self._inputs(batch["input_pts"], batch["training_pts"], batch["gt"])
-        B, M = check_shapes(x, p, g, n)
-        ws = self._workspace(B, n, M)
+        x, p, g, B, M, ws = self._inputs(batch["input_pts"], batch["training_pts"], batch["gt"], n)
         loss = torch.empty(3, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.bnv_train_eval_loss(_lib.ptr(self.params), _lib.ptr(self.running), _lib.ptr(x), _lib.ptr(p),
-                                              _lib.ptr(g), B, n, M, _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
-                                              _lib.stream_ptr())
-        _lib.check(rc, "bnv_train_eval_loss")
+        self._call("eval_loss", self.params, self.running, x, p, g, B, n, M, loss, ws, ws.numel())
         return loss[1]
-
-    # ---- weights out ----
-    def parameters(self):
-        """name -> device tensor view into the flat parameter buffer, in state_dict shapes."""
-        out, o = {}, 0
-        for k, shape in PARAM_SHAPES:
-            size = int(np.prod(shape))
-            out[k] = self.params[o: o + size].view(shape)
-            o += size
-        return out
-
-    def gradients(self):
-        """name -> device tensor view of the last step's gradients."""
-        out, o = {}, 0
-        for k, shape in PARAM_SHAPES:
-            size = int(np.prod(shape))
-            out[k] = self.grads[o: o + size].view(shape)
-            o += size
-        return out
 
     def state_dict(self):
         """The weights as numpy arrays with exactly the keys, shapes and dtypes of weights/pointnet_fp32.npz."""
-        par = self.params.cpu().numpy()
-        run = self.running.cpu().numpy()
-        sd, o = {}, 0
-        for k, shape in PARAM_SHAPES:
-            size = int(np.prod(shape))
-            sd[k] = par[o: o + size].reshape(shape).copy()
-            o += size
-        o = 0
-        for k, shape in RUNNING_SHAPES:
-            sd[k] = run[o: o + shape[0]].copy()
-            o += shape[0]
+        sd = {k: v.copy() for k, v in _views(self.params.cpu().numpy(), PARAM_SHAPES).items()}
+        sd.update({k: v.copy() for k, v in _views(self.running.cpu().numpy(), RUNNING_SHAPES).items()})
         for i in range(4):
             sd[f"pointnet_backbone.bn{i + 1}.num_batches_tracked"] = np.array(self.num_batches_tracked[i], np.int64)
         return {k: sd[k] for k in state_dict_keys()}
-
-    def save_npz(self, path):
-        """Writes the weights in the layout of weights/pointnet_fp32.npz (``load_pretrained(path=...)`` reads it)."""
-        with open(path, "wb") as fh:
-            np.savez(fh, **self.state_dict())
 
     def save_ckpt(self, path):
         """Writes ``{"state_dict": ...}`` that the reference's LitFusionPointNet loads strictly (run_e2e.py:232-233):
@@ -291,23 +306,10 @@ def tcnn_default_state_dict(seed=0):
 def check_tcnn_shapes(input_pts, training_pts, gt, n):
     """ValueError unless input_pts [B, 64, 6], training_pts [B, M, 3], gt [B, M] (or [B, M, 1]), 1 <= n <= 64, M >= 1
     and B M <= 2^24 (no BatchNorm: B n = 1 is valid)."""
-    if input_pts.dim() != 3 or input_pts.shape[0] < 1 or input_pts.shape[1] != N_LOCAL_SAMPLES or \
-            input_pts.shape[2] != 6:
-        raise ValueError(f"input_pts must be [B >= 1, {N_LOCAL_SAMPLES}, 6], got {tuple(input_pts.shape)}")
-    B = input_pts.shape[0]
-    if training_pts.dim() != 3 or training_pts.shape[0] != B or training_pts.shape[2] != 3:
-        raise ValueError(f"training_pts must be [B={B}, M, 3], got {tuple(training_pts.shape)}")
-    M = training_pts.shape[1]
-    if tuple(gt.shape) not in ((B, M), (B, M, 1)):
-        raise ValueError(f"gt must be [B={B}, M={M}], got {tuple(gt.shape)}")
-    if not 1 <= n <= N_LOCAL_SAMPLES:
-        raise ValueError(f"n={n}: 1 .. {N_LOCAL_SAMPLES} input points per patch")
-    if M < 1 or B * M > (1 << 24):
-        raise ValueError(f"B * M = {B * M}: 1 .. 2^24 query points")
-    return B, M
+    return _check_shapes(input_pts, training_pts, gt, n, batchnorm=False)
 
 
-class TcnnEmbeddingTrainer(EmbeddingTrainer):
+class TcnnEmbeddingTrainer(_Trainer):
     """Trains the tiny-cuda-nn point encoder and SDF decoder (the reference's default, ``tiny_cuda: True``) with Adam
     and an epoch-wise StepLR, like ``EmbeddingTrainer``: csrc/train_tcnn.hip, include/bnv_fusion.h
     (bnv_train_tcnn_step).  Forward in the f16 arithmetic of MLP mode 2, backward straight-through with hi + lo f16
@@ -318,112 +320,45 @@ class TcnnEmbeddingTrainer(EmbeddingTrainer):
     weights.DEFAULT_TCNN)`` fine-tunes the shipped checkpoint); None: ``tcnn_default_state_dict(seed)``.  ``seed`` also
     seeds the draw of ``n``."""
 
-    def __init__(self, state_dict=None, seed=0, lr=1e-3, device="cuda:0", betas=(0.9, 0.999), eps=1e-8):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("TcnnEmbeddingTrainer runs on the GPU (device='cuda:<i>')")
-        self.lib = _lib.require_device(self.device.index or 0)
-        sd = tcnn_default_state_dict(seed) if state_dict is None else {k: _np(v) for k, v in state_dict.items()}
-        for k, shape in TCNN_SHAPES:
-            if k not in sd:
-                raise ValueError(f"state_dict lacks {k}")
-            if tuple(np.shape(sd[k])) != shape:
-                raise ValueError(f"{k}: shape {np.shape(sd[k])}, expected {shape}")
-        flat = np.concatenate([np.asarray(sd[k], np.float32).ravel() for k in TCNN_KEYS])
-        assert flat.size == int(self.lib.bnv_train_tcnn_param_floats())
-        self.params = torch.from_numpy(flat).to(self.device)
-        self.grads = torch.zeros_like(self.params)
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
-        self.adam_step = torch.zeros(1, dtype=torch.int64, device=self.device)   # advanced on the device
-        self.base_lr, self.betas, self.eps = float(lr), tuple(float(b) for b in betas), float(eps)
-        self.epoch = 0
-        self.rng = np.random.default_rng(seed)
-        self._ws = {}
+    SHAPES, BATCHNORM, ENTRY = TCNN_SHAPES, False, "train_tcnn"
 
-    def _workspace(self, B, n, M):
-        key = (B, M)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = int(self.lib.bnv_train_tcnn_workspace_bytes(B, N_LOCAL_SAMPLES, M))   # the largest n
-            if nbytes == 0:
-                raise ValueError(f"shape B={B}, M={M} out of range")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws = {key: ws}
-        return ws
+    def __init__(self, state_dict=None, seed=0, lr=1e-3, device="cuda:0", betas=(0.9, 0.999), eps=1e-8):
+        sd = tcnn_default_state_dict(seed) if state_dict is None else {k: _np(v) for k, v in state_dict.items()}
+        _require(sd, TCNN_KEYS, TCNN_SHAPES)
+        super().__init__(sd, seed, lr, device, betas, eps)
+        self.adam_step = torch.zeros(1, dtype=torch.int64, device=self.device)   # advanced on the device
 
     def step(self, input_pts, training_pts, gt, n=None):
         """One training step on a batch: input_pts [B, 64, 6], training_pts [B, M, 3], gt [B, M].  The first ``n``
         points of every patch feed the encoder (None: drawn).  Returns device tensors {"loss", "bce_loss",
         "reg_loss", "skipped"} (skipped: bool, the step left the weights and Adam's state as they were); nothing
         synchronises."""
-        if n is None:
-            n = self.draw_n()
-        n = int(n)
-        x, p, g = self._inputs(input_pts, training_pts, gt)
-        B, M = check_tcnn_shapes(x, p, g, n)
-        ws = self._workspace(B, n, M)
+        n = self.draw_n() if n is None else int(n)
+        x, p, g, B, M, ws = self._inputs(input_pts, training_pts, gt, n)
         loss = torch.empty(4, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.bnv_train_tcnn_step(
-                _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                _lib.ptr(self.adam_step), _lib.ptr(x), _lib.ptr(p), _lib.ptr(g), B, n, M, C.c_float(self.lr),
-                C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), _lib.ptr(loss),
-                _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, "bnv_train_tcnn_step")
+        self._call("step", self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.adam_step, x, p, g, B, n, M,
+                   *self._adam_args(), loss, ws, ws.numel())
         return {"loss": loss[0], "bce_loss": loss[1], "reg_loss": loss[2], "skipped": loss[3] != 0}
 
     def eval_loss(self, batch, n=N_LOCAL_SAMPLES):
         """Validation loss: all 64 points; returns the L1 term as a device scalar.  ``batch``: a dict with input_pts,
         training_pts, gt."""
-        x, p, g = self._inputs(batch["input_pts"], batch["training_pts"], batch["gt"])
-        B, M = check_tcnn_shapes(x, p, g, n)
-        ws = self._workspace(B, n, M)
+        x, p, g, B, M, ws = self._inputs(batch["input_pts"], batch["training_pts"], batch["gt"], n)
         loss = torch.empty(3, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.bnv_train_tcnn_eval_loss(_lib.ptr(self.params), _lib.ptr(x), _lib.ptr(p), _lib.ptr(g), B, n,
-                                                   M, _lib.ptr(loss), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, "bnv_train_tcnn_eval_loss")
+        self._call("eval_loss", self.params, x, p, g, B, n, M, loss, ws, ws.numel())
         return loss[1]
 
     def forward(self, input_pts, training_pts, n=N_LOCAL_SAMPLES):
         """feats [B, 8] and pred [B, M] of the current weights (device tensors, f16 values)."""
-        x, p, _ = self._inputs(input_pts, training_pts, torch.zeros(np.shape(training_pts)[:2]))
-        B, M = check_tcnn_shapes(x, p, torch.zeros(x.shape[0], p.shape[1]), n)
-        ws = self._workspace(B, n, M)
+        x, p, _, B, M, ws = self._inputs(input_pts, training_pts, torch.zeros(np.shape(training_pts)[:2]), n)
         feats = torch.empty(B, 8, dtype=torch.float32, device=self.device)
         pred = torch.empty(B, M, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.bnv_train_tcnn_forward(_lib.ptr(self.params), _lib.ptr(x), _lib.ptr(p), B, n, M,
-                                                 _lib.ptr(feats), _lib.ptr(pred), _lib.ptr(ws), ws.numel(),
-                                                 _lib.stream_ptr())
-        _lib.check(rc, "bnv_train_tcnn_forward")
+        self._call("forward", self.params, x, p, B, n, M, feats, pred, ws, ws.numel())
         return feats, pred
-
-    def _views(self, buf):
-        out, o = {}, 0
-        for k, shape in TCNN_SHAPES:
-            out[k] = buf[o: o + shape[0]]
-            o += shape[0]
-        return out
-
-    def parameters(self):
-        """name -> device tensor view into the flat parameter buffer (the two flat master vectors)."""
-        return self._views(self.params)
-
-    def gradients(self):
-        """name -> device tensor view of the last step's gradients."""
-        return self._views(self.grads)
 
     def state_dict(self):
         """The weights as numpy arrays with exactly the keys, shapes and dtypes of weights/pointnet_tcnn.npz."""
-        return {k: v.cpu().numpy().copy() for k, v in self._views(self.params).items()}
-
-    def save_npz(self, path):
-        """Writes the weights in the layout of weights/pointnet_tcnn.npz (``load_pretrained(tiny_cuda=True,
-        path=...)`` reads it)."""
-        with open(path, "wb") as fh:
-            np.savez(fh, **self.state_dict())
+        return {k: v.copy() for k, v in _views(self.params.cpu().numpy(), TCNN_SHAPES).items()}
 
     def save_ckpt(self, path):
         """Writes ``{"state_dict": {the two flat vectors}}``, what the reference's LitFusionPointNet(tiny_cuda=True)
