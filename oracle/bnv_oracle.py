@@ -682,7 +682,8 @@ def stratified_samples(n_samples, lengths, rand):
     """stratified_sampling (render_utils.py:77-94): one uniform draw inside each of n_samples strata of
     [0, length]; ``lengths`` [b, n, 1]; ``rand(b, n, s)`` supplies the uniforms -> [b, n, s, 1]."""
     b, n = lengths.shape[:2]
-    edges = torch.linspace(0, 1, steps=n_samples, device=lengths.device).unsqueeze(0).repeat(b, n, 1) * lengths
+    edges = torch.linspace(0, 1, steps=n_samples, device=lengths.device, dtype=lengths.dtype)    # (float32 lengths:
+    edges = edges.unsqueeze(0).repeat(b, n, 1) * lengths                # the reference's call; float64: exact strata)
     mids = 0.5 * (edges[..., 1:] + edges[..., :-1])
     upper = torch.cat([mids, edges[..., -1:]], dim=-1)
     lower = torch.cat([edges[..., :1], mids], dim=-1)
@@ -704,12 +705,15 @@ def hierarchical_samples(n_fine, n_coarse, depths, surface, dirs, centre, offset
     return pts, dists
 
 
-def sdf_ray_loss(rays, pred_sdf, pts, centre, n_valid, truncated_dist):
-    """compute_sdf_loss (render_utils.py:508-549): L1 between the decoded SDF and the signed distance to the
-    nearest valid neighbouring surface point, on samples in front of / just behind the surface."""
+def ray_targets(rays, pts, centre, truncated_dist):
+    """What compute_sdf_loss (render_utils.py:508-549) sums over, per sample [b, n, S], in the dtype of its inputs:
+    the L1 target (signed distance to the nearest valid neighbouring surface point, truncated), the sample weight
+    (sample in front of / just behind the surface x ray mask) and the unclipped ``gt_depth - depth`` that decides
+    the target's sign and the sample's validity."""
     gt_depth = torch.sqrt(torch.sum((rays["gt_pts"] - centre.unsqueeze(1)) ** 2, dim=-1)).unsqueeze(-1)
     depth = torch.sqrt(torch.sum((pts - centre.unsqueeze(1).unsqueeze(1)) ** 2, dim=-1))
-    gt_sdf = torch.clip(gt_depth - depth, min=-truncated_dist, max=truncated_dist)
+    raw_sdf = gt_depth - depth
+    gt_sdf = torch.clip(raw_sdf, min=-truncated_dist, max=truncated_dist)
     valid = gt_sdf > max(-truncated_dist * 0.5, -0.05)
     d = torch.sqrt(torch.sum((rays["neighbor_pts"].unsqueeze(2) - pts.unsqueeze(3)) ** 2, dim=-1))
     nm = rays["neighbor_masks"].unsqueeze(2).repeat(1, 1, pts.shape[2], 1)
@@ -717,8 +721,20 @@ def sdf_ray_loss(rays, pred_sdf, pts, centre, n_valid, truncated_dist):
     nearest = torch.min(d, dim=-1)[0]
     sign = torch.where(gt_sdf > 0, torch.ones_like(gt_sdf), torch.ones_like(gt_sdf) * -1)
     target = torch.clip(nearest * sign, min=-truncated_dist, max=truncated_dist)
-    l1 = F.l1_loss(pred_sdf, target, reduction="none") * valid
-    return (l1 * rays["mask"].unsqueeze(-1)).sum() / n_valid
+    weight = valid.to(target.dtype) * rays["mask"].unsqueeze(-1)
+    return target, weight, raw_sdf
+
+
+def weighted_l1(pred_sdf, target, weight, n_valid):
+    """sum weight |pred - target| / n_valid: the L1 sum of compute_sdf_loss over ``ray_targets``."""
+    return (F.l1_loss(pred_sdf, target, reduction="none") * weight).sum() / n_valid
+
+
+def sdf_ray_loss(rays, pred_sdf, pts, centre, n_valid, truncated_dist):
+    """compute_sdf_loss (render_utils.py:508-549): L1 between the decoded SDF and the signed distance to the
+    nearest valid neighbouring surface point, on samples in front of / just behind the surface."""
+    target, weight, _ = ray_targets(rays, pts, centre, truncated_dist)
+    return weighted_l1(pred_sdf, target, weight, n_valid)
 
 
 def calculate_loss(volume, rays, sd, truncated_units, truncated_dist, ray_max_dist, sdf_delta=None, rand=None):

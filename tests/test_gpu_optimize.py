@@ -286,8 +286,7 @@ def _split_rays(rays, lo, hi):
     return {k: (v if k in whole else v[:, lo:hi]) for k, v in rays.items()}
 
 
-@pytest.mark.parametrize("with_delta", [False, True])
-def test_batched_step_equals_split_by_split(bnv, model, with_delta):
+def _batched_step_equals_split_by_split(bnv, model, with_delta, per):
     """optimize.ray_batch_step (bnv_optim_step: ALL ray splits of a step in one forward + loss + backward launch, the
     count_optim of the splits deferred as per-row split masks) against the split-by-split sequence of ray_split_step
     (count_optim -> decode_pts -> loss -> backward per split, the reference's order run_e2e.py:127-153): same sample
@@ -300,7 +299,7 @@ def test_batched_step_equals_split_by_split(bnv, model, with_delta):
     rays = {k[5:]: torch.from_numpy(op[k]).to(DEV) for k in op.files if k.startswith("rays_")}
     delta = torch.from_numpy(dec["sdf_delta"]).to(DEV) if with_delta else None
     args = (int(op["truncated_units"]), float(op["truncated_dist"]), int(op["ray_max_dist"]))
-    n, per = int(rays["uv"].shape[1]), 40            # 4 splits of 40 rays x 35 samples (1,400: not a multiple of a chunk)
+    n = int(rays["uv"].shape[1])                     # 160 rays: 4 splits of ``per`` rays x 35 samples
     vols = []
     for _ in range(2):
         v = _insertion_order_volume(bnv)
@@ -332,13 +331,26 @@ def test_batched_step_equals_split_by_split(bnv, model, with_delta):
     if masked_a is not None:
         masked_b = pred_b == voxel
         assert torch.equal(masked_a, masked_b)                       # every mask decision
-        live = (~masked_a).view(n // per, -1).float().mean(1)
+        live = torch.stack([(~masked_a[lo: lo + per]).float().mean() for lo in range(0, n, per)])
+        assert len(live) == 4
         assert float(live[0]) == 0.0 and float(live[-1]) > 0.02 and float(live[1]) > 0.0, live   # they DO differ by split
     assert float((pred_a - pred_b).abs().max()) <= 2e-7
     la = float(sum(float(x) for x in loss_a))
     assert abs(float(loss_b) - la) <= 2e-6 * abs(la)
     assert float(grad_a.abs().max()) > 0
     assert float((grad_a - grad_b).abs().max()) <= 2e-5 * float(grad_a.abs().max())
+
+
+@pytest.mark.parametrize("with_delta", [False, True])
+def test_batched_step_equals_split_by_split(bnv, model, with_delta):
+    """4 splits of 40 rays x 35 samples (1,400: not a multiple of a chunk)."""
+    _batched_step_equals_split_by_split(bnv, model, with_delta, 40)
+
+
+@pytest.mark.parametrize("with_delta", [False, True])
+def test_batched_step_equals_split_by_split_uneven_last_split(bnv, model, with_delta):
+    """160 = 3 x 48 + 16 rays: the last split is shorter, its n_valid and split index come from the uneven path."""
+    _batched_step_equals_split_by_split(bnv, model, with_delta, 48)
 
 
 def test_batched_optimize_follows_the_split_by_split_optimiser(bnv):
