@@ -36,6 +36,8 @@ from .evaluate import evaluate_meshes, nearest_neighbors, sample_surface  # noqa
 from .mesh import TriMesh, load_ply  # noqa: F401,E402
 from . import tracking  # noqa: F401,E402
 from .tracking import Tracker, icp_align  # noqa: F401,E402
+from . import odometry  # noqa: F401,E402
+from .odometry import PreparedFrame, RgbdOdometry, prepare_frame, rgbd_align  # noqa: F401,E402
 from .frontend import DepthFilter, filter_depth  # noqa: F401,E402
 from . import plan  # noqa: F401,E402
 from .plan import VolumePlan, VolumePlanner, plan_volume  # noqa: F401,E402

@@ -4,7 +4,9 @@
 normals, as ``NeuralMap.render``, ``NeuralMap.render_tsdf`` and ``MeshScanner.render_depth`` make them):
 csrc/track.hip behind bnv_icp_align (include/bnv_fusion.h, "Tracking").  All iterations run on the device without a
 host read in between; the host reads the result once.  ``Tracker`` is the tracked fusion loop: the poses a data set
-gives serve as odometry, every frame is aligned to the map built so far and fused with the corrected pose.  GPU only.
+gives serve as odometry (or, with ``odometry="rgbd"``, the frame-to-frame motion ``odometry.RgbdOdometry`` estimates
+from the frames themselves), every frame is aligned to the map built so far and fused with the corrected pose.  GPU
+only.
 
     tracker = Tracker(neural_map, source="tsdf", model_size=(120, 160))
     for frame in frames:                       # frame["T_wc"]: drifting odometry
@@ -160,11 +162,21 @@ class Tracker:
     given poses serve as odometry), renders the map there (``source``: "neural" or "tsdf"; ``model_size``: the view's
     (H, W), default the frame's), aligns the frame and fuses it with the corrected pose.  A frame the aligner refuses
     is fused with ``T_pred`` and counted in ``failures`` (``statuses`` has every frame's code, -1 for the first
-    ``warmup`` frames, which are fused with their given pose).  ``poses``: the pose every frame was fused with."""
+    ``warmup`` frames, which are fused with their given pose).  ``poses``: the pose every frame was fused with.
+    ``odometry``: None (the given poses, as above), "rgbd" or an ``odometry.RgbdOdometry``: the motion between
+    consecutive frames is then estimated from the frames themselves, ``T_pred = T_prev_tracked inv(T_rel)``, and only
+    the first frame's ``T_wc`` is read (identity when it has none); a pair the odometry refuses contributes its
+    constant-velocity guess (``odometry.failures``).  The map's depth filter runs once, before odometry and tracking."""
 
-    def __init__(self, nm, source="neural", model_size=None, warmup=1, **icp):
+    def __init__(self, nm, source="neural", model_size=None, warmup=1, odometry=None, **icp):
         if source not in ("neural", "tsdf"):
             raise ValueError(f"source {source!r}: 'neural' or 'tsdf'")
+        if isinstance(odometry, str):
+            if odometry != "rgbd":
+                raise ValueError(f"odometry {odometry!r}: None, 'rgbd' or an RgbdOdometry")
+            from .odometry import RgbdOdometry
+            odometry = RgbdOdometry(max_depth=icp.get("max_depth", nm.max_depth))
+        self.odometry = odometry
         self.nm, self.source, self.model_size, self.warmup, self.icp = nm, source, model_size, int(warmup), icp
         self.poses, self.statuses, self.failures = [], [], 0
         self.last = None
@@ -172,6 +184,8 @@ class Tracker:
 
     def integrate(self, frame):
         frame = self.nm.prepare_frame(frame)      # the map's depth filter, once: tracking and fusion read one image
+        if self.odometry is not None:
+            return self._integrate_from_odometry(frame)
         given = np.asarray(frame["T_wc"], dtype=np.float64).reshape(4, 4)
         if len(self.poses) < self.warmup or self._prev_given is None:
             T, status = given, -1
@@ -182,6 +196,28 @@ class Tracker:
             T = self.last.T_wc if status == OK else T_pred
             self.failures += status != OK
         self._prev_given, self._prev_tracked = given, T
+        self.poses.append(T)
+        self.statuses.append(status)
+        fused = dict(frame)
+        fused["T_wc"] = T
+        return self.nm.integrate(fused)
+
+    def _integrate_from_odometry(self, frame):
+        """``integrate`` when the motion comes from ``self.odometry``: ``frame`` is prepared already."""
+        step = self.odometry.step(frame)
+        if self._prev_tracked is None:
+            T = np.eye(4) if frame.get("T_wc") is None else np.array(frame["T_wc"], dtype=np.float64).reshape(4, 4)
+            status = -1
+        else:
+            T_pred = self._prev_tracked @ rigid_inverse(step.T_wc)
+            T, status = T_pred, -1
+            if len(self.poses) >= self.warmup:
+                self.last = self.nm.track(frame, T_guess=T_pred, source=self.source, model_size=self.model_size,
+                                          **self.icp)
+                status = self.last.status
+                T = self.last.T_wc if status == OK else T_pred
+                self.failures += status != OK
+        self._prev_tracked = T
         self.poses.append(T)
         self.statuses.append(status)
         fused = dict(frame)

@@ -8,6 +8,8 @@ sequence directory, periodic global optimisation, mesh extraction, final artefac
     python examples/run_e2e.py --synthetic-arkit 24 --out /tmp/bnv_arkit                    # writes a synthetic one first
     python examples/run_e2e.py --sweep 60 --grid 256 --pose-drift 0.005 0.003 --track tsdf --no-optimize --out /tmp/trk
                                                     # drifting odometry, every frame aligned to the map before it is fused
+    python examples/run_e2e.py --sweep 60 --grid 256 --odometry rgbd --track tsdf --no-optimize --out /tmp/odo
+                                                    # no poses but the first: frame-to-frame odometry, then frame-to-model
     python examples/run_e2e.py ... --depth-filter                                           # smooth every depth image first
     python examples/run_e2e.py ... --plan-volume --plan-voxel-sizes 0.01 0.02 0.04         # extent and voxel size from the frames
     python examples/run_e2e.py --sweep 600 --grid 512 --decode-frames --pipelined --no-optimize --out /tmp/sweep
@@ -91,6 +93,12 @@ def main():
                          "as odometry).  Off by default: poses are taken as given")
     ap.add_argument("--track-view", type=int, nargs=2, metavar=("H", "W"),
                     help="--track: size of the rendered model view (default: the frame's)")
+    ap.add_argument("--odometry", choices=["rgbd"],
+                    help="estimate the motion between consecutive frames from the frames themselves (odometry.RgbdOdometry: "
+                         "joint photometric and depth alignment; depth only where the sequence has no colour images) "
+                         "instead of reading it from the poses: only the first frame's pose is used.  With --track the "
+                         "tracker predicts every pose from it; without, the chained motions are the poses.  Prints the "
+                         "trajectory's errors against the sequence's own poses")
     ap.add_argument("--pose-drift", type=float, nargs=2, metavar=("SIGMA_T", "SIGMA_R"),
                     help="replace the poses by drifting odometry (scan.drift_poses: a random walk of SIGMA_T metres and "
                          "SIGMA_R radians per frame and axis, seed 0); the frames are held in memory.  With --track the "
@@ -114,6 +122,8 @@ def main():
     if args.color and (args.synthetic or args.sweep or args.synthetic_arkit):
         sys.exit("--color: the sequences --synthetic, --sweep and --synthetic-arkit write hold depth only, there is no "
                  "colour image to take the colours from (a grey mesh is not written instead)")
+    has_rgb = not (args.synthetic or args.sweep or args.synthetic_arkit)
+    load_rgb = args.color or (bool(args.odometry) and has_rgb)
     depth_filter = None
     if args.depth_filter is not None:
         from bnv_fusion_amd import frontend
@@ -151,11 +161,11 @@ def main():
                                      cap["poses"], cap["dimensions"], center=cap["center"])
     if args.arkit:
         data = datasets.ARKitDataset(args.data_dir, args.scan_id, confidence_level=args.confidence_level,
-                                     skip_images=args.skip_images, device=dev, load_rgb=args.color,
+                                     skip_images=args.skip_images, device=dev, load_rgb=load_rgb,
                                      volume="plan" if args.plan_volume else "file")
     else:
         data = datasets.FusionInferenceDataset(args.data_dir, args.scan_id, skip_images=args.skip_images, device=dev,
-                                               load_rgb=args.color, volume="plan" if args.plan_volume else "file")
+                                               load_rgb=load_rgb, volume="plan" if args.plan_volume else "file")
     plan = None
     if args.plan_volume:
         # the dataset planned its extent and serves aligned frames; the candidates are counted in that frame
@@ -181,9 +191,13 @@ def main():
         truth = np.stack([np.asarray(fr["T_wc"], dtype=np.float64) for fr in data])
         drifted = scan.drift_poses(truth, args.pose_drift[0], args.pose_drift[1], seed=0)
         data = [dict(fr, T_wc=T) for fr, T in zip(data, drifted)]
+    odo, odo_poses, given_poses = None, [], []
     if args.track:
         from bnv_fusion_amd import tracking
-        tracker = tracking.Tracker(nm, source=args.track, model_size=args.track_view)
+        tracker = tracking.Tracker(nm, source=args.track, model_size=args.track_view, odometry=args.odometry)
+    elif args.odometry:
+        from bnv_fusion_amd import odometry, tracking
+        odo = odometry.RgbdOdometry(max_depth=data.max_depth)
     if args.decode_frames:
         # the per-frame loop of the benchmark metric: fuse + decode of the touched voxels, synchronous or pipelined
         from bnv_fusion_amd import sequence
@@ -198,6 +212,12 @@ def main():
     for idx, frame in enumerate(data):                                   # run_e2e.py:243-279
         t0 = time.perf_counter()
         frame = nm.prepare_frame(frame)             # --depth-filter: filtered once, for tracking, fusion and nm.frames
+        if args.odometry and not np.isnan(frame["T_wc"]).any():
+            given_poses.append(np.asarray(frame["T_wc"], dtype=np.float64))
+        if odo is not None and not np.isnan(frame["T_wc"]).any():
+            step = odo.step(frame)
+            odo_poses.append(odo_poses[-1] @ tracking.rigid_inverse(step.T_wc) if odo_poses else given_poses[0])
+            frame = dict(frame, T_wc=odo_poses[-1])
         if tracker is not None and not np.isnan(frame["T_wc"]).any():
             tracker.integrate(frame)
             frame = dict(frame, T_wc=tracker.poses[-1])              # the optimiser's rays start at the corrected pose
@@ -226,6 +246,14 @@ def main():
     if tracker is not None:
         print(f"tracking ({args.track}): {tracker.failures} of {len(tracker.poses)} frames refused by the aligner "
               "(fused with the predicted pose)")
+    if args.odometry:
+        from bnv_fusion_amd import evaluate
+        runner = tracker.odometry if tracker is not None else odo
+        e = evaluate.trajectory_errors(tracker.poses if tracker is not None else odo_poses, truth[:len(given_poses)]
+                                       if truth is not None else given_poses)
+        print(f"odometry (rgbd): {runner.failures} of {max(len(runner.statuses) - 1, 0)} pairs refused (the constant-velocity guess "
+              f"stands in); trajectory against the sequence's poses: translation RMSE {e['translation_rmse'] * 1e3:.2f} "
+              f"mm, mean rotation error {e['rotation_mean_deg']:.3f} deg over {e['n']} frames")
     if tracker is not None and truth is not None:
         compare_given_and_tracked(args, data, truth, tracker, mesh, model, nm, dev)
     steps = int(len(nm.frames) * args.skip_images) * (1 if args.mode == "demo" else 2)   # :283-284

@@ -1162,6 +1162,74 @@ int bnv_icp_align(const void* depth, int depth_dtype, int32_t H, int32_t W, cons
                   double min_pair_share, double min_spread, void* workspace, size_t ws_bytes, double* pose_out,
                   double* poses_out, double* stats_out, int32_t* status_out, bnv_stream_t stream);
 
+/* ---- Odometry (bnv_fusion_amd/csrc/odometry.hip; bnv_fusion_amd/odometry.py): frame-to-frame RGB-D odometry.  Aligns
+ * two consecutive frames (depth, and colour where there is one) by a joint photometric and depth alignment and returns
+ * the motion between them: T maps reference-camera points to current-camera points.  The reference takes every pose as
+ * given and has no such entry; tests/odometry_restatement.py restates what follows in numpy.  Every operation is one
+ * IEEE float64 rounding, in the order written (no contraction); division and sqrt are correctly rounded; what is stored
+ * in a prepared frame is rounded to float32 once.
+ *
+ * A prepared frame (bnv_rgbd_prepare; bnv_rgbd_frame_bytes(H, W, levels) bytes of device memory the caller owns, 0 for
+ * invalid sizes) holds `levels` pyramid levels, level l of H >> l by W >> l pixels (1 <= levels <= BNV_ICP_MAX_LEVELS
+ * and the last level at least 1 x 1), one after the other, each on a 256-byte boundary.  A level is an array of pixel
+ * records float32 [H_l][W_l][8] = D, I, I_x, I_y, D_x, D_y, valid (1 or 0), 0.
+ *
+ * Intensity.  rgb uint8 [H_c, W_c, 3] (device) with intrinsics K_c_host, or NULL: I = 0 everywhere (align such frames
+ * with lambda_depth = 1).  Y(j, i) = ((0.299 R + 0.587 G) + 0.114 B) of a colour pixel.  Depth pixel p along an axis
+ * with (f, c) and the colour image's (f_c, c_c), n_c pixels: lo = f_c (((p - 0.5) - c) / f) + c_c, hi the same with
+ * p + 0.5, mid with p; first = min(max(ceil(lo), 0), n_c), last = max(min(ceil(hi), n_c), first): the colour pixels
+ * first .. last - 1 have their centres in the depth pixel's footprint.  With pixels on both axes I = (sum of Y over the
+ * footprint in row-major order / (rows cols)) / 255, else the bilinear sample at (mid_x, mid_y), each clamped to
+ * [0, n_c - 1]: i0 = min(floor(x), max(n_c - 2, 0)), a = x - i0, i1 = min(i0 + 1, n_c - 1);
+ * top = Y00 + a_x (Y01 - Y00), bot = Y10 + a_x (Y11 - Y10), Y = top + a_y (bot - top); I = Y / 255.
+ * Level 0.  d as for bnv_icp_align (depth_dtype 0 / 1); D = (float)d when 0 < d <= max_depth and d is finite, else 0.
+ * depth_jump is the depth step between neighbouring pixels of level 0 that counts as an edge.  The pixels of level l
+ * are 2^l as wide and the same surface slope steps 2^l as far between them, so level l uses jump_l = 2^l depth_jump
+ * (exact): with one jump for all levels an oblique wall has no gradient-valid pixel left two levels up.
+ * Level l + 1 takes each 2 x 2 block of level l (an odd last row or column is dropped): dmin = the smallest D > 0 of
+ * the block; kept = the pixels with D > 0 and D - dmin <= jump_(l+1), so the foreground wins and nothing is averaged
+ * across an edge; D and I are the sums over the kept pixels in row-major order / their number, 0 when none is kept.
+ * Intrinsics of level l, s = 2^l: fx / s, fy / s, (cx + 0.5) / s - 0.5, (cy + 0.5) / s - 0.5.
+ * Gradients.  A pixel is gradient-valid iff it is not on the level's border, D > 0 for it and its left, right, upper
+ * and lower neighbour, and |D_neighbour - D| <= jump_l for each; then I_x = (I(u + 1) - I(u - 1)) / 2, I_y, D_x,
+ * D_y alike; else all four are 0.
+ *
+ * A pair.  At the estimate T = [R | t], reference pixel (u, v) with z = D_ref > 0:
+ *   x = (u - cx) / fx, y = (v - cy) / fy, P = (x z, y z, z);  Q_a = ((R[a][0] P0 + R[a][1] P1) + R[a][2] P2) + t_a;
+ *   reject unless Q2 > 0;  xq = fx Q0 / Q2 + cx, yq = fy Q1 / Q2 + cy;  x0 = floor(xq), y0 = floor(yq); reject unless
+ *   0 <= x0 <= W_l - 2 and 0 <= y0 <= H_l - 2;  the four pixels (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1)
+ *   of the current frame must all be gradient-valid and max D - min D of the four <= jump_l;
+ *   a = xq - x0, b = yq - y0; every plane c is sampled as top = c00 + a (c10 - c00), bot = c01 + a (c11 - c01),
+ *   top + b (bot - top) -> I1, D1, Ix, Iy, Dx, Dy;  rd = Q2 - D1: reject unless |rd| <= dist.
+ * Rows.  With s_I = sqrt(1 - lambda_depth), s_D = sqrt(lambda_depth), a row of image gradient (a, b), z-term c and
+ * scale s: a' = s a, b' = s b, c' = s c; gx = (a' fx) / Q2, gy = (b' fy) / Q2,
+ * gz = (0 - (gx Q0 + gy Q1) / Q2) - c'; J = [Q x g, g] with (Q x g)_0 = Q1 gz - Q2 gy and cyclic.  The pair adds the
+ * intensity row (Ix, Iy, 0, s_I) with r = s_I (I_ref - I1), then the depth row (Dx, Dy, 1, s_D) with r = s_D rd.
+ * J = -dr/dxi for the left twist xi = (w, v), Q' = Q + w x Q + v: A xi = sum J r is the system of bnv_icp_align, and
+ * T <- exp(xi^) T.
+ * Sums, solve, statuses, outputs and workspace are those of bnv_icp_align (BNV_ICP_*): the 29 sums take both rows of
+ * every pair and count a pair once; thread g of the BNV_ICP_BLOCKS x 256 grid takes the level's reference pixels
+ * g, g + G, ... (numbered v W_l + u); BNV_ICP_LOST compares pairs with min_pair_share H_l W_l; spread is the smallest
+ * eigenvalue of A[3:, 3:] / pairs (a constant-colour fronto-parallel plane gives exactly 0).
+ * Schedule.  schedule_host int32 [n_steps][2] = (pyramid level, iterations), 1 <= n_steps <= BNV_ICP_MAX_LEVELS,
+ * 0 <= level < levels, iterations >= 0, at least one and at most 4096 iterations in all; odometry.DEFAULT_SCHEDULE is
+ * ((2, 6), (1, 6), (0, 8)).  Workspace: bnv_rgbd_align_bytes(n_steps, schedule_host) bytes, laid out as
+ * bnv_icp_align's.  Both frames must have been prepared with the same H, W, levels and intrinsics K_host.
+ * Null pointers (rgb, poses_out excepted), invalid sizes or schedule, non-finite matrices, a zero focal length,
+ * lambda_depth outside [0, 1], max_depth, dist or depth_jump not positive and finite and negative or non-finite
+ * thresholds are BNV_ERR_INVALID_ARGUMENT before any HIP call; a buffer below its size entry is
+ * BNV_ERR_WORKSPACE_TOO_SMALL.  No allocation, synchronisation or host read. */
+size_t bnv_rgbd_frame_bytes(int32_t H, int32_t W, int32_t levels);
+size_t bnv_rgbd_align_bytes(int32_t n_steps, const int32_t* schedule_host);
+int bnv_rgbd_prepare(const void* depth, int depth_dtype, int32_t H, int32_t W, const double K_host[9],
+                     const uint8_t* rgb, int32_t H_c, int32_t W_c, const double K_c_host[9], int32_t levels,
+                     double max_depth, double depth_jump, void* frame, size_t frame_bytes, bnv_stream_t stream);
+int bnv_rgbd_align(const void* ref_frame, const void* cur_frame, int32_t H, int32_t W, int32_t levels,
+                   const double K_host[9], const double T_guess_host[16], int32_t n_steps,
+                   const int32_t* schedule_host, double lambda_depth, double dist, double depth_jump,
+                   double min_pair_share, double min_spread, void* workspace, size_t ws_bytes, double* pose_out,
+                   double* poses_out, double* stats_out, int32_t* status_out, bnv_stream_t stream);
+
 /* ---- Depth filter (bnv_fusion_amd/csrc/depth_filter.hip; bnv_fusion_amd/frontend.py: filter_depth): edge-preserving
  * smoothing of a depth image in front of the front end and the tracker.  Sensor depth is disparity-quantised (one
  * step of the reference's Kinect model is z^2 / (8 * 35.130): 3.6 mm at 1 m, 32 mm at 3 m) and the front end's 3x3
