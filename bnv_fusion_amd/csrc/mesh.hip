@@ -18,6 +18,7 @@
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
 #include "scan.hpp"
+#include "workspace.hpp"
 
 namespace bnv {
 
@@ -244,19 +245,21 @@ struct TmGrid {
 
 struct TmLayout {
   int64_t tiles, blocks;
-  size_t masks, voff, toff, bsum, bytes;
+  unsigned long long* masks;     // [tiles, 3]
+  int64_t *voff, *toff, *bsum;   // [tiles], [tiles], [blocks, 2]
+  size_t bytes;
 };
 
-static TmLayout tm_layout(int64_t n) {
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+static TmLayout tm_layout(int64_t n, const void* base) {
+  Carver c(base);
   TmLayout L;
   L.tiles = (n + 63) / 64;
   L.blocks = (L.tiles + kTmScan - 1) / kTmScan;
-  L.masks = 0;
-  L.voff = L.masks + up((size_t)L.tiles * 3 * sizeof(unsigned long long));
-  L.toff = L.voff + up((size_t)L.tiles * sizeof(int64_t));
-  L.bsum = L.toff + up((size_t)L.tiles * sizeof(int64_t));
-  L.bytes = L.bsum + up((size_t)L.blocks * 2 * sizeof(int64_t));
+  L.masks = c.take<unsigned long long>(L.tiles * 3);
+  L.voff = c.take<int64_t>(L.tiles);
+  L.toff = c.take<int64_t>(L.tiles);
+  L.bsum = c.take<int64_t>(L.blocks * 2);
+  L.bytes = c.bytes();
   return L;
 }
 
@@ -588,7 +591,7 @@ static TmGrid tm_grid(const float* tsdf, const float* weight, const int32_t* dim
 int bnv_tsdf_mesh_workspace_bytes(const int32_t dim[3], int64_t* bytes) {
   int64_t n;
   if (!bytes || !tm_dims(dim, n)) return BNV_ERR_INVALID_ARGUMENT;
-  *bytes = (int64_t)tm_layout(n).bytes;
+  *bytes = (int64_t)tm_layout(n, nullptr).bytes;
   return BNV_OK;
 }
 
@@ -598,27 +601,22 @@ int bnv_tsdf_mesh_count(const float* tsdf, const float* weight, const int32_t di
   int64_t n;
   if (!tsdf || !tm_dims(dim, n) || !tri_table || !workspace || !totals || (observed_only && !weight))
     return BNV_ERR_INVALID_ARGUMENT;
-  const TmLayout L = tm_layout(n);
+  const TmLayout L = tm_layout(n, workspace);
   if (ws_bytes < (int64_t)L.bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
   hipStream_t s = (hipStream_t)stream;
   if (dim[0] < 2 || dim[1] < 2 || dim[2] < 2) {   // no cell: an empty mesh
     BNV_HIP_CHECK(hipMemsetAsync(totals, 0, 2 * sizeof(int64_t), s));
     return BNV_OK;
   }
-  char* ws = (char*)workspace;
-  auto* masks = (unsigned long long*)(ws + L.masks);
-  auto* voff = (int64_t*)(ws + L.voff);
-  auto* toff = (int64_t*)(ws + L.toff);
-  auto* bsum = (int64_t*)(ws + L.bsum);
   const TmGrid g = tm_grid(tsdf, weight, dim, level, observed_only);
   hipLaunchKernelGGL(k_tm_count, dim3(blocks_for(L.tiles, kTmWaves)), dim3(256), 0, s, g, tri_table,
-                     L.tiles, masks, voff, toff);
+                     L.tiles, L.masks, L.voff, L.toff);
   BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_tm_scan_reduce, dim3((unsigned)L.blocks), dim3(kTmScan), 0, s, voff, toff, L.tiles, bsum);
+  hipLaunchKernelGGL(k_tm_scan_reduce, dim3((unsigned)L.blocks), dim3(kTmScan), 0, s, L.voff, L.toff, L.tiles, L.bsum);
   BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_tm_scan_top, dim3(1), dim3(kTmScan), 0, s, bsum, L.blocks, totals);
+  hipLaunchKernelGGL(k_tm_scan_top, dim3(1), dim3(kTmScan), 0, s, L.bsum, L.blocks, totals);
   BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_tm_scan_apply, dim3((unsigned)L.blocks), dim3(kTmScan), 0, s, voff, toff, L.tiles, bsum);
+  hipLaunchKernelGGL(k_tm_scan_apply, dim3((unsigned)L.blocks), dim3(kTmScan), 0, s, L.voff, L.toff, L.tiles, L.bsum);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
@@ -632,14 +630,13 @@ int bnv_tsdf_mesh_emit(const float* tsdf, const float* weight, const float* colo
   if (!tsdf || !tm_dims(dim, n) || !origin || !tri_table || !workspace || !vertices || (observed_only && !weight) ||
       n_vertices < 0 || n_faces < 0)
     return BNV_ERR_INVALID_ARGUMENT;
-  const TmLayout L = tm_layout(n);
+  const TmLayout L = tm_layout(n, workspace);
   if (ws_bytes < (int64_t)L.bytes) return BNV_ERR_WORKSPACE_TOO_SMALL;
   if (dim[0] < 2 || dim[1] < 2 || dim[2] < 2 || n_vertices == 0) return BNV_OK;
-  const char* ws = (const char*)workspace;
   const TmGrid g = tm_grid(tsdf, weight, dim, level, observed_only);
   hipLaunchKernelGGL(k_tm_emit, dim3(blocks_for(L.tiles, kTmWaves)), dim3(256), 0,
-                     (hipStream_t)stream, g, color, tri_table, L.tiles, (const unsigned long long*)(ws + L.masks),
-                     (const int64_t*)(ws + L.voff), (const int64_t*)(ws + L.toff), origin[0], origin[1], origin[2],
+                     (hipStream_t)stream, g, color, tri_table, L.tiles, (const unsigned long long*)L.masks,
+                     (const int64_t*)L.voff, (const int64_t*)L.toff, origin[0], origin[1], origin[2],
                      voxel_size, n_vertices, n_faces, vertices, faces, normals, colors);
   BNV_LAUNCH_CHECK();
   return BNV_OK;

@@ -12,18 +12,14 @@
 #include <cmath>
 
 #include "../../include/bnv_fusion.h"
-#include "bnv_common.hpp"
-#include "workspace.hpp"
+#include "mesh_face.hpp"
 
 namespace bnv {
 namespace {
 
 constexpr int kColorThreads = 256;
 constexpr int kTotSlots = 64;                         // the exact area total is spread over this many words
-constexpr double kNormalScale = 281474976710656.0;    // 2^48
-constexpr double kAreaScale50 = 1125899906842624.0;   // 2^50: the unit of mesh.connected_components' areas
-constexpr double kAreaLimit12 = 4096.0;               // total area below 2^12: |sum of rint(cross * 2^48)| < 2^61
-enum : int32_t { kErrNonFinite = 1, kErrFaceIndex = 2, kErrArea = 8 };
+constexpr double kNormalScale = 281474976710656.0;    // 2^48: |sum of rint(cross * 2^48)| < 2^61 below kAreaLimit
 
 struct NormHdr {
   unsigned long long tot_hi[kTotSlots], tot_lo[kTotSlots];   // sums of q >> 31 and q & (2^31 - 1), q = rint(area 2^50)
@@ -67,33 +63,14 @@ __global__ __launch_bounds__(kColorThreads) void k_vn_faces(const float* __restr
   int64_t q = 0;
   if (t < T) {
     int64_t c[3];
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      c[k] = fin[t * 3 + k];
-      ok &= c[k] >= 0 && c[k] < V;
-    }
+    const bool ok = load_face(fin, t, V, c);
     int32_t err = ok ? 0 : (int32_t)kErrFaceIndex;
     if (ok) {
-      double p[3][3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) p[k][a] = (double)vin[c[k] * 3 + a];
-      const double e1x = __dsub_rn(p[1][0], p[0][0]), e1y = __dsub_rn(p[1][1], p[0][1]),
-                   e1z = __dsub_rn(p[1][2], p[0][2]);
-      const double e2x = __dsub_rn(p[2][0], p[0][0]), e2y = __dsub_rn(p[2][1], p[0][1]),
-                   e2z = __dsub_rn(p[2][2], p[0][2]);
-      const double cx = __dsub_rn(__dmul_rn(e1y, e2z), __dmul_rn(e1z, e2y));
-      const double cy = __dsub_rn(__dmul_rn(e1z, e2x), __dmul_rn(e1x, e2z));
-      const double cz = __dsub_rn(__dmul_rn(e1x, e2y), __dmul_rn(e1y, e2x));
-      const double area = __dmul_rn(
-          0.5, __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(cx, cx), __dmul_rn(cy, cy)), __dmul_rn(cz, cz))));
-      if (area < kAreaLimit12) {   // (non-finite corners fail the test; |cross| = 2 area < 2^13)
-        q = (int64_t)rint(__dmul_rn(area, kAreaScale50));
-        const long long n[3] = {(long long)rint(__dmul_rn(cx, kNormalScale)),
-                                (long long)rint(__dmul_rn(cy, kNormalScale)),
-                                (long long)rint(__dmul_rn(cz, kNormalScale))};
+      double cr[3];
+      if (area_units(face_cross(vin, c, cr), q)) {   // (|cross| = 2 area < 2^13)
+        const long long n[3] = {(long long)rint(__dmul_rn(cr[0], kNormalScale)),
+                                (long long)rint(__dmul_rn(cr[1], kNormalScale)),
+                                (long long)rint(__dmul_rn(cr[2], kNormalScale))};
 #pragma unroll
         for (int k = 0; k < 3; ++k)
 #pragma unroll
@@ -105,12 +82,8 @@ __global__ __launch_bounds__(kColorThreads) void k_vn_faces(const float* __restr
     }
     if (err) atomicOr(&w.hdr->error, err);
   }
-  unsigned long long hi = (unsigned long long)q >> 31, lo = (unsigned long long)q & 0x7fffffffull;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    hi += __shfl_xor(hi, d, 64);
-    lo += __shfl_xor(lo, d, 64);
-  }
+  unsigned long long hi, lo;
+  wave_area_total(q, hi, lo);
   if ((threadIdx.x & 63) == 0 && (hi | lo)) {
     const int slot = (int)((blockIdx.x * (kColorThreads / 64) + (threadIdx.x >> 6)) % kTotSlots);
     atomicAdd(&w.hdr->tot_hi[slot], hi);
@@ -145,7 +118,7 @@ __global__ void k_vn_status(NormWs w, int32_t* status) {
     hi += w.hdr->tot_hi[k];
     lo += w.hdr->tot_lo[k];
   }
-  *status = (w.hdr->error || hi + (lo >> 31) >= (1ull << 31)) ? -1 : 0;
+  *status = (w.hdr->error || total_reaches_limit(hi, lo)) ? -1 : 0;
 }
 
 // ---- colours --------------------------------------------------------------------------------------------------------

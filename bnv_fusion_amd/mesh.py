@@ -230,6 +230,19 @@ def post_process_mesh(mesh, vertex_threshold=0.005, surface_threshold=None):
 _POST_EXTENT_LIMIT = 2.0 ** 29   # |x| / eps below it: the device neighbour grid is exact (bnv_fusion.h: 2^30 on u)
 
 
+def _upload(mesh, device):
+    """A TriMesh -> (vertices [V, 3] float32, faces [T, 3] int64) on ``device``."""
+    return (torch.from_numpy(np.ascontiguousarray(mesh.vertices, dtype=np.float32)).to(device),
+            torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int64)).to(device))
+
+
+def _workspace(query, dev, *sizes):
+    """The workspace a ``bnv_*_workspace_bytes`` entry asks for at ``sizes`` -> (uint8 tensor on ``dev``, its bytes)."""
+    need = C.c_int64()
+    _lib.check(getattr(_lib.load(), query)(*sizes, C.byref(need)), query)
+    return torch.empty(int(need.value), dtype=torch.uint8, device=dev), int(need.value)
+
+
 def post_process_mesh_tensors(vertices, faces, vertex_threshold=0.005, surface_threshold=None):
     """``post_process_mesh`` on the device (csrc/meshpost.hip; include/bnv_fusion.h, "Mesh post-processing"):
     vertices [V, 3] float32 and faces [T, 3] int64 on the GPU -> (vertices [V', 3] float32, faces [T', 3] int64) on the
@@ -267,15 +280,13 @@ def post_process_mesh_tensors(vertices, faces, vertex_threshold=0.005, surface_t
         raise ValueError(f"post_process_mesh_tensors: coordinates up to {got[1]:g} are beyond 2^29 vertex thresholds "
                          f"({eps:g}): the device neighbour grid would not be exact")
     lib = _lib.load()
-    need = C.c_int64()
-    _lib.check(lib.bnv_mesh_post_workspace_bytes(V, T, C.byref(need)), "bnv_mesh_post_workspace_bytes")
+    ws, need = _workspace("bnv_mesh_post_workspace_bytes", dev, V, T)
     with torch.cuda.device(dev):
-        ws = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
         v_out = torch.empty((V, 3), dtype=torch.float32, device=dev)
         f_out = torch.empty((T, 3), dtype=torch.int64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
         _lib.check(lib.bnv_mesh_post_process(_lib.ptr(vertices), V, _lib.ptr(faces), T, C.c_double(eps), _lib.ptr(ws),
-                                             int(need.value), _lib.ptr(v_out), _lib.ptr(f_out), _lib.ptr(counts),
+                                             need, _lib.ptr(v_out), _lib.ptr(f_out), _lib.ptr(counts),
                                              _lib.stream_ptr()), "bnv_mesh_post_process")
         nv, nf = counts.tolist()                   # the one host read of the result: the mesh's size
     if nv < 0:
@@ -286,9 +297,7 @@ def post_process_mesh_tensors(vertices, faces, vertex_threshold=0.005, surface_t
 def post_process_mesh_gpu(mesh, vertex_threshold=0.005, device="cuda:0", surface_threshold=None):
     """``post_process_mesh`` of a TriMesh on the GPU: the same TriMesh, bit for bit, through one upload and
     ``to_host``.  Same errors as post_process_mesh_tensors."""
-    v = torch.from_numpy(np.ascontiguousarray(mesh.vertices, dtype=np.float32)).to(device)
-    f = torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int64)).to(device)
-    vs, fs = post_process_mesh_tensors(v, f, vertex_threshold, surface_threshold=surface_threshold)
+    vs, fs = post_process_mesh_tensors(*_upload(mesh, device), vertex_threshold, surface_threshold=surface_threshold)
     return TriMesh(*to_host(vs, fs))
 
 
@@ -308,20 +317,35 @@ def _check_filter_args(who, min_area, min_faces, keep_largest):
     return a, int(min_faces), 0 if keep_largest is None else int(keep_largest)
 
 
-def _face_area_units(v, f):
-    """q [T] int64 = rint(area * 2^50) per face, in float64 from the float32 coordinates, one rounding per operation."""
+def _host_mesh(who, mesh):
+    """A TriMesh's arrays with the checks the host functions share -> (v [V, 3] float32, f [T, 3] int64)."""
+    v = np.asarray(mesh.vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
+    if not np.isfinite(v).all():
+        raise ValueError(f"{who}: vertices must be finite")
+    if len(f) and (len(v) == 0 or f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"{who}: a face indexes a vertex outside [0, {len(v)})")
+    return v, f
+
+
+def _face_cross64(v, f):
+    """(b - a) x (c - a) per face -> (cx, cy, cz) [T] float64 from the float32 coordinates, one rounding per operation."""
     p = v.astype(np.float64)
     a, b, c = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
     e1, e2 = b - a, c - a
     cx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
     cy = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
     cz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    return cx, cy, cz
+
+
+def _face_area_units(v, f, who="connected_components", cross=None):
+    """q [T] int64 = rint(area * 2^50) per face, one rounding per operation (``cross``: the caller's ``_face_cross64``)."""
+    cx, cy, cz = cross if cross is not None else _face_cross64(v, f)
     area = 0.5 * np.sqrt((cx * cx + cy * cy) + cz * cz)
-    if (area >= _AREA_LIMIT).any():
-        raise ValueError("connected_components: the mesh's total area reaches 2^12 square units")
-    q = np.rint(area * _AREA_SCALE).astype(np.int64)
-    if int((q >> 31).sum()) * 2 ** 31 + int((q & (2 ** 31 - 1)).sum()) >= 2 ** 62:
-        raise ValueError("connected_components: the mesh's total area reaches 2^12 square units")
+    q = None if (area >= _AREA_LIMIT).any() else np.rint(area * _AREA_SCALE).astype(np.int64)
+    if q is None or int((q >> 31).sum()) * 2 ** 31 + int((q & (2 ** 31 - 1)).sum()) >= 2 ** 62:
+        raise ValueError(f"{who}: the mesh's total area reaches 2^12 square units")
     return q
 
 
@@ -336,13 +360,8 @@ def connected_components(mesh):
     ValueError on a non-finite vertex, a face index outside [0, V), or a total area of 2^12 square units or more."""
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components as cc
-    v = np.asarray(mesh.vertices, dtype=np.float32).reshape(-1, 3)
-    f = np.asarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
-    V, T = len(v), len(f)
-    if not np.isfinite(v).all():
-        raise ValueError("connected_components: vertices must be finite")
-    if T and (V == 0 or f.min() < 0 or f.max() >= V):
-        raise ValueError(f"connected_components: a face indexes a vertex outside [0, {V})")
+    v, f = _host_mesh("connected_components", mesh)
+    T = len(f)
     if T == 0:
         return np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0, np.float64)
     q = _face_area_units(v, f)
@@ -424,14 +443,8 @@ def _refused_component_input(who, vertices, faces, V, T):
     return ValueError(f"{who}: the mesh's total area reaches 2^12 square units")      # the one check left
 
 
-def _components_workspace(lib, V, T, dev):
-    need = C.c_int64()
-    _lib.check(lib.bnv_mesh_components_workspace_bytes(V, T, C.byref(need)), "bnv_mesh_components_workspace_bytes")
-    return torch.empty(int(need.value), dtype=torch.uint8, device=dev), int(need.value)
-
-
 def connected_components_tensors(vertices, faces):
-    """``connected_components`` on the device (csrc/meshpost.hip; include/bnv_fusion.h, "Mesh components"): vertices
+    """``connected_components`` on the device (csrc/meshcomp.hip; include/bnv_fusion.h, "Mesh components"): vertices
     [V, 3] float32 and faces [T, 3] int64 on the GPU -> (labels [T] int32, n_faces [C] int64, areas [C] float64) on the
     same device, bit for bit what the host function returns.  One host read: C, which is -1 when the device's input
     checks refuse the mesh (a second read then finds which check to name).  Raises ValueError on CPU tensors, wrong shapes or dtypes, non-finite vertices, face indices outside [0, V), or a
@@ -440,8 +453,8 @@ def connected_components_tensors(vertices, faces):
     vertices, faces, V, T = _check_mesh_tensors(who, vertices, faces, "connected_components")
     dev = vertices.device
     lib = _lib.load()
+    ws, need = _workspace("bnv_mesh_components_workspace_bytes", dev, V, T)
     with torch.cuda.device(dev):
-        ws, need = _components_workspace(lib, V, T, dev)
         labels = torch.empty(T, dtype=torch.int32, device=dev)
         n_faces = torch.empty(T, dtype=torch.int64, device=dev)
         areas = torch.empty(T, dtype=torch.float64, device=dev)
@@ -460,8 +473,8 @@ def _filter_components(who, vertices, faces, min_area, min_faces, k):
     V, T = int(vertices.shape[0]), int(faces.shape[0])
     dev = vertices.device
     lib = _lib.load()
+    ws, need = _workspace("bnv_mesh_components_workspace_bytes", dev, V, T)
     with torch.cuda.device(dev):
-        ws, need = _components_workspace(lib, V, T, dev)
         v_out = torch.empty((V, 3), dtype=torch.float32, device=dev)
         f_out = torch.empty((T, 3), dtype=torch.int64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
@@ -489,9 +502,7 @@ def remove_small_components_tensors(vertices, faces, min_area=0.0, min_faces=0, 
 def remove_small_components_gpu(mesh, min_area=0.0, min_faces=0, keep_largest=None, device="cuda:0"):
     """``remove_small_components`` of a TriMesh on the GPU: the same TriMesh, bit for bit, through one upload and
     ``to_host``.  Same errors as remove_small_components_tensors."""
-    v = torch.from_numpy(np.ascontiguousarray(mesh.vertices, dtype=np.float32)).to(device)
-    f = torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int64)).to(device)
-    vs, fs = remove_small_components_tensors(v, f, min_area, min_faces, keep_largest)
+    vs, fs = remove_small_components_tensors(*_upload(mesh, device), min_area, min_faces, keep_largest)
     return TriMesh(*to_host(vs, fs))
 
 
@@ -504,31 +515,18 @@ DEFAULT_FILL = (128, 128, 128)
 def vertex_normals(mesh):
     """Area-weighted vertex normals of a TriMesh on the host -> float32 [V, 3], unit length, or (0, 0, 0) for a vertex
     no face references, that only degenerate faces touch, or whose faces cancel.  Per face the cross product
-    (b - a) x (c - a) in float64 from the float32 coordinates (the operation order of ``_face_area_units``), quantised
+    (b - a) x (c - a) in float64 from the float32 coordinates (``_face_cross64``), quantised
     to rint(x * 2^48) and summed per vertex as int64: the order of the faces does not matter.  The same bits as
     ``vertex_normals_tensors``.  Raises ValueError on a non-finite vertex, a face index outside [0, V) or a total area
     of 2^12 square units or more."""
-    v = np.asarray(mesh.vertices, dtype=np.float32).reshape(-1, 3)
-    f = np.asarray(mesh.faces, dtype=np.int64).reshape(-1, 3)
-    V, T = len(v), len(f)
-    if not np.isfinite(v).all():
-        raise ValueError("vertex_normals: vertices must be finite")
-    if T and (V == 0 or f.min() < 0 or f.max() >= V):
-        raise ValueError(f"vertex_normals: a face indexes a vertex outside [0, {V})")
-    out = np.zeros((V, 3), dtype=np.float32)
-    if T == 0:
+    v, f = _host_mesh("vertex_normals", mesh)
+    out = np.zeros((len(v), 3), dtype=np.float32)
+    if len(f) == 0:
         return out
-    try:
-        _face_area_units(v, f)
-    except ValueError:
-        raise ValueError("vertex_normals: the mesh's total area reaches 2^12 square units") from None
-    p = v.astype(np.float64)
-    a, b, c = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
-    e1, e2 = b - a, c - a
-    cross = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
-                      e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], axis=1)
-    q = np.rint(cross * _NORMAL_SCALE).astype(np.int64)
-    sums = np.zeros((V, 3), dtype=np.int64)
+    cross = _face_cross64(v, f)
+    _face_area_units(v, f, "vertex_normals", cross)
+    q = np.rint(np.stack(cross, axis=1) * _NORMAL_SCALE).astype(np.int64)
+    sums = np.zeros(out.shape, dtype=np.int64)
     for k in range(3):
         np.add.at(sums, f[:, k], q)
     some = (sums != 0).any(axis=1)
@@ -551,14 +549,12 @@ def vertex_normals_tensors(vertices, faces):
             raise ValueError(f"{who}: a face indexes a vertex outside [0, 0)")
         return torch.zeros((0, 3), dtype=torch.float32, device=dev)
     lib = _lib.load()
-    need = C.c_int64()
-    _lib.check(lib.bnv_mesh_normals_workspace_bytes(V, C.byref(need)), "bnv_mesh_normals_workspace_bytes")
+    ws, need = _workspace("bnv_mesh_normals_workspace_bytes", dev, V)
     with torch.cuda.device(dev):
-        ws = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
         out = torch.empty((V, 3), dtype=torch.float32, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.bnv_mesh_vertex_normals(_lib.ptr(vertices), V, _lib.ptr(faces), T, _lib.ptr(ws),
-                                               int(need.value), _lib.ptr(out), _lib.ptr(status), _lib.stream_ptr()),
+        _lib.check(lib.bnv_mesh_vertex_normals(_lib.ptr(vertices), V, _lib.ptr(faces), T, _lib.ptr(ws), need,
+                                               _lib.ptr(out), _lib.ptr(status), _lib.stream_ptr()),
                    "bnv_mesh_vertex_normals")
         refused = int(status.item()) < 0           # the one host read of the result
     if refused:
@@ -613,11 +609,8 @@ class VertexColorer:
         self.vertices, self.faces, self.normals = vertices, faces, normals.detach().contiguous()
         self.device, self.n_vertices, self.n_frames = vertices.device, V, 0
         self._lib = _lib.load()
-        need = C.c_int64()
-        _lib.check(self._lib.bnv_mesh_color_workspace_bytes(V, C.byref(need)), "bnv_mesh_color_workspace_bytes")
-        self._ws_bytes = int(need.value)
+        self._ws, self._ws_bytes = _workspace("bnv_mesh_color_workspace_bytes", self.device, V)
         with torch.cuda.device(self.device):
-            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
             _lib.check(self._lib.bnv_mesh_color_begin(_lib.ptr(self._ws), self._ws_bytes, V, _lib.stream_ptr()),
                        "bnv_mesh_color_begin")
 
@@ -728,9 +721,7 @@ def color_vertices(mesh_or_tensors, frames, fill=DEFAULT_FILL, return_weights=Fa
     ``depth_tol``, ``cos_min``, ``near``, ``max_depth``."""
     if isinstance(mesh_or_tensors, TriMesh):
         m = mesh_or_tensors
-        v = torch.from_numpy(np.ascontiguousarray(m.vertices, dtype=np.float32)).to(device)
-        f = torch.from_numpy(np.ascontiguousarray(m.faces, dtype=np.int64)).to(device)
-        colorer = VertexColorer(v, f, **kw).add(frames)
+        colorer = VertexColorer(*_upload(m, device), **kw).add(frames)
         out = colorer.result(fill, return_weights)
         host = to_host(colorer.normals, out[0], out[1].to(torch.uint8), *out[2:])
         m.vertex_normals, m.vertex_colors = host[0], host[1]

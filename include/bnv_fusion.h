@@ -962,7 +962,7 @@ int bnv_mesh_post_process(const float* vertices, int64_t n_vertices, const int64
                           double vertex_threshold, void* workspace, int64_t ws_bytes, float* vertices_out,
                           int64_t* faces_out, int64_t* counts, bnv_stream_t stream);
 
-/* ---- Mesh components (bnv_fusion_amd/csrc/meshpost.hip): connected components of a mesh's faces, their face counts and
+/* ---- Mesh components (bnv_fusion_amd/csrc/meshcomp.hip): connected components of a mesh's faces, their face counts and
  * areas, and the filter that removes the small ones -- mesh.connected_components / mesh.remove_small_components on the
  * device with the same output bit for bit.  This is the block the reference's o3d_helper.post_process_mesh documents
  * ("merge close vertices and remove small connected components") and keeps commented out (src/utils/o3d_helper.py:

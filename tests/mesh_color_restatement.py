@@ -35,6 +35,19 @@ def soup():
     return v, f
 
 
+def area_limit_cases():
+    """name -> (v, f, accepted): one face tiled up to the total area of 2^12 and one short of it.  4096 faces of area 1
+    are 64 waves of the normals kernel, 8192 of area 0.5 are 128: every one of its 64 total slots is added to twice.
+    In exact arithmetic (2^50 or 2^49 units per face) the total reaches 2^62 at 4096 and at 8192 faces, not before."""
+    unit = np.array([[0, 0, 0], [2, 0, 0], [0, 1, 0]], np.float32)      # area 1
+    half = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32)      # area 0.5
+    whole = np.array([[0, 0, 0], [128, 0, 0], [0, 64, 0]], np.float32)  # area 2^12 in one face
+    tile = lambda n: np.tile(np.array([[0, 1, 2]], np.int64), (n, 1))
+    return {"4095 of area 1": (unit, tile(4095), True), "4096 of area 1": (unit, tile(4096), False),
+            "8191 of area 0.5": (half, tile(8191), True), "8192 of area 0.5": (half, tile(8192), False),
+            "one face of area 2^12": (whole, tile(1), False)}
+
+
 def _cross(v, f):
     p = np.asarray(v, np.float32).astype(np.float64)
     a, b, c = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]

@@ -91,6 +91,21 @@ def test_normals_refusals():
         mesh.vertex_normals_tensors(up(many), up(np.array([[0, 1, 2], [0, 1, 2]])))
 
 
+@pytest.mark.parametrize("case", list(M.area_limit_cases()))
+def test_normals_total_area_limit(case):
+    """The total-area step over many waves and every total slot: refused exactly when the total reaches 2^12, although
+    no single face does (but in the last case); one face short of it, the restatement's bits."""
+    from bnv_fusion_amd import mesh
+    v, f, accepted = M.area_limit_cases()[case]
+    if not accepted:
+        with pytest.raises(ValueError, match="2\\^12"):
+            mesh.vertex_normals_tensors(up(v), up(f))
+        return
+    got = mesh.vertex_normals_tensors(up(v), up(f)).cpu().numpy()
+    assert got.dtype == np.float32 and (bits(got) == bits(M.vertex_normals(v, f))).all()
+    assert (got == np.array([0, 0, 1], np.float32)).all()
+
+
 # ---- colours -----------------------------------------------------------------------------------------------------------
 def poses(n):
     from bnv_fusion_amd import scan

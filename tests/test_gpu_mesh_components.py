@@ -1,4 +1,4 @@
-"""Mesh components on the GPU (csrc/meshpost.hip: bnv_mesh_components, bnv_mesh_filter_components) against the host
+"""Mesh components on the GPU (csrc/meshcomp.hip: bnv_mesh_components, bnv_mesh_filter_components) against the host
 functions mesh.connected_components / mesh.remove_small_components, bit for bit: labels, face counts, area float64 bits,
 filtered vertex float32 bits, faces."""
 import numpy as np

@@ -95,6 +95,20 @@ def test_refusals():
         ["finite", None, "area", "area"]
 
 
+@pytest.mark.parametrize("case", list(M.area_limit_cases()))
+def test_host_and_restatement_agree_at_the_total_area_limit(case):
+    """The inputs of test_gpu_mesh_color.py::test_normals_total_area_limit: the host function refuses exactly those the
+    restatement refuses, and gives the restatement's bits, (0, 0, 1), one face short of the limit."""
+    v, f, accepted = M.area_limit_cases()[case]
+    assert M.refused(v, f) == (None if accepted else "area")
+    if not accepted:
+        with pytest.raises(ValueError, match="2\\^12"):
+            mesh.vertex_normals(mesh.TriMesh(v, f))
+        return
+    got = mesh.vertex_normals(mesh.TriMesh(v, f))
+    assert (bits(got) == bits(M.vertex_normals(v, f))).all() and (got == np.array([0, 0, 1], np.float32)).all()
+
+
 def test_colors_against_ground_truth(cube, scene):
     """The restated colouring of the cube (386 vertices, 8 poses at 40 x 30, depth in uint16 millimetres, the default
     parameters) against ``synthetic.surface_color`` at the vertices.  Measured with this restatement on this scene:
