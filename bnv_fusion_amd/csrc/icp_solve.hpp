@@ -1,10 +1,12 @@
-// What the two aligners share (track.hip: frame-to-model ICP; odometry.hip: frame-to-frame RGB-D odometry): the 29
-// float64 sums of an iteration, their reduction inside a block, and the launches around them.
+// What the three aligners share (track.hip: frame-to-model ICP; odometry.hip: frame-to-frame RGB-D odometry;
+// register.hip: point-to-mesh registration): the 29 float64 sums of an iteration, their reduction inside a block, and
+// the launches around them.
 //   k_icp_init        writes the guess, the status word and the zeroed outputs.
 //   icp_block_reduce  a thread's 29 sums -> one partial row per block: a fixed __shfl_down tree per wave, LDS across the
 //                     block's four waves in wave order.
 //   k_icp_solve       one wave: sums the partial rows in ascending block order, decides the status, solves the 6 x 6
-//                     system by LDL^T, applies exp(xi^) to the pose in device memory.
+//                     system by LDL^T, applies exp(xi^) to the pose in device memory.  A step beyond IcpSolve's
+//                     limits is refused (the trackers) or, with `clamp`, scaled onto them (registration).
 // Semantics: include/bnv_fusion.h, "Tracking" (Sums, Solve); restated in float64 numpy by tests/track_restatement.py.
 // float64 throughout, one rounding per operation (-ffp-contract=off).
 #pragma once
@@ -33,6 +35,8 @@ struct IcpSolve {
   double T0[16];
   double min_pairs;   // min_pair_share * (sampled pixels of the level)
   double min_spread;
+  double max_w, max_v;   // limits of one step: radians, metres
+  int clamp;             // 0: a step beyond the limits is BNV_ICP_JUMP; 1: it is scaled onto them (register.hip)
   int iter, n_iter;
 };
 
@@ -200,7 +204,23 @@ __global__ __launch_bounds__(64) void k_icp_solve(IcpSolve a, const double* __re
       }
       wn = sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]);
       vn = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
-      if (!(wn <= BNV_ICP_MAX_ROTATION && vn <= BNV_ICP_MAX_TRANSLATION)) code = BNV_ICP_JUMP;   // (NaN too)
+      if (a.clamp) {
+        // a step beyond the limits is scaled onto them, all six components by one factor; the norms are those of the
+        // step that is applied.  Only a non-finite step is refused.
+        if (!(isfinite(wn) && isfinite(vn))) {
+          code = BNV_ICP_JUMP;
+        } else {
+          const double s = fmin(1.0, fmin(a.max_w / wn, a.max_v / vn));
+          if (s < 1.0) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) xi[i] = xi[i] * s;
+            wn = sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]);
+            vn = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
+          }
+        }
+      } else if (!(wn <= a.max_w && vn <= a.max_v)) {
+        code = BNV_ICP_JUMP;   // (NaN too)
+      }
     }
   }
   st[0] = pairs;

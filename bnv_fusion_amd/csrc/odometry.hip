@@ -373,6 +373,9 @@ int bnv_rgbd_align(const void* ref_frame, const void* cur_frame, int32_t H, int3
   IcpSolve sol;
   for (int i = 0; i < 16; ++i) sol.T0[i] = T_guess_host[i];
   sol.min_spread = min_spread;
+  sol.max_w = BNV_ICP_MAX_ROTATION;
+  sol.max_v = BNV_ICP_MAX_TRANSLATION;
+  sol.clamp = 0;
   sol.n_iter = (int)n_iter;
   RgbdPair f;
   f.s_int = sqrt(1.0 - lambda_depth);

@@ -176,6 +176,9 @@ int bnv_icp_align(const void* depth, int depth_dtype, int32_t H, int32_t W, cons
   IcpSolve sol;
   for (int i = 0; i < 16; ++i) sol.T0[i] = T_guess_host[i];
   sol.min_spread = min_spread;
+  sol.max_w = BNV_ICP_MAX_ROTATION;
+  sol.max_v = BNV_ICP_MAX_TRANSLATION;
+  sol.clamp = 0;
   sol.n_iter = (int)n_iter;
   int iter = 0;
   for (int l = 0; l < n_levels; ++l) {

@@ -211,7 +211,7 @@ def evaluate(pred_points, gt_points, threshold=0.025):
 
 
 def evaluate_meshes(pred, gt, n_samples=100000, threshold=0.025, vertices_only=False, normals=False, generator=None,
-                    device=None, gt_recall=None):
+                    device=None, gt_recall=None, align=None):
     """compute_chamfer.py:36-75 / evaluate_bnvf.py:56-72: ``n_samples`` surface samples on each mesh (TriMesh or
     (vertices, faces) device tensors), then ``evaluate``.
 
@@ -219,7 +219,14 @@ def evaluate_meshes(pred, gt, n_samples=100000, threshold=0.025, vertices_only=F
     (compute_chamfer.py:40-41) instead of surface samples.  normals: adds ``normal_consistency`` -- the signed mean of
     gt_normal . pred_normal[idx], idx from the gt -> pred query (compute_chamfer.py:66-75).  gt_recall: optionally a
     second ground truth for the recall side (a region every view saw: synthetic.gt_mesh("common")) -- the precision
-    side then uses ``gt`` and the recall side ``gt_recall``."""
+    side then uses ``gt`` and the recall side ``gt_recall``.
+
+    align: None scores the two meshes as they are.  True, or a dict of ``register.register_points`` keywords (a
+    ``T_guess`` among them), first registers the prediction's samples to the ground-truth mesh (point-to-mesh ICP,
+    register.py) and scores the transformed samples (the normals turn with them): the result gains ``"T_align"``
+    (float64 [4, 4], prediction -> ground truth), ``"align_status"`` (register.OK, ...) and the five figures before
+    alignment under ``"unaligned"``.  A refused registration scores unaligned: ``"T_align"`` is then the guess and
+    ``"align_status"`` says why."""
     if normals and vertices_only:
         raise ValueError("normals need surface samples of the ground truth (compute_chamfer.py:73)")
     dev = _device(device if device is not None else (pred[0].device if isinstance(pred, tuple) else None))
@@ -236,15 +243,34 @@ def evaluate_meshes(pred, gt, n_samples=100000, threshold=0.025, vertices_only=F
 
     p = sample_surface(pv, pf, n_samples, generator=generator, return_normals=normals)
     pred_pts = p[0]
+    pred_nrm = p[2] if normals else None
     gt_pts, gt_nrm = gt_side(gt)
-    d_pg, _ = nearest_neighbors(pred_pts, gt_pts)
-    if gt_recall is not None:
-        gt_pts, gt_nrm = gt_side(gt_recall)
-    d_gp, idx = nearest_neighbors(gt_pts, pred_pts)
-    res = metrics_from_distances(d_pg, d_gp, threshold)
-    if normals:
-        dots = (gt_nrm.double() * p[2].double()[idx]).sum(-1)
-        res["normal_consistency"] = float(dots.mean())
+    gt_pts_recall, gt_nrm_recall = gt_side(gt_recall) if gt_recall is not None else (gt_pts, gt_nrm)
+
+    def score(pts, nrm):
+        d_pg, _ = nearest_neighbors(pts, gt_pts)
+        d_gp, idx = nearest_neighbors(gt_pts_recall, pts)
+        res = metrics_from_distances(d_pg, d_gp, threshold)
+        if normals:
+            dots = (gt_nrm_recall.double() * nrm.double()[idx]).sum(-1)
+            res["normal_consistency"] = float(dots.mean())
+        return res
+
+    if align is None or align is False:
+        return score(pred_pts, pred_nrm)
+    from . import register
+    unaligned = score(pred_pts, pred_nrm)
+    kw = {} if align is True else dict(align)
+    target = _mesh_tensors(*gt) if isinstance(gt, tuple) else _mesh_tensors(gt, None, dev)
+    reg = register.register_points(pred_pts, target, **kw)
+    if reg.status == register.OK:
+        moved = register.transform_points(reg.T, pred_pts)
+        if normals:
+            pred_nrm = (pred_nrm.double() @ torch.as_tensor(reg.T[:3, :3], device=dev).T).float()
+        res = score(moved, pred_nrm)
+    else:
+        res = dict(unaligned)
+    res["T_align"], res["align_status"], res["unaligned"] = reg.T, reg.status, unaligned
     return res
 
 
@@ -272,14 +298,35 @@ def depth_errors(pred, gt, threshold=0.025):
                 within=float((e <= threshold).double().mean()))
 
 
-def trajectory_errors(est, gt):
-    """Absolute error of a trajectory against the true one, pose by pose and without any alignment of the two:
-    ``est``, ``gt`` [n, 4, 4] camera-to-world -> {"translation_rmse": metres, "rotation_mean_deg": the mean angle of
-    R_est^T R_gt, "translation_max", "rotation_max_deg", "n"}."""
+def rigid_fit(src, dst):
+    """The rigid transform (no scale) that best maps the points ``src`` [n, 3] onto ``dst`` [n, 3] in the least-squares
+    sense (Horn 1987 / Kabsch: the SVD of the centred cross-covariance, a reflection turned back) -> float64 [4, 4]."""
+    src = np.asarray(src, dtype=np.float64).reshape(-1, 3)
+    dst = np.asarray(dst, dtype=np.float64).reshape(-1, 3)
+    cs, cd = src.mean(0), dst.mean(0)
+    U, _, Vt = np.linalg.svd((dst - cd).T @ (src - cs))
+    D = np.diag([1.0, 1.0, 1.0 if np.linalg.det(U @ Vt) >= 0.0 else -1.0])
+    T = np.eye(4)
+    T[:3, :3] = U @ D @ Vt
+    T[:3, 3] = cd - T[:3, :3] @ cs
+    return T
+
+
+def trajectory_errors(est, gt, align=False):
+    """Absolute error of a trajectory against the true one, pose by pose: ``est``, ``gt`` [n, 4, 4] camera-to-world ->
+    {"translation_rmse": metres, "rotation_mean_deg": the mean angle of R_est^T R_gt, "translation_max",
+    "rotation_max_deg", "n"}.  By default without any alignment of the two; ``align=True`` first applies to ``est`` the
+    rigid transform (no scale, ``rigid_fit``) that best maps the estimated positions onto the true ones -- for a
+    trajectory in a frame of its own -- and returns it as ``"T_align"``."""
     est = np.asarray(est, dtype=np.float64).reshape(-1, 4, 4)
     gt = np.asarray(gt, dtype=np.float64).reshape(-1, 4, 4)
     if est.shape != gt.shape or len(est) == 0:
         raise ValueError(f"trajectory_errors: {est.shape} against {gt.shape}")
+    if align:
+        T_align = rigid_fit(est[:, :3, 3], gt[:, :3, 3])
+        res = trajectory_errors(T_align @ est, gt)
+        res["T_align"] = T_align
+        return res
     dt = np.linalg.norm(est[:, :3, 3] - gt[:, :3, 3], axis=1)
     tr = np.einsum("nij,nij->n", est[:, :3, :3], gt[:, :3, :3])
     ang = np.degrees(np.arccos(np.clip((tr - 1.0) / 2.0, -1.0, 1.0)))

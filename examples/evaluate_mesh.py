@@ -3,6 +3,7 @@ distance, precision, gt -> pred mean distance, recall, F1 at 2.5 cm; bnv_fusion_
 
     python examples/evaluate_mesh.py --pred a.ply --gt b.ply [--vertices-only] [--normals]     # compute_chamfer.py
     python examples/evaluate_mesh.py --pred-dir PRED --gt-dir GT --file-name final.ply          # evaluate_bnvf.py
+    python examples/evaluate_mesh.py --pred a.ply --gt b.ply --align [--align-guess POSE.txt]   # register, then score
 
 Single-pair mode mirrors src/scripts/compute_chamfer.py; directory mode mirrors src/scripts/evaluate_bnvf.py: every
 sequence directory of PRED with exactly one file whose name contains --file-name is scored against
@@ -38,14 +39,32 @@ def main():
     ap.add_argument("--n-samples", type=int, default=100000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json", help="write the figures to this file")
+    ap.add_argument("--align", action="store_true",
+                    help="register the prediction to the ground-truth mesh first (point-to-mesh ICP)")
+    ap.add_argument("--align-guess", metavar="POSE.txt",
+                    help="with --align: a 4 x 4 text matrix, prediction -> ground truth, to start from (default identity)")
     args = ap.parse_args()
+    if args.align_guess and not args.align:
+        ap.error("--align-guess goes with --align")
     dev = "cuda:0"
     gen = torch.Generator(device=dev).manual_seed(args.seed)
     kw = dict(n_samples=args.n_samples, threshold=args.threshold, vertices_only=args.vertices_only, generator=gen,
               device=dev)
+    if args.align:
+        kw["align"] = {"T_guess": np.loadtxt(args.align_guess).reshape(4, 4)} if args.align_guess else True
+
+    def report_alignment(res):
+        """Prints what --align did and makes the result JSON-ready."""
+        from bnv_fusion_amd import register
+        print(f"alignment: {register.STATUS_NAMES[res['align_status']]}; unaligned "
+              f"{evaluate.summary_line(res['unaligned'])}")
+        print(np.array2string(res["T_align"], precision=6, suppress_small=True))
+        res["T_align"] = res["T_align"].tolist()
 
     if args.pred and args.gt:
         res = evaluate.evaluate_meshes(load_ply(args.pred), load_ply(args.gt), normals=args.normals, **kw)
+        if args.align:
+            report_alignment(res)
         print("pred -> gt: ", res["pred_gt"])
         print(f"precision @ {args.threshold}:", res["accuracy"])
         print("gt -> pred: ", res["gt_pred"])
@@ -70,6 +89,8 @@ def main():
             print(f"{seq}:")
             res = evaluate.evaluate_meshes(load_ply(os.path.join(seq_dir, files[0])),
                                            load_ply(os.path.join(args.gt_dir, seq, "gt_mesh.ply")), **kw)
+            if args.align:
+                report_alignment(res)
             for k in evaluate.KEYS:
                 acc[k].append(res[k])
             out["sequences"][seq] = res

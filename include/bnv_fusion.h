@@ -1230,6 +1230,60 @@ int bnv_rgbd_align(const void* ref_frame, const void* cur_frame, int32_t H, int3
                    double min_pair_share, double min_spread, void* workspace, size_t ws_bytes, double* pose_out,
                    double* poses_out, double* stats_out, int32_t* status_out, bnv_stream_t stream);
 
+/* ---- Registration (bnv_fusion_amd/csrc/register.hip; bnv_fusion_amd/register.py): point-to-mesh ICP.  Aligns a point
+ * cloud (a reconstruction's surface samples, in its own frame) to a triangle mesh (the ground truth) from a guess and
+ * returns the rigid transform T that maps source points into the mesh's frame, so that a reconstruction can be scored
+ * in the ground truth's frame.  No camera and no rendered view: every point is paired with the exact closest point of
+ * the mesh, by the search of bnv_mesh_sdf_query over the index bnv_mesh_sdf_build made.  The reference has no such
+ * entry; tests/register_restatement.py restates what follows in numpy.  Every operation is one IEEE float64 rounding,
+ * in the order written (no contraction); division and sqrt are correctly rounded; the closest point is the fp32 one of
+ * bnv_mesh_sdf_query, bit for bit.
+ *
+ * Inputs.  mesh_index / index_bytes: the workspace bnv_mesh_sdf_build filled, only read.  points f32 [n_points, 3]
+ * (device), source frame, 1 <= n_points <= INT32_MAX.  T_guess_host float64 [16] row-major, source -> mesh.
+ *
+ * Schedule.  levels_host int32 [n_levels][2] = (stride, iterations) as for bnv_icp_align; dist_host float64
+ * [n_levels]: the pairing gate of every level in metres; register.DEFAULT_LEVELS is ((4, 10, 0.2), (2, 6, 0.05),
+ * (1, 4, 0.02)).  At stride s the sampled points are i = 0, s, 2 s, ...: n_s = ceil(n_points / s) of them, numbered
+ * i / s.  n_iter = the sum of the iterations is fixed.
+ *
+ * A pair.  At the current estimate T = [R | t], sampled point p = points[i]:
+ *   qd_a = ((R[a][0] p0 + R[a][1] p1) + R[a][2] p2) + t_a,  q = (float)qd;  a non-finite q is no pair;
+ *   c = the closest point of the mesh to q and its feature, exactly what bnv_mesh_sdf_query answers for the query q
+ *   (an index whose header does not fit index_bytes, or without a valid triangle, answers nothing: no pair);
+ *   u = (double)q - (double)c,  d2 = (u0 u0 + u1 u1) + u2 u2,  d = sqrt(d2);   reject unless d2 <= dist dist;
+ *   with reject_boundary, reject when the feature carries 0x10 (the closest edge or vertex lies on the rim of an open
+ *   mesh: a source point that hangs over the rim must not pull);
+ *   d == 0 counts as a pair and adds nothing else;  otherwise n = u / d, e = -u, r = (n0 e0 + n1 e1) + n2 e2,
+ *   J = [q x n, n] on the float64 value of the fp32 q, (q x n)_0 = q1 n2 - q2 n1 and cyclic.  The twist xi = (w, v)
+ *   multiplies on the left: T <- exp(xi^) T.  No robust weights: the gate is the outlier rule.
+ * Sums.  Those of bnv_icp_align: thread g of the BNV_ICP_BLOCKS x 256 grid takes the sampled points g, g + G, ...
+ *
+ * Solve.  That of bnv_icp_align, with one difference: registration starts further off than a tracker does, so a step
+ * beyond the limits is scaled, not refused: s = min(1, max_rotation / |w|, max_translation / |v|) and, when s < 1,
+ * every xi_a <- xi_a s; |w| and |v| of the stats and the xi of the record are those of the applied step.
+ * BNV_ICP_JUMP then only answers a step that is not finite.  BNV_ICP_LOST compares pairs with min_pair_share n_s.
+ * A sticky status restores T_guess bit for bit.  Two launches per iteration; nothing is read by the host, allocated
+ * or synchronised between the first and the last launch.
+ *
+ * Dumps (device, each optional).  q_out f32 [n_points, 3], closest_out f32 [n_points, 3], face_out int32 [n_points],
+ * feature_out uint8 [n_points]: every iteration writes, for sampled point k of its level, row k: q, and the closest
+ * point, face and feature (NaN, -1, 0 where the search answered nothing); rows n_s and up are not touched.  After the
+ * call they hold the last iteration's values.
+ * Outputs pose_out, poses_out (or NULL), stats_out, status_out and the workspace
+ * (bnv_mesh_register_bytes: partial rows, then one record per iteration) are those of bnv_icp_align.
+ * Null pointers (poses_out and the dumps excepted), n_points out of range, an invalid schedule, a dist that is not
+ * positive and finite, a non-finite T_guess, negative or non-finite thresholds, step limits that are not positive and
+ * finite and an index_bytes no index fits into are BNV_ERR_INVALID_ARGUMENT before any HIP call; a workspace below its
+ * size entry is BNV_ERR_WORKSPACE_TOO_SMALL. */
+size_t bnv_mesh_register_bytes(int32_t n_levels, const int32_t* levels_host);
+int bnv_mesh_register(const void* mesh_index, int64_t index_bytes, const float* points, int64_t n_points,
+                      const double T_guess_host[16], int32_t n_levels, const int32_t* levels_host,
+                      const double* dist_host, int32_t reject_boundary, double min_pair_share, double min_spread,
+                      double max_rotation, double max_translation, void* workspace, size_t ws_bytes,
+                      double* pose_out, double* poses_out, double* stats_out, int32_t* status_out, float* q_out,
+                      float* closest_out, int32_t* face_out, uint8_t* feature_out, bnv_stream_t stream);
+
 /* ---- Depth filter (bnv_fusion_amd/csrc/depth_filter.hip; bnv_fusion_amd/frontend.py: filter_depth): edge-preserving
  * smoothing of a depth image in front of the front end and the tracker.  Sensor depth is disparity-quantised (one
  * step of the reference's Kinect model is z^2 / (8 * 35.130): 3.6 mm at 1 m, 32 mm at 3 m) and the front end's 3x3
