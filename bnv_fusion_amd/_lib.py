@@ -189,6 +189,8 @@ SIGNATURES = {
     "bnv_mesh_components_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
     "bnv_mesh_components": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
     "bnv_mesh_filter_components": (C.c_int, [vp, i64, vp, i64, C.c_double, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "bnv_mesh_simplify_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+    "bnv_mesh_simplify": (C.c_int, [vp, i64, vp, i64, C.c_double, i32, C.c_double, vp, i64, vp, vp, vp, vp]),
     "bnv_train_param_floats": (i64, []),
     "bnv_train_running_floats": (i64, []),
     "bnv_train_workspace_bytes": (sz, [i64, i32, i64]),

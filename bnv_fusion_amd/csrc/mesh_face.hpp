@@ -1,6 +1,7 @@
 // What the mesh operators share (meshpost.hip, meshcomp.hip, meshcolor.hip): the error bits, the per-face step (corner
 // indices with their range check, float64 cross product and area, the area as an integer and its exact total), which
-// decides which meshes every entry refuses, the union-find, and the rocPRIM temporary-storage helpers.
+// decides which meshes every entry refuses, the union-find, the face step of the operators that merge vertices
+// (meshpost.hip, meshsimplify.hip), and the rocPRIM temporary-storage helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -118,6 +119,104 @@ __device__ __forceinline__ int64_t lower_bound_u64(const uint64_t* __restrict__ 
   return lo;
 }
 
+// ---- the face step: corners -> clusters, collapsed faces dropped, cyclic duplicates keep the first ---------------------
+// (meshpost.hip and meshsimplify.hip).  A face's corners go vertex -> [unique point ->] cluster; a face with two equal
+// clusters is dropped; a face rotated so its smallest cluster comes first (cyclic order kept) is a duplicate of an
+// earlier face with the same rotation, and the smallest face index of every such key is kept through an integer
+// atomic-min, so the answer does not depend on the order threads arrive in.  The pieces live in the caller's workspace.
+struct FaceStep {
+  const int32_t* inv;   // [V] vertex -> unique point, or null: the vertex itself
+  const int32_t* cl;    // [V] unique point -> cluster
+  int32_t* canon;       // [T, 3] face corners as cluster labels, rotated (canon[3t] = -1: dropped)
+  int32_t* slot_of;     // [T] hash slot of every kept face
+  int32_t* keep;        // [T]
+  int32_t* fscan;       // [T] inclusive scan of keep
+  int32_t* slots;       // [H] first face claiming a slot (-1 empty)
+  uint32_t* minf;       // [H] smallest face index with the slot's key
+  int32_t* flag;        // [V] 1 for every cluster a kept face references
+  int32_t* error;       // the header's error word
+  uint64_t H;
+};
+
+inline uint64_t face_hash_slots(int64_t T) {
+  uint64_t h = 64;
+  while (h < 2 * (uint64_t)T) h <<= 1;
+  return h;
+}
+
+__device__ __forceinline__ bool face_clusters(const int64_t* __restrict__ fin, int64_t t, int64_t V,
+                                              const FaceStep& w, int32_t c[3]) {
+  int64_t v[3];
+  if (!load_face(fin, t, V, v)) return false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) c[k] = w.cl[w.inv ? w.inv[v[k]] : (int32_t)v[k]];
+  return true;
+}
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_face_canon(const int64_t* __restrict__ fin, int64_t T, int64_t V,
+                                                        FaceStep w) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= T) return;
+  int32_t c[3];
+  int32_t* out = w.canon + t * 3;
+  if (!face_clusters(fin, t, V, w, c)) {
+    atomicOr(w.error, (int32_t)kErrFaceIndex);
+    out[0] = -1;
+    return;
+  }
+  if (c[0] == c[1] || c[1] == c[2] || c[0] == c[2]) {
+    out[0] = -1;
+    return;
+  }
+  const int lo = (c[1] < c[0]) ? ((c[2] < c[1]) ? 2 : 1) : ((c[2] < c[0]) ? 2 : 0);
+  out[0] = c[lo];
+  out[1] = c[(lo + 1) % 3];
+  out[2] = c[(lo + 2) % 3];
+}
+
+__device__ __forceinline__ uint64_t face_hash(int32_t a, int32_t b, int32_t c) {
+  uint64_t h = ((uint64_t)(uint32_t)a << 32 | (uint32_t)b) * 0x9E3779B97F4A7C15ull;
+  h ^= (uint64_t)(uint32_t)c * 0xC2B2AE3D27D4EB4Full;
+  h ^= h >> 29;
+  h *= 0xBF58476D1CE4E5B9ull;
+  h ^= h >> 32;
+  return h;
+}
+
+// canon[] was written by the previous launch, so every thread reads every face's key coherently
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_face_insert(int64_t T, FaceStep w) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= T) return;
+  const int32_t* f = w.canon + t * 3;
+  if (f[0] < 0) return;
+  const uint64_t mask = w.H - 1;
+  for (uint64_t h = face_hash(f[0], f[1], f[2]) & mask;; h = (h + 1) & mask) {
+    const int32_t owner = atomicCAS(&w.slots[h], -1, (int32_t)t);
+    const int32_t* g = w.canon + (int64_t)(owner < 0 ? t : owner) * 3;
+    if (owner < 0 || (g[0] == f[0] && g[1] == f[1] && g[2] == f[2])) {
+      atomicMin(&w.minf[h], (uint32_t)t);
+      w.slot_of[t] = (int32_t)h;
+      return;
+    }
+  }
+}
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_face_keep(int64_t T, FaceStep w) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= T) return;
+  const int32_t* f = w.canon + t * 3;
+  const int32_t keep = f[0] >= 0 && w.minf[w.slot_of[t]] == (uint32_t)t;
+  w.keep[t] = keep;
+  if (keep) {
+    w.flag[f[0]] = 1;   // referenced cluster
+    w.flag[f[1]] = 1;
+    w.flag[f[2]] = 1;
+  }
+}
+
 // ---- rocPRIM temporary storage: the bytes of a radix sort of n keys K (with int32 values, or alone), of an int32 scan --
 template <class K>
 inline size_t prim_sort_bytes(int64_t n, bool pairs = true) {
@@ -138,5 +237,19 @@ inline size_t prim_scan_bytes(int64_t n) {
 
 // rocPRIM takes the temporary storage size by reference: every call is handed the whole block (`w.tmp_bytes` into `tb`)
 #define BNV_PRIM_CHECK(expr) do { tb = w.tmp_bytes; BNV_HIP_CHECK(expr); } while (0)
+
+// The face step's launches (T > 0): keep[] and its scan fscan[], flag[] (cleared here over n_flags entries).
+inline int run_face_step(const int64_t* faces, int64_t T, int64_t V, const FaceStep& f, int64_t n_flags, void* tmp,
+                         size_t tmp_bytes, hipStream_t s) {
+  constexpr int kThreads = 256;
+  BNV_HIP_CHECK(hipMemsetAsync(f.slots, 0xff, (size_t)f.H * 4, s));
+  BNV_HIP_CHECK(hipMemsetAsync(f.minf, 0xff, (size_t)f.H * 4, s));
+  BNV_HIP_CHECK(hipMemsetAsync(f.flag, 0, (size_t)n_flags * 4, s));
+  k_face_canon<kThreads><<<blocks_for(T, kThreads), kThreads, 0, s>>>(faces, T, V, f);
+  k_face_insert<kThreads><<<blocks_for(T, kThreads), kThreads, 0, s>>>(T, f);
+  k_face_keep<kThreads><<<blocks_for(T, kThreads), kThreads, 0, s>>>(T, f);
+  BNV_HIP_CHECK(rocprim::inclusive_scan(tmp, tmp_bytes, f.keep, f.fscan, (size_t)T, rocprim::plus<int32_t>(), s));
+  return BNV_OK;
+}
 
 }  // namespace bnv

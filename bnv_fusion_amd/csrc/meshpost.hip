@@ -26,12 +26,6 @@ struct PostHdr {
   int32_t n_unique, n_clusters, n_vout, n_fout, error, pad[3];
 };
 
-static inline uint64_t hash_slots(int64_t T) {
-  uint64_t h = 64;
-  while (h < 2 * (uint64_t)T) h <<= 1;
-  return h;
-}
-
 struct PostWs {
   PostHdr* hdr;
   uint64_t* key[3];   // [V] sortable bits of u per axis
@@ -65,7 +59,7 @@ struct PostWs {
 static size_t post_ws_layout(int64_t V, int64_t T, char* base, PostWs* w) {
   Carver c(base);
   PostWs l{};
-  l.H = hash_slots(T);
+  l.H = face_hash_slots(T);
   l.hdr = c.take<PostHdr>(1);
   for (int a = 0; a < 3; ++a) l.key[a] = c.take<uint64_t>(V);
   l.ka = c.take<uint64_t>(V);
@@ -260,75 +254,9 @@ __global__ __launch_bounds__(kPostThreads) void k_pp_mean(int64_t V, PostWs w) {
   w.mean[c * 3 + 2] = __ddiv_rn(s2, dc);
 }
 
-// ---- 4. faces: corners -> clusters, degenerate ones dropped, duplicates (same cyclic order) keep the first ---------
-__device__ __forceinline__ bool face_clusters(const int64_t* __restrict__ fin, int64_t t, int64_t V, const PostWs& w,
-                                              int32_t c[3]) {
-  int64_t v[3];
-  if (!load_face(fin, t, V, v)) return false;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) c[k] = w.cl[w.inv[v[k]]];
-  return true;
-}
-
-__global__ __launch_bounds__(kPostThreads) void k_pp_face_canon(const int64_t* __restrict__ fin, int64_t T,
-                                                                int64_t V, PostWs w) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= T) return;
-  int32_t c[3];
-  int32_t* out = w.canon + t * 3;
-  if (!face_clusters(fin, t, V, w, c)) {
-    atomicOr(&w.hdr->error, (int32_t)kErrFaceIndex);
-    out[0] = -1;
-    return;
-  }
-  if (c[0] == c[1] || c[1] == c[2] || c[0] == c[2]) {
-    out[0] = -1;
-    return;
-  }
-  const int lo = (c[1] < c[0]) ? ((c[2] < c[1]) ? 2 : 1) : ((c[2] < c[0]) ? 2 : 0);
-  out[0] = c[lo];
-  out[1] = c[(lo + 1) % 3];
-  out[2] = c[(lo + 2) % 3];
-}
-
-__device__ __forceinline__ uint64_t face_hash(int32_t a, int32_t b, int32_t c) {
-  uint64_t h = ((uint64_t)(uint32_t)a << 32 | (uint32_t)b) * 0x9E3779B97F4A7C15ull;
-  h ^= (uint64_t)(uint32_t)c * 0xC2B2AE3D27D4EB4Full;
-  h ^= h >> 29;
-  h *= 0xBF58476D1CE4E5B9ull;
-  h ^= h >> 32;
-  return h;
-}
-
-// canon[] was written by the previous launch, so every thread reads every face's key coherently
-__global__ __launch_bounds__(kPostThreads) void k_pp_face_insert(int64_t T, PostWs w) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= T) return;
-  const int32_t* f = w.canon + t * 3;
-  if (f[0] < 0) return;
-  const uint64_t mask = w.H - 1;
-  for (uint64_t h = face_hash(f[0], f[1], f[2]) & mask;; h = (h + 1) & mask) {
-    const int32_t owner = atomicCAS(&w.slots[h], -1, (int32_t)t);
-    const int32_t* g = w.canon + (int64_t)(owner < 0 ? t : owner) * 3;
-    if (owner < 0 || (g[0] == f[0] && g[1] == f[1] && g[2] == f[2])) {
-      atomicMin(&w.minf[h], (uint32_t)t);
-      w.slot_of[t] = (int32_t)h;
-      return;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kPostThreads) void k_pp_face_keep(int64_t T, PostWs w) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= T) return;
-  const int32_t* f = w.canon + t * 3;
-  const int32_t keep = f[0] >= 0 && w.minf[w.slot_of[t]] == (uint32_t)t;
-  w.keep[t] = keep;
-  if (keep) {
-    w.flag[f[0]] = 1;   // referenced cluster
-    w.flag[f[1]] = 1;
-    w.flag[f[2]] = 1;
-  }
+// ---- 4. faces: the shared face step (mesh_face.hpp) over vertex -> unique point -> cluster ---------------------------
+static FaceStep face_step(const PostWs& w) {
+  return FaceStep{w.inv, w.cl, w.canon, w.slot_of, w.keep, w.fscan, w.slots, w.minf, w.flag, &w.hdr->error, w.H};
 }
 
 // ---- 5. referenced clusters only, in label order ------------------------------------------------------------------
@@ -346,12 +274,13 @@ __global__ __launch_bounds__(kPostThreads) void k_pp_vert_compact(int64_t V, int
 }
 
 __global__ __launch_bounds__(kPostThreads) void k_pp_face_write(const int64_t* __restrict__ fin, int64_t T,
-                                                                int64_t V, PostWs w, int64_t* __restrict__ fout) {
+                                                                int64_t V, PostWs w, FaceStep fs,
+                                                                int64_t* __restrict__ fout) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
   uint64_t* e = w.edges + t * 6;
   int32_t c[3];
-  if (!w.keep[t] || !face_clusters(fin, t, V, w, c)) {
+  if (!w.keep[t] || !face_clusters(fin, t, V, fs, c)) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) e[k] = kPadKey;
     return;
@@ -478,17 +407,12 @@ int bnv_mesh_post_process(const float* vertices, int64_t n_vertices, const int64
   k_pp_cstart<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, w);
   k_pp_mean<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, w);
   // 4. faces
-  BNV_HIP_CHECK(hipMemsetAsync(w.slots, 0xff, (size_t)w.H * 4, s));
-  BNV_HIP_CHECK(hipMemsetAsync(w.minf, 0xff, (size_t)w.H * 4, s));
-  BNV_HIP_CHECK(hipMemsetAsync(w.flag, 0, v * 4, s));
-  k_pp_face_canon<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(faces, T, V, w);
-  k_pp_face_insert<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(T, w);
-  k_pp_face_keep<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(T, w);
-  BNV_PRIM_CHECK(rocprim::inclusive_scan(w.tmp, tb, w.keep, w.fscan, (size_t)T, rocprim::plus<int32_t>(), s));
+  const FaceStep fs = face_step(w);
+  BNV_TRY(run_face_step(faces, T, V, fs, V, w.tmp, w.tmp_bytes, s));
   // 5. referenced vertices
   BNV_PRIM_CHECK(rocprim::inclusive_scan(w.tmp, tb, w.flag, w.scan, v, rocprim::plus<int32_t>(), s));
   k_pp_vert_compact<<<blocks_for(V, kPostThreads), kPostThreads, 0, s>>>(V, T, w);
-  k_pp_face_write<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(faces, T, V, w, faces_out);
+  k_pp_face_write<<<blocks_for(T, kPostThreads), kPostThreads, 0, s>>>(faces, T, V, w, fs, faces_out);
   // 6. smoothing over the sorted directed edges
   const int64_t E = 6 * T;
   BNV_PRIM_CHECK(rocprim::radix_sort_keys(w.tmp, tb, w.edges, w.edges_s, (size_t)E, 0, 64, s));

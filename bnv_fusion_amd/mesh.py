@@ -506,6 +506,196 @@ def remove_small_components_gpu(mesh, min_area=0.0, min_faces=0, keep_largest=No
     return TriMesh(*to_host(vs, fs))
 
 
+# ---- simplification (include/bnv_fusion.h, "Mesh simplification"; csrc/meshsimplify.hip) ----------------------------
+_SIMPLIFY_EXTENT = 2.0 ** 20     # |x| / cell below it: every axis index fits 21 bits of the cell key
+_SIMPLIFY_MAX_FACES = 2 ** 30    # corner ids 3 t + k fit 32 bits
+_PLACEMENTS = {"quadric": 0, "mean": 1}     # BNV_SIMPLIFY_QUADRIC, BNV_SIMPLIFY_MEAN
+_TARGET_RUNS = 16                # device runs of the bisection of simplify_mesh_gpu(target_faces=...)
+
+
+def _check_simplify_args(who, cell, placement, min_det):
+    if placement not in _PLACEMENTS:
+        raise ValueError(f"{who}: placement must be 'quadric' or 'mean' (got {placement!r})")
+    h, md = float(cell), float(min_det)
+    if not (np.isfinite(h) and h > 0.0):
+        raise ValueError(f"{who}: cell must be finite and > 0 (got {h})")
+    if not (np.isfinite(md) and md >= 0.0):
+        raise ValueError(f"{who}: min_det must be finite and >= 0 (got {md})")
+    return h, md
+
+
+def _ordered_sums(group, n_groups, values):
+    """values [n, k] float64 summed per group one after another in the order given -> [n_groups, k].  Round r adds
+    every group's r-th member at once: a group occurs once per round, so the sums keep their order."""
+    order = np.argsort(group, kind="stable")
+    g = group[order]
+    rank = np.arange(len(g)) - np.searchsorted(g, g, "left")
+    acc = np.zeros((n_groups, values.shape[1]))
+    by_rank = np.argsort(rank, kind="stable")
+    ends = np.searchsorted(rank[by_rank], np.arange(int(rank.max()) + 2 if len(rank) else 1))
+    for r in range(len(ends) - 1):
+        sel = by_rank[ends[r]:ends[r + 1]]
+        acc[g[sel]] = acc[g[sel]] + values[order[sel]]
+    return acc
+
+
+def simplify_mesh(mesh, cell, placement="quadric", min_det=1e-3):
+    """Simplifies a mesh by vertex clustering on a uniform grid of edge ``cell``: all vertices of a grid cell become
+    one vertex, faces that collapse are dropped.  ``placement="quadric"`` puts the vertex where the planes of the
+    faces around the cluster meet (the minimum of their area-weighted quadric, solved relative to the cell centre),
+    which keeps edges and corners sharp; the position is taken only when the quadric is well conditioned --
+    |det A| >= ``min_det`` (trace A / 3)^3, 1 for three orthogonal equal planes and 0 for a plane or a straight edge --
+    and within the cell dilated to twice its size; otherwise, and always with ``placement="mean"``, the vertex is the
+    mean of the cluster's vertices (on a plane or an edge the mean is on the surface already).  Faces: the face step
+    of ``post_process_mesh`` (two equal clusters drop a face; of faces with the same cyclic triple the first stays;
+    input order kept); vertices: the referenced clusters in ascending cell order; no smoothing.  A mesh without faces
+    gives an empty mesh.  Host function in numpy: the path the device functions are held to bit for bit; the
+    specification is include/bnv_fusion.h, "Mesh simplification".  Raises ValueError on non-finite vertices, a face
+    index outside [0, V), a coordinate 2^20 cells or more from the origin, a non-finite or non-positive ``cell`` or a
+    non-finite or negative ``min_det``.  -> a new TriMesh."""
+    who = "simplify_mesh"
+    h, min_det = _check_simplify_args(who, cell, placement, min_det)
+    v, f = _host_mesh(who, mesh)
+    V, T = len(v), len(f)
+    if V >= 2 ** 31 - 1 or T > _SIMPLIFY_MAX_FACES:
+        raise ValueError(f"{who}: {V} vertices / {T} faces: beyond 2^31 - 2 vertices or 2^30 faces")
+    p = v.astype(np.float64)
+    q = p / h
+    if V and np.abs(q).max() >= _SIMPLIFY_EXTENT:
+        raise ValueError(f"{who}: coordinates up to {np.abs(p).max():g} are 2^20 cells ({h:g}) or more from the origin")
+    if V == 0 or T == 0:
+        return TriMesh(v[:0], f[:0])
+    idx = np.floor(q).astype(np.int64)
+    key = (idx[:, 0] + 2 ** 20) << 42 | (idx[:, 1] + 2 ** 20) << 21 | (idx[:, 2] + 2 ** 20)
+    keys, first, cl = np.unique(key, return_index=True, return_inverse=True)
+    cl = cl.reshape(-1)
+    n_c = len(keys)
+    pos = _ordered_sums(cl, n_c, p) / np.bincount(cl, minlength=n_c).astype(np.float64)[:, None]
+    if placement == "quadric":
+        centre = (idx[first].astype(np.float64) + 0.5) * h                      # [n_c, 3]
+        ok = (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
+        corner = np.flatnonzero(np.repeat(ok, 3))                               # ascending corner id 3 t + k
+        fc = f[corner // 3]
+        c = cl[fc[np.arange(len(corner)), corner % 3]]
+        ctr = centre[c]
+        p0, p1, p2 = p[fc[:, 0]] - ctr, p[fc[:, 1]] - ctr, p[fc[:, 2]] - ctr
+        e1, e2 = p1 - p0, p2 - p0
+        n0 = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+        n1 = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+        n2 = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        L = np.sqrt((n0 * n0 + n1 * n1) + n2 * n2)
+        live = L != 0.0
+        c, p0, n0, n1, n2, L = c[live], p0[live], n0[live], n1[live], n2[live], L[live]
+        u0, u1, u2 = n0 / L, n1 / L, n2 / L
+        w = 0.5 * L
+        d = -((u0 * p0[:, 0] + u1 * p0[:, 1]) + u2 * p0[:, 2])
+        wu0, wu1, wu2, wd = w * u0, w * u1, w * u2, w * d
+        Q = _ordered_sums(c, n_c, np.stack([wu0 * u0, wu0 * u1, wu0 * u2, wu1 * u1, wu1 * u2, wu2 * u2,
+                                            wd * u0, wd * u1, wd * u2], 1))
+        a00, a01, a02, a11, a12, a22, b0, b1, b2 = Q.T
+        c00 = a11 * a22 - a12 * a12
+        c01 = a02 * a12 - a01 * a22
+        c02 = a01 * a12 - a02 * a11
+        c11 = a00 * a22 - a02 * a02
+        c12 = a01 * a02 - a00 * a12
+        c22 = a00 * a11 - a01 * a01
+        det = (a00 * c00 + a01 * c01) + a02 * c02
+        tr = (a00 + a11) + a22
+        r0, r1, r2 = -b0, -b1, -b2
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):     # det = 0: x infinite or NaN, refused
+            x = np.stack([((c00 * r0 + c01 * r1) + c02 * r2) / det, ((c01 * r0 + c11 * r1) + c12 * r2) / det,
+                          ((c02 * r0 + c12 * r1) + c22 * r2) / det], 1)
+            m = tr / 3.0
+            take = (tr > 0.0) & (np.abs(det) >= min_det * ((m * m) * m)) & (np.abs(x) <= h).all(1)
+        pos[take] = centre[take] + x[take]
+    fcl = cl[f]
+    fcl = fcl[(fcl[:, 0] != fcl[:, 1]) & (fcl[:, 1] != fcl[:, 2]) & (fcl[:, 0] != fcl[:, 2])]
+    if len(fcl):
+        lo = np.argmin(fcl, axis=1)
+        rot = np.take_along_axis(fcl, (lo[:, None] + np.arange(3)[None]) % 3, axis=1)
+        _, keep = np.unique(rot, axis=0, return_index=True)
+        fcl = fcl[np.sort(keep)]
+    used = np.unique(fcl)
+    remap = np.full(n_c, -1, dtype=np.int64)
+    remap[used] = np.arange(len(used))
+    return TriMesh(pos[used].astype(np.float32), remap[fcl])
+
+
+def simplify_mesh_tensors(vertices, faces, cell, placement="quadric", min_det=1e-3):
+    """``simplify_mesh`` on the device (csrc/meshsimplify.hip; include/bnv_fusion.h, "Mesh simplification"): vertices
+    [V, 3] float32 and faces [T, 3] int64 on the GPU -> (vertices [V', 3] float32, faces [T', 3] int64) on the same
+    device, bit for bit what the host function returns.  The only host reads: one for the input checks, one for the
+    two output counts.  Raises ValueError on CPU tensors, wrong shapes or dtypes, more than 2^30 faces, and on
+    everything ``simplify_mesh`` refuses."""
+    who = "simplify_mesh_tensors"
+    h, min_det = _check_simplify_args(who, cell, placement, min_det)
+    vertices, faces, V, T = _check_mesh_tensors(who, vertices, faces, "simplify_mesh")
+    if T > _SIMPLIFY_MAX_FACES:
+        raise ValueError(f"{who}: {T} faces: corner ids are 32 bits on the device (2^30 faces at most)")
+    dev = vertices.device
+    # one host read for every check: finite, face index range, extent against the cell keys
+    checks = [torch.isfinite(vertices).all().to(torch.float64)]
+    if V:
+        checks.append(vertices.abs().max().to(torch.float64))
+    if T:
+        checks += [faces.min().to(torch.float64), faces.max().to(torch.float64)]
+    got = torch.stack(checks).tolist()
+    if not got[0]:
+        raise ValueError(f"{who}: vertices must be finite")
+    if T and (V == 0 or got[-2] < 0 or got[-1] >= V):
+        raise ValueError(f"{who}: a face indexes a vertex outside [0, {V})")
+    if V and got[1] / h >= _SIMPLIFY_EXTENT:
+        raise ValueError(f"{who}: coordinates up to {got[1]:g} are 2^20 cells ({h:g}) or more from the origin")
+    lib = _lib.load()
+    ws, need = _workspace("bnv_mesh_simplify_bytes", dev, V, T)
+    with torch.cuda.device(dev):
+        v_out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        f_out = torch.empty((T, 3), dtype=torch.int64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(lib.bnv_mesh_simplify(_lib.ptr(vertices), V, _lib.ptr(faces), T, C.c_double(h),
+                                         _PLACEMENTS[placement], C.c_double(min_det), _lib.ptr(ws), need,
+                                         _lib.ptr(v_out), _lib.ptr(f_out), _lib.ptr(counts), _lib.stream_ptr()),
+                   "bnv_mesh_simplify")
+        nv, nf = counts.tolist()                   # the one host read of the result: the mesh's size
+    if nv < 0:
+        raise _lib.BnvError("bnv_mesh_simplify rejected input that passed the host-side checks")
+    return v_out[:nv], f_out[:nf]
+
+
+def simplify_mesh_gpu(mesh, cell=None, target_faces=None, placement="quadric", min_det=1e-3, device="cuda:0"):
+    """``simplify_mesh`` of a TriMesh on the GPU: the same TriMesh, bit for bit, through one upload and ``to_host``.
+    Exactly one of ``cell`` and ``target_faces`` is given.  ``target_faces``: the cell is searched on the host by a
+    geometric bisection between extent / 2^19 and extent (extent: the largest |coordinate|), 16 device runs, and the
+    run with the most faces not above the target is returned -- AT MOST ``target_faces`` faces, not the closest count:
+    the face count is not strictly monotone in the cell, and when even the coarsest run tried is above the target the
+    result is the empty mesh a single cell gives.  Same errors as simplify_mesh_tensors."""
+    who = "simplify_mesh_gpu"
+    if (cell is None) == (target_faces is None):
+        raise ValueError(f"{who}: give exactly one of cell and target_faces")
+    vt, ft = _upload(mesh, device)
+    if cell is not None:
+        return TriMesh(*to_host(*simplify_mesh_tensors(vt, ft, cell, placement, min_det)))
+    if int(target_faces) != target_faces or int(target_faces) < 0:
+        raise ValueError(f"{who}: target_faces must be an integer >= 0 (got {target_faces})")
+    _check_simplify_args(who, 1.0, placement, min_det)
+    extent = float(vt.abs().max()) if vt.numel() else 0.0
+    best = (vt[:0], ft[:0])
+    if np.isfinite(extent) and extent > 0.0:
+        lo, hi = extent / 2.0 ** 19, extent
+        for _ in range(_TARGET_RUNS):
+            mid = float(np.sqrt(lo * hi))
+            got = simplify_mesh_tensors(vt, ft, mid, placement, min_det)
+            if len(got[1]) <= int(target_faces):
+                hi = mid
+                if len(got[1]) >= len(best[1]):
+                    best = got
+            else:
+                lo = mid
+    elif not np.isfinite(extent):
+        raise ValueError(f"{who}: vertices must be finite")
+    return TriMesh(*to_host(*best))
+
+
 # ---- vertex normals and colours (include/bnv_fusion.h, "Mesh normals and colours"; csrc/meshcolor.hip) --------------
 _NORMAL_SCALE = 2.0 ** 48        # cross products are summed as integers in units of 2^-48
 COLOR_MAX_FRAMES = 8             # BNV_MESH_COLOR_MAX_FRAMES

@@ -377,12 +377,14 @@ class NeuralMap:
         return self.volume.meshlize_sdf(self.pointnet.nerf, delta)
 
     def extract_mesh(self, path=None, post_process=None, min_component_area=None, normals=False, color=None,
-                     color_options=None):
+                     color_options=None, simplify=None):
         """run_e2e.py:164-167: mesh of the whole volume (TSDF prior included when enabled) -> TriMesh or None.
         ``post_process``: None, or a vertex threshold (run_e2e.py:293 uses voxel_size / 4) -- the mesh is then
         post-processed on the device, the same as mesh.post_process_mesh(extract_mesh(), post_process).
         ``min_component_area``: None, or an area -- connected components of the post-processed mesh below it are
         removed on the device (mesh.remove_small_components); ValueError without ``post_process``.
+        ``simplify``: None, or a cell edge -- the mesh is then simplified on the device after those two stages, the
+        same as mesh.simplify_mesh(..., simplify) of their result (one vertex per grid cell, at its quadric position).
         ``normals``: the mesh carries area-weighted ``vertex_normals``.  ``color``: None; True -- the vertices are
         coloured from the key frames in ``self.frames`` that carry ``rgb`` (ValueError when none does); or an iterable
         of frame dicts with ``rgb`` (mesh.VertexColorer; ``color_options``: its keyword arguments, ``max_depth``
@@ -404,7 +406,7 @@ class NeuralMap:
         self.volume.to_tensor()
         out = self.volume.meshlize(self.pointnet.nerf, delta, path, post_process=post_process,
                                    min_component_area=min_component_area, normals=normals, color=color,
-                                   color_options=color_options)
+                                   color_options=color_options, simplify=simplify)
         return None if out is None else out[1]
 
     def render(self, T_wc, intr_mat, H, W, normals=True):

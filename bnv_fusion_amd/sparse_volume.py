@@ -636,7 +636,7 @@ class SparseVolume:
         return self._lattice_last[off + 4: off + 8].view(torch.int32)
 
     def meshlize(self, nerf, sdf_delta=None, path=None, post_process=None, min_component_area=None, normals=False,
-                 color=None, color_options=None):
+                 color=None, color_options=None, simplify=None):
         """sparse_volume.py:697-766: decode the 3x3x3 lattice of every active voxel and run per-voxel
         marching cubes -- both on the GPU.  Returns (active_pts, mesh) like the reference (None when no
         voxel straddles the surface); ``mesh`` is a bnv_fusion_amd.mesh.TriMesh (vertices / faces /
@@ -645,13 +645,15 @@ class SparseVolume:
         result) before it leaves it.  ``min_component_area``: None, or an area -- connected components of the
         post-processed mesh below it are removed on the device too (mesh.remove_small_components); it needs
         ``post_process``, because in the unwelded per-voxel concatenation every voxel's patch is its own component.
+        ``simplify``: None, or a cell edge -- the mesh is then simplified on the device (mesh.simplify_mesh_tensors:
+        one vertex per grid cell, at its quadric position) after post-processing and the component filter.
         ``normals``: the mesh carries ``vertex_normals`` (mesh.vertex_normals_tensors).  ``color``: None, or an
         iterable of frame dicts with ``rgb`` -- the mesh then carries ``vertex_colors`` (mesh.VertexColorer with
         ``color_options`` as keyword arguments; vertices no frame saw get its fill) and, implied, the normals.  Both
-        are computed on the device after post-processing and filtering, on the mesh that is returned; its vertices and
-        faces are byte for byte those of the call without them."""
-        from .mesh import (TriMesh, VertexColorer, marching_cubes_lattice_indexed, post_process_mesh_tensors, to_host,
-                           vertex_normals_tensors)
+        are computed on the device after post-processing, filtering and simplification, on the mesh that is returned;
+        its vertices and faces are byte for byte those of the call without them."""
+        from .mesh import (TriMesh, VertexColorer, marching_cubes_lattice_indexed, post_process_mesh_tensors,
+                           simplify_mesh_tensors, to_host, vertex_normals_tensors)
         if min_component_area is not None and post_process is None:
             raise ValueError("meshlize: min_component_area needs post_process (a vertex threshold): the unwelded "
                              "per-voxel mesh has one component per voxel patch")
@@ -666,6 +668,8 @@ class SparseVolume:
         if post_process is not None:
             verts, faces = post_process_mesh_tensors(verts, faces, float(post_process),
                                                      surface_threshold=min_component_area)
+        if simplify is not None:
+            verts, faces = simplify_mesh_tensors(verts, faces, float(simplify))
         attrs = []
         if (normals or color is not None) and verts.shape[0]:
             attrs.append(vertex_normals_tensors(verts, faces))

@@ -77,6 +77,10 @@ def main():
                     help="remove connected components of the post-processed meshes whose surface is below A square "
                          "metres (the block the reference keeps commented out in o3d_helper.post_process_mesh, there "
                          "with 0.1), on either --post-process route; prints what the final mesh lost")
+    ap.add_argument("--simplify", type=float, metavar="CELL",
+                    help="simplify the final mesh on the GPU after post-processing and the component filter: one "
+                         "vertex per grid cell of CELL metres, at its quadric position (mesh.simplify_mesh_gpu); "
+                         "colours are computed on the simplified mesh")
     ap.add_argument("--arkit", action="store_true",
                     help="read --data-dir/--scan-id as an iPhone / iPad LiDAR capture (3D Scanner app, 'All Data')")
     ap.add_argument("--confidence-level", type=int, default=2,
@@ -285,6 +289,12 @@ def main():
         print(f"components: {len(areas)}, the largest holds {share} of the area; below "
               f"{args.min_component_area:g} m^2: {int(gone.sum())} components, {n_before - len(mesh.faces)} faces, "
               f"{areas[gone].sum():.6f} m^2 removed")
+    if mesh is not None and args.simplify is not None:
+        from bnv_fusion_amd.mesh import simplify_mesh_gpu
+        n_v, n_f = len(mesh.vertices), len(mesh.faces)
+        mesh = simplify_mesh_gpu(mesh, cell=args.simplify, device=dev)
+        print(f"simplify ({args.simplify:g} m cells): {n_v} vertices / {n_f} faces -> {len(mesh.vertices)} / "
+              f"{len(mesh.faces)}")
     if mesh is not None and args.color:
         from bnv_fusion_amd.mesh import color_vertices
         _, observed = color_vertices(mesh, nm.frames, max_depth=max_depth, device=dev)

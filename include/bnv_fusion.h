@@ -1004,6 +1004,43 @@ int bnv_mesh_filter_components(const float* vertices, int64_t n_vertices, const 
                                int64_t ws_bytes, float* vertices_out, int64_t* faces_out, int64_t* counts,
                                bnv_stream_t stream);
 
+/* ---- Mesh simplification (bnv_fusion_amd/csrc/meshsimplify.hip): vertex clustering on a uniform grid with quadric
+ * placement -- mesh.simplify_mesh on the device with the same output bit for bit.  All arithmetic is float64, one
+ * rounding per operation in the order written, no contraction; sqrt and division are correctly rounded.
+ * tests/mesh_simplify_restatement.py states every step as code.
+ *
+ * Input: vertices f32 [V, 3], faces i64 [T, 3], cell h > 0, placement, min_det >= 0.
+ * 1. Cells.  i_a = floor(double(x_a) / h) per axis; key = (ix + 2^20) << 42 | (iy + 2^20) << 21 | (iz + 2^20).  Clusters
+ *    are the distinct keys, numbered in ascending key order.  Cell centre c_a = (i_a + 0.5) * h.
+ * 2. Mean: the float64 coordinates of ALL the cluster's vertices (referenced by a face or not), summed one after another
+ *    in ascending vertex index, divided by their number.
+ * 3. Quadric (BNV_SIMPLIFY_QUADRIC).  Corner 3 t + k belongs to the cluster of vertex faces[t][k]; a cluster's corners
+ *    are taken in ascending corner id (a face with two corners in a cluster counts twice).  Per corner, with the face's
+ *    vertices minus the cluster's cell centre as p0, p1, p2: e1 = p1 - p0, e2 = p2 - p0, n = (e1y*e2z - e1z*e2y,
+ *    e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x), L = sqrt((n0*n0 + n1*n1) + n2*n2).  L == 0 or a repeated index: nothing.
+ *    Else u = n / L, w = 0.5 * L, d = -((u0*p0x + u1*p0y) + u2*p0z); A_ij += (w*u_i)*u_j for ij = 00 01 02 11 12 22 and
+ *    b_i += (w*d)*u_i.  Then c00 = A11*A22 - A12*A12, c01 = A02*A12 - A01*A22, c02 = A01*A12 - A02*A11,
+ *    c11 = A00*A22 - A02*A02, c12 = A01*A02 - A00*A12, c22 = A00*A11 - A01*A01, det = (A00*c00 + A01*c01) + A02*c02,
+ *    tr = (A00 + A11) + A22, r = -b, x_i = ((c_i0*r0 + c_i1*r1) + c_i2*r2) / det (c symmetric).  The position c + x is
+ *    taken iff tr > 0, |det| >= min_det * (((tr/3)*(tr/3))*(tr/3)) and every |x_a| <= h; otherwise, and always with
+ *    BNV_SIMPLIFY_MEAN, the mean.  The result is rounded to float32 once.
+ * 4. Faces: the face step of the post-processing (corners -> clusters, faces with two equal clusters dropped, of faces
+ *    with the same cyclic triple the first kept, input order kept); only referenced clusters come out, in key order.
+ *
+ * Workspace: bnv_mesh_simplify_bytes (~52 B per vertex + ~80 B per face; V < 2^31 - 1, T <= 2^30 so that corner ids fit
+ * 32 bits, else BNV_ERR_INVALID_ARGUMENT).  bnv_mesh_simplify writes vertices_out f32 [V, 3] and faces_out i64 [T, 3]
+ * (capacities of the input's size) and the device int64[2] counts = {V', T'}; rows past the counts are unspecified.
+ * Nothing is clamped: a non-finite vertex, a face index outside [0, V) or a coordinate with |x| / h >= 2^20 gives
+ * counts = {-1, -1}; a non-finite or non-positive cell, a non-finite or negative min_det or an unknown placement is
+ * BNV_ERR_INVALID_ARGUMENT.  No faces (or no vertices) gives an empty mesh.  No allocation, synchronisation or host
+ * read: the caller reads the two counts. */
+#define BNV_SIMPLIFY_QUADRIC 0
+#define BNV_SIMPLIFY_MEAN 1
+int bnv_mesh_simplify_bytes(int64_t n_vertices, int64_t n_faces, int64_t* bytes);
+int bnv_mesh_simplify(const float* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, double cell,
+                      int32_t placement, double min_det, void* workspace, int64_t ws_bytes, float* vertices_out,
+                      int64_t* faces_out, int64_t* counts, bnv_stream_t stream);
+
 /* ---- Training of the local shape embedding (bnv_fusion_amd/csrc/train.hip): the reference's
  * LitFusionPointNet.training_step with training_global=False (local_point_fusion.py:381-460), in exact fp32.
  *
