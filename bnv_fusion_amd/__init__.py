@@ -42,7 +42,7 @@ from . import register  # noqa: F401,E402
 from .register import register_mesh, register_points  # noqa: F401,E402
 from .frontend import DepthFilter, filter_depth  # noqa: F401,E402
 from . import plan  # noqa: F401,E402
-from .plan import VolumePlan, VolumePlanner, plan_volume  # noqa: F401,E402
+from .plan import ManhattanFrame, VolumePlan, VolumePlanner, plan_volume  # noqa: F401,E402
 
 
 MLP_MODE_FP32_EXACT = 0     # v_mfma_f32_32x32x2_f32

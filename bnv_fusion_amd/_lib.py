@@ -244,6 +244,8 @@ SIGNATURES = {
                                   vp]),
     "bnv_plan_count": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                  C.c_double, vp, C.c_int, C.POINTER(Grid), C.c_int, i64, vp, sz, vp, vp]),
+    "bnv_plan_normals": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                   C.c_double, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

@@ -1,9 +1,12 @@
 // plan.hip -- planning the fusion volume from the depth frames themselves (bnv_plan_extent, bnv_plan_count;
 // include/bnv_fusion.h, "Volume planning"; bnv_fusion_amd/plan.py).  Two passes over the frames, both built on the
 // float64 front end (frontend.hpp: pixel_valid, world_point) and on the encoder's voxelisation (bnv_common.hpp:
-// in_bounds, voxel_coord; encode.hpp: corner_xyz, voxel_id), so that every number is the one a fusion run would see:
+// in_bounds, voxel_coord; encode.hpp: corner_xyz, voxel_id), so that every number is the one a fusion run would see;
+// before them an optional pass 0 (bnv_plan_normals) for scenes whose world frame is not the room's:
 //
-//   k_plan_extent   pass 1: per valid pixel and direction d, the bin of t = d . p in a histogram of uint64 counters that
+//   k_plan_normals  pass 0: per pixel with four valid neighbours a float64 normal, binned on a cube map; per bin the
+//                   count and the fixed-point sum of the normals.  The host finds the Manhattan frame in it.
+//   k_plan_extent  pass 1: per valid pixel and direction d, the bin of t = d . p in a histogram of uint64 counters that
 //                   accumulates over the frames.  The host reads the histograms once and takes the (trimmed) extent
 //                   along every direction from them: the bounds, and the yaw that minimises the footprint.
 //   k_plan_count    pass 2: per valid pixel and candidate voxel size, the 8 corner voxels of the point go into a hash
@@ -12,7 +15,8 @@
 //   k_plan_reduce   the table -> the frame's row (valid points, touched voxels, histogram of pair counts), leaving the
 //                   table clean for the next frame;  k_plan_finish flags a table that went past half load.
 //
-// All of it is integer counting: any schedule gives the same result, tests/plan_restatement.py restates it in numpy.
+// All of it is integer counting: any schedule gives the same result, tests/plan_restatement.py (passes 1 and 2) and
+// tests/manhattan_restatement.py (pass 0) restate it in numpy.
 #include "encode.hpp"
 #include "frontend.hpp"
 #include "workspace.hpp"
@@ -29,6 +33,143 @@ constexpr int kPlanHistCap = 64;      // BNV_PLAN_HIST_CAP: pair counts of 64 or
 constexpr int kPlanWindow = 256;      // bins of the in-workgroup window of pass 1 (one per thread)
 constexpr uint32_t kPlanEmpty = 0xffffffffu;   // (voxel ids are below 2^31)
 constexpr int64_t kPlanMaxPixels = (int64_t)1 << 24;
+
+// ---- pass 0 ------------------------------------------------------------------------------------------------------
+// The normal histogram of the Manhattan frame (plan.py: ManhattanFrame; tests/manhattan_restatement.py).  Per pixel a
+// central-difference normal over a baseline of `step` pixels, float64 with one rounding per operation in the written
+// order, rotated into the world, binned on a cube map of n_side x n_side cells a face.  What is accumulated per bin is
+// integer: the count and the normal's components in 2^-20 fixed point.
+struct PlanNormalsArgs {
+  FrontArgs front;
+  int step, n_side;
+  double jump;
+  unsigned long long* hist;   // [6 n_side^2][4]: count, sum n_x, sum n_y, sum n_z (two's complement)
+};
+
+constexpr int kPlanNormalSlots = 512;     // twice the workgroup's pixels: the LDS table never passes half load
+constexpr double kPlanNormalScale = 1048576.0;   // 2^20
+
+// depth in metres as this pass reads it: 0 < z <= max_depth and finite, and the confidence gate; else 0.  Deliberately
+// not depth_at (frontend.hpp), whose mask is the reference's z < max_depth: pass 0 is defined with the inclusive bound
+// of the tracking entries, and its gate applies to all five pixels of the stencil.  A pixel at exactly max_depth thus
+// votes for a direction here and is no point in passes 1 and 2; it only votes, so no bound or count depends on it.
+__device__ __forceinline__ double plan_normal_depth(const FrontArgs& a, int y, int x) {
+  const size_t i = (size_t)y * a.W + x;
+  double d;
+  if (a.dtype == 0) d = __ddiv_rn((double)((const uint16_t*)a.depth)[i], 1000.0);
+  else if (a.dtype == 1) d = (double)((const float*)a.depth)[i];
+  else d = ((const double*)a.depth)[i];
+  return (isfinite(d) && d > 0.0 && d <= a.max_depth && conf_ok(a, (int64_t)i)) ? d : 0.0;
+}
+
+__device__ __forceinline__ void plan_camera_point(const FrontArgs& a, int y, int x, double z, double (&p)[3]) {
+  p[0] = __dmul_rn(__ddiv_rn(__dsub_rn((double)x, a.cx), a.fx), z);
+  p[1] = __dmul_rn(__ddiv_rn(__dsub_rn((double)y, a.cy), a.fy), z);
+  p[2] = z;
+}
+
+__device__ __forceinline__ double plan_dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
+  return __dadd_rn(__dadd_rn(__dmul_rn(a0, b0), __dmul_rn(a1, b1)), __dmul_rn(a2, b2));
+}
+
+// The bin and the fixed-point normal of pixel (y, x); false when the pixel does not count.
+__device__ __forceinline__ bool plan_normal_of(const PlanNormalsArgs& p, int y, int x, int& bin, int (&fx)[3]) {
+  const FrontArgs& a = p.front;
+  const int s = p.step;
+  if (x - s < 0 || x + s >= a.W || y - s < 0 || y + s >= a.H) return false;
+  const double zc = plan_normal_depth(a, y, x);
+  if (!(zc > 0.0)) return false;
+  const double zl = plan_normal_depth(a, y, x - s), zr = plan_normal_depth(a, y, x + s);
+  const double zu = plan_normal_depth(a, y - s, x), zd = plan_normal_depth(a, y + s, x);
+  if (!(zl > 0.0 && zr > 0.0 && zu > 0.0 && zd > 0.0)) return false;
+  const double gate = __dmul_rn(p.jump, zc);
+  if (!(fabs(__dsub_rn(zl, zc)) <= gate && fabs(__dsub_rn(zr, zc)) <= gate && fabs(__dsub_rn(zu, zc)) <= gate &&
+        fabs(__dsub_rn(zd, zc)) <= gate))
+    return false;
+  double pc[3], pl[3], pr[3], pu[3], pd[3];
+  plan_camera_point(a, y, x, zc, pc);
+  plan_camera_point(a, y, x - s, zl, pl);
+  plan_camera_point(a, y, x + s, zr, pr);
+  plan_camera_point(a, y - s, x, zu, pu);
+  plan_camera_point(a, y + s, x, zd, pd);
+  const double e[3] = {__dsub_rn(pr[0], pl[0]), __dsub_rn(pr[1], pl[1]), __dsub_rn(pr[2], pl[2])};
+  const double f[3] = {__dsub_rn(pd[0], pu[0]), __dsub_rn(pd[1], pu[1]), __dsub_rn(pd[2], pu[2])};
+  double n[3] = {__dsub_rn(__dmul_rn(e[1], f[2]), __dmul_rn(e[2], f[1])),
+                 __dsub_rn(__dmul_rn(e[2], f[0]), __dmul_rn(e[0], f[2])),
+                 __dsub_rn(__dmul_rn(e[0], f[1]), __dmul_rn(e[1], f[0]))};
+  if (plan_dot3(n[0], n[1], n[2], pc[0], pc[1], pc[2]) > 0.0) {   // face the camera
+    n[0] = -n[0];
+    n[1] = -n[1];
+    n[2] = -n[2];
+  }
+  double w[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) w[r] = plan_dot3(a.T[4 * r], a.T[4 * r + 1], a.T[4 * r + 2], n[0], n[1], n[2]);
+  const double len = __dsqrt_rn(plan_dot3(w[0], w[1], w[2], w[0], w[1], w[2]));
+  if (!(len > 0.0) || !isfinite(len)) return false;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) w[r] = __ddiv_rn(w[r], len);
+  int m = 0;
+  if (fabs(w[1]) > fabs(w[m])) m = 1;
+  if (fabs(w[2]) > fabs(w[m])) m = 2;   // (ties: the lower index)
+  const double wm = m == 0 ? w[0] : (m == 1 ? w[1] : w[2]);
+  const double wa = m == 0 ? w[1] : (m == 1 ? w[2] : w[0]);
+  const double wb = m == 0 ? w[2] : (m == 1 ? w[0] : w[1]);
+  const double am = fabs(wm);
+  if (!(am > 0.0)) return false;        // (cannot happen for a finite positive length; keeps the divisions defined)
+  const double side = (double)p.n_side;
+  double qa = floor(__dmul_rn(__dmul_rn(__dadd_rn(__ddiv_rn(wa, am), 1.0), 0.5), side));
+  double qb = floor(__dmul_rn(__dmul_rn(__dadd_rn(__ddiv_rn(wb, am), 1.0), 0.5), side));
+  qa = !(qa >= 0.0) ? 0.0 : (qa > side - 1.0 ? side - 1.0 : qa);
+  qb = !(qb >= 0.0) ? 0.0 : (qb > side - 1.0 ? side - 1.0 : qb);
+  const int face = 2 * m + (wm < 0.0 ? 1 : 0);
+  bin = (face * p.n_side + (int)qa) * p.n_side + (int)qb;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) fx[r] = (int)rint(__dmul_rn(w[r], kPlanNormalScale));   // |.| <= 2^20
+  return true;
+}
+
+// One thread per pixel.  The pixels of a workgroup on one wall share one or two bins, so nothing goes to global memory
+// pixel by pixel: a workgroup sums what shares a bin in an LDS table keyed by bin (key claimed by CAS, linear probing;
+// 256 pixels in 512 slots always find one) -- 256 normals of at most 2^20 a component fit int32 -- and then adds each
+// occupied slot to the histogram with four 64-bit atomics on one 32-byte row.
+__global__ __launch_bounds__(kPlanThreads) void k_plan_normals(PlanNormalsArgs p) {
+  __shared__ uint32_t s_key[kPlanNormalSlots];
+  __shared__ int s_val[kPlanNormalSlots][4];
+  const FrontArgs& a = p.front;
+  const int64_t n = (int64_t)a.H * a.W;
+  const int64_t i = (int64_t)blockIdx.x * kPlanThreads + threadIdx.x;
+  for (int s = threadIdx.x; s < kPlanNormalSlots; s += kPlanThreads) {
+    s_key[s] = kPlanEmpty;
+    s_val[s][0] = s_val[s][1] = s_val[s][2] = s_val[s][3] = 0;
+  }
+  int bin = 0, fx[3] = {0, 0, 0};
+  const bool counts = i < n && plan_normal_of(p, (int)(i / a.W), (int)(i % a.W), bin, fx);
+  __syncthreads();
+  if (counts) {
+    uint32_t s = ((uint32_t)bin * 0x9E3779B1u) >> 23;   // 9 bits: kPlanNormalSlots
+    for (int probe = 0; probe < kPlanNormalSlots; ++probe) {
+      uint32_t k = __hip_atomic_load(&s_key[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (k == kPlanEmpty) k = atomicCAS(&s_key[s], kPlanEmpty, (uint32_t)bin);
+      if (k == kPlanEmpty || k == (uint32_t)bin) {
+        atomicAdd(&s_val[s][0], 1);
+        atomicAdd(&s_val[s][1], fx[0]);
+        atomicAdd(&s_val[s][2], fx[1]);
+        atomicAdd(&s_val[s][3], fx[2]);
+        break;
+      }
+      s = (s + 1u) & (uint32_t)(kPlanNormalSlots - 1);
+    }
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < kPlanNormalSlots; s += kPlanThreads) {
+    const uint32_t k = s_key[s];
+    if (k == kPlanEmpty) continue;
+    unsigned long long* row = p.hist + (size_t)k * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) atomicAdd(&row[c], (unsigned long long)(long long)s_val[s][c]);
+  }
+}
 
 // ---- pass 1 ------------------------------------------------------------------------------------------------------
 struct PlanExtentArgs {
@@ -338,6 +479,26 @@ extern "C" int bnv_plan_workspace_reset(void* workspace, size_t ws_bytes, int H,
     BNV_HIP_CHECK(hipMemsetAsync(t[s].keys, 0xff, (size_t)t[s].slots * 4, stream));
     BNV_HIP_CHECK(hipMemsetAsync(t[s].counts, 0, (size_t)t[s].slots * 4, stream));
   }
+  return BNV_OK;
+}
+
+extern "C" int bnv_plan_normals(const void* depth, int depth_dtype, int H, int W, const double* intr_host,
+                                const double* T_wc_host, double max_depth, const uint8_t* conf, int conf_level, int step,
+                                double jump, int n_side, int64_t* hist, bnv_stream_t stream_) {
+  if (!plan_frame_args_ok(depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth, conf, conf_level) || !hist ||
+      step < 1 || step > 64 || !(std::isfinite(jump) && jump > 0.0) || n_side < 4 || n_side > 64)
+    return BNV_ERR_INVALID_ARGUMENT;
+  PlanNormalsArgs p{};
+  front_args_fill(p.front, depth, depth_dtype, H, W, intr_host, T_wc_host, max_depth);
+  p.front.conf = conf;
+  p.front.conf_level = conf_level;
+  p.step = step;
+  p.n_side = n_side;
+  p.jump = jump;
+  p.hist = (unsigned long long*)hist;
+  const unsigned n_blocks = blocks_for((int64_t)H * W, kPlanThreads);
+  hipLaunchKernelGGL(k_plan_normals, dim3(n_blocks), dim3(kPlanThreads), 0, (hipStream_t)stream_, p);
+  BNV_LAUNCH_CHECK();
   return BNV_OK;
 }
 

@@ -163,9 +163,14 @@ def _scaled_intrinsics(intr, sy, sx):
 
 def _plan_extent(dataset, plan_options):
     """``volume="plan"``: pass 1 of the volume planner (plan.VolumePlanner) over the dataset's own frames, served
-    unaligned -> its Extent.  ``plan_options``: keyword arguments of VolumePlanner (trim, margin, align_yaw, up, ...)."""
+    unaligned -> its Extent.  ``plan_options``: keyword arguments of VolumePlanner (trim, margin, align_yaw, up, ...);
+    with ``align="manhattan"`` among them its pass 0 runs first and the frames are served in the scene's own axes."""
     from .plan import VolumePlanner
     planner = VolumePlanner(device=dataset.device, max_depth=dataset.max_depth, **(plan_options or {}))
+    if planner.align == "manhattan":
+        for k in range(len(dataset)):
+            planner.add_normals(dataset[k])
+        planner.manhattan()
     for k in range(len(dataset)):
         planner.add(dataset[k])
     return planner.extent()

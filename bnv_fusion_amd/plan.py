@@ -19,7 +19,14 @@ poses alone, in two passes on the GPU and without evaluating any network:
     for f in frames:
         nm.integrate(plan.apply(f))
 
-tests/plan_restatement.py is the definition in numpy.  GPU only: there is no CPU fallback.
+With ``align="manhattan"`` a pass 0 (``VolumePlanner.add_normals`` / ``manhattan``) comes first, for worlds whose axes
+are not the room's: a histogram of per-pixel normals on a cube map, from which the host finds the scene's three dominant
+orthogonal plane directions and which of them is down (``ManhattanFrame``); ``axis_align_mat``'s rotation is that frame.
+
+    plan = plan_volume(frames, align="manhattan")        # frames in the first camera's frame, say
+
+tests/plan_restatement.py and tests/manhattan_restatement.py are the definition in numpy.  GPU only: there is no CPU
+fallback.
 """
 import ctypes as C
 import dataclasses
@@ -86,6 +93,113 @@ class Extent:
     n_frames: int
     n_skipped: int
     hist: np.ndarray
+    manhattan: object = None   # the ManhattanFrame whose rotation axis_align_mat carries (align="manhattan"), or None
+
+
+@dataclasses.dataclass
+class ManhattanFrame:
+    """Result of pass 0: the scene's three dominant orthogonal plane directions.  ``R`` [3, 3]: its rows are the frame's
+    x, y (down, the datasets' convention) and z axes in the world, so ``R @ p`` is a world point in the frame;
+    ``axis_mass`` [3]: the share of all normals within ``cone`` degrees of +-x, +-y, +-z; ``confidence``: their sum."""
+    R: np.ndarray
+    confidence: float
+    axis_mass: np.ndarray
+    n_normals: int
+    n_frames: int
+
+
+NORMAL_SCALE = 2.0 ** 20   # fixed point of the normal sums (csrc/plan.hip: kPlanNormalScale)
+_N_FIRST, _N_ANGLES, _N_ROUNDS = 16, 45, 5
+
+
+def _dot(v, a):
+    """v [..., 3] against ONE vector a [3], in a fixed order of operations."""
+    return (v[..., 0] * a[0] + v[..., 1] * a[1]) + v[..., 2] * a[2]
+
+
+def _bin_centres(n_side):
+    """float64 [6 n_side^2, 3]: the unit vector through the middle of every cube-map bin, in bin order."""
+    q = (np.arange(n_side) + 0.5) * 2.0 / n_side - 1.0
+    c = np.zeros((6, n_side, n_side, 3))
+    for face in range(6):
+        m = face // 2
+        c[face, ..., m] = -1.0 if face & 1 else 1.0
+        c[face, ..., (m + 1) % 3] = q[:, None]
+        c[face, ..., (m + 2) % 3] = q[None, :]
+    c = c.reshape(-1, 3)
+    return c / np.sqrt((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2])[:, None]
+
+
+def _nearest_rotation(M):
+    U, _, Vt = np.linalg.svd(M)
+    return U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt
+
+
+def manhattan_from_histogram(hist, n_side, cone=10.0, min_confidence=0.3, down=(0.0, 1.0, 0.0), view=(0.0, 0.0, 1.0),
+                             n_frames=0):
+    """The ``ManhattanFrame`` of a normal histogram (int64 [6 n_side^2, 4] of bnv_plan_normals), float64 on the
+    integers alone.  Coarse: each of the 16 fullest bins as the first axis, 45 angles in [0, 90) degrees about it, scored
+    by the count in bins whose centre lies within ``cone`` degrees of a signed axis (the earlier candidate wins a tie).
+    Five rounds of refinement: every axis becomes the sign-folded sum of the fixed-point normal sums of its cone's bins
+    -- the sums, not the centres: no half-bin bias -- and the three, each weighted by the count in its cone (an axis that
+    a few stray normals define must not turn the other two), are projected to the nearest rotation by SVD.  ``down`` (the
+    mean camera down) names +y, ``view`` (the first frame's viewing direction) picks +z among the horizontal axes."""
+    hist = np.asarray(hist, dtype=np.int64)
+    count, sums = hist[:, 0], hist[:, 1:].astype(np.float64)
+    total = int(count.sum())
+    refuse = ("a Manhattan frame is not defined for this scene: plan it with a known up axis (up=, align_yaw=) "
+              "instead of align=\"manhattan\"")
+    if total == 0:
+        raise _lib.BnvError(f"volume planning: no pixel gave a normal (0 normals in {n_frames} frames); {refuse}")
+    centres, cos_cone = _bin_centres(n_side), math.cos(math.radians(cone))
+    axes, best = None, -1
+    for b in np.argsort(-count, kind="stable")[:_N_FIRST]:
+        if count[b] == 0:
+            break
+        a = centres[b]
+        e = np.zeros(3)
+        e[int(np.argmin(np.abs(a)))] = 1.0
+        p = np.cross(a, e)
+        p = p / np.sqrt(_dot(p, p))
+        q = np.cross(a, p)
+        in_a = np.abs(_dot(centres, a)) >= cos_cone
+        for j in range(_N_ANGLES):
+            th = j * (math.pi / 2) / _N_ANGLES
+            s = math.cos(th) * p + math.sin(th) * q
+            t = np.cross(a, s)
+            score = int(count[in_a | (np.abs(_dot(centres, s)) >= cos_cone) | (np.abs(_dot(centres, t)) >= cos_cone)].sum())
+            if score > best:
+                axes, best = np.stack([a, s, t]), score
+    for _ in range(_N_ROUNDS):
+        rows = []
+        for ax in axes:
+            d = _dot(centres, ax)
+            inside = np.abs(d) >= cos_cone
+            v = (np.where(d[inside] < 0.0, -1.0, 1.0)[:, None] * sums[inside]).sum(axis=0)
+            n = math.sqrt(float(_dot(v, v)))
+            rows.append(float(count[inside].sum()) * (v / n if n > 0.0 else ax))
+        axes = _nearest_rotation(np.stack(rows))
+    mass = np.array([int(count[np.abs(_dot(centres, ax)) >= cos_cone].sum()) for ax in axes]) / total
+    confidence = float(mass.sum())
+    if int((mass > 0).sum()) < 2:
+        raise _lib.BnvError(f"volume planning: {int((mass > 0).sum())} axis carries normals (axis mass "
+                            f"{mass.round(3).tolist()} of {total} normals), two are needed; {refuse}")
+    if confidence < min_confidence:
+        raise _lib.BnvError(f"volume planning: confidence {confidence:.3f} < min_confidence {min_confidence:g} (the "
+                            f"share of {total} normals within {cone:g} degrees of an axis; normals spread evenly "
+                            f"give 0.046); {refuse}")
+
+    def closest(v, among):
+        v = np.asarray(v, dtype=np.float64)
+        dots = [sg * float(_dot(axes[i], v)) for i, sg in among]
+        return among[int(np.argmax(dots))]          # (ties: the first)
+
+    signed = [(i, sg) for i in range(3) for sg in (1.0, -1.0)]
+    iy, sy = closest(down, signed)
+    iz, sz = closest(view, [c for c in signed if c[0] != iy])
+    y, z = sy * axes[iy], sz * axes[iz]
+    return ManhattanFrame(R=np.stack([np.cross(y, z), y, z]), confidence=confidence,
+                          axis_mass=mass[[3 - iy - iz, iy, iz]], n_normals=total, n_frames=int(n_frames))
 
 
 @dataclasses.dataclass
@@ -135,6 +249,7 @@ class VolumePlan:
     candidates: list
     voxel_size: object         # the smallest candidate that is ``ok``, or None
     min_pts_in_grid: int = 8
+    manhattan: object = None   # the ManhattanFrame of align="manhattan" (axis_align_mat's rotation is its R), or None
 
     def apply(self, frame):
         """A shallow copy of the frame with ``T_wc = axis_align_mat @ T_wc`` (float64): the frame as the planned volume
@@ -161,8 +276,13 @@ class VolumePlan:
         d, b = self.dimensions, self.bounds
         lines = [f"frames {self.n_frames} (skipped {self.n_skipped}), valid points {self.n_points}",
                  "bounds  " + "  ".join(f"{a} [{b[i, 0]:.2f}, {b[i, 1]:.2f}]" for i, a in enumerate("xyz")),
-                 f"dimensions {d[0]:.2f} x {d[1]:.2f} x {d[2]:.2f} m, yaw {self.yaw_deg:g} deg",
-                 f"{'voxel':>8} {'grid':>18} {'min':>7} {'mean':>7} {'p50':>7} {'max':>7} {'live':>6}  ok"]
+                 f"dimensions {d[0]:.2f} x {d[1]:.2f} x {d[2]:.2f} m, yaw {self.yaw_deg:g} deg"]
+        if self.manhattan is not None:
+            m = self.manhattan
+            lines.append(f"manhattan frame: confidence {m.confidence:.3f} (x {m.axis_mass[0]:.3f}, y {m.axis_mass[1]:.3f}, "
+                         f"z {m.axis_mass[2]:.3f}) of {m.n_normals} normals in {m.n_frames} frames")
+            lines += [f"  {a} = ({r[0]:+.6f}, {r[1]:+.6f}, {r[2]:+.6f})" for a, r in zip("xyz", m.R)]
+        lines += [f"{'voxel':>8} {'grid':>18} {'min':>7} {'mean':>7} {'p50':>7} {'max':>7} {'live':>6}  ok"]
         for c in self.candidates:
             grid = "x".join(str(n) for n in c.n_xyz)
             if not c.fits:
@@ -198,14 +318,50 @@ class VolumePlanner:
     ``extent()``; ``count(frames, voxel_sizes)`` for the statistics (with the extent of the added frames, or with
     ``dimensions`` / ``axis_align_mat`` the caller has).  ``trim``: the fraction of points ignored at each end of every
     direction (0: the exact extent, rounded outward to bins); ``margin``: added on every side, at least one bin;
-    ``align_yaw=K`` (1..30): also try K yaw angles in [0, 90) degrees about ``up`` and keep the smallest footprint."""
+    ``align_yaw=K`` (1..30): also try K yaw angles in [0, 90) degrees about ``up`` and keep the smallest footprint.
+
+    ``align="manhattan"``: for a world whose axes are not the room's (a first camera's frame, a capture's arbitrary
+    one).  A pass 0 comes first -- ``add_normals(frame)`` per frame, then ``manhattan()`` -- which finds the scene's
+    three dominant orthogonal plane directions and which of them is down, from a histogram of per-pixel normals
+    (central differences over ``normal_step`` pixels, None: max(1, W // 80); neighbours further than ``jump`` * z away
+    in depth do not count; a cube map of ``n_side`` x ``n_side`` bins a face).  Pass 1 then runs along the frame's three
+    axes and ``axis_align_mat``'s rotation is the frame: no ``up``, no yaw search.  A scene with less than
+    ``min_confidence`` of its normals within ``cone`` degrees of the axes, or with fewer than two axes, is refused.
+    ``down_hint``: a world vector that points roughly down, instead of the mean of the cameras' down axes."""
 
     def __init__(self, device="cuda:0", max_depth=3.0, bin_size=0.01, n_bins=32768, trim=0.0, margin=0.05,
-                 align_yaw=None, up="y"):
+                 align_yaw=None, up="y", align=None, normal_step=None, jump=0.1, n_side=32, cone=10.0,
+                 min_confidence=0.3, down_hint=None):
         if up not in _AXES:
             raise ValueError(f"up {up!r}: 'x', 'y' or 'z'")
         if align_yaw is not None and not 1 <= int(align_yaw) <= 30:
             raise ValueError(f"align_yaw {align_yaw}: None or 1 .. 30")
+        if align not in (None, "manhattan"):
+            raise ValueError(f"align {align!r}: None or 'manhattan'")
+        if align is not None and align_yaw is not None:
+            raise ValueError("align='manhattan' finds the whole rotation: it does not go together with align_yaw")
+        if normal_step is not None and not 1 <= int(normal_step) <= 64:
+            raise ValueError(f"normal_step {normal_step}: None or 1 .. 64")
+        if not (math.isfinite(jump) and jump > 0):
+            raise ValueError(f"jump {jump}: positive and finite")
+        if not 4 <= int(n_side) <= 64:
+            raise ValueError(f"n_side {n_side}: 4 .. 64")
+        if not 0.0 < cone < 45.0:
+            raise ValueError(f"cone {cone}: in (0, 45) degrees")
+        if not 0.0 <= min_confidence <= 1.0:
+            raise ValueError(f"min_confidence {min_confidence}: in [0, 1]")
+        if down_hint is not None:
+            down_hint = np.asarray(down_hint, dtype=np.float64)
+            if down_hint.shape != (3,) or not np.isfinite(down_hint).all() or not down_hint.any():
+                raise ValueError(f"down_hint {down_hint}: a finite non-zero 3-vector")
+        self.align, self.normal_step = align, None if normal_step is None else int(normal_step)
+        self.jump, self.n_side, self.cone = float(jump), int(n_side), float(cone)
+        self.min_confidence, self.down_hint = float(min_confidence), down_hint
+        self._normal_hist = None
+        self._frame = None
+        self._down_sum = np.zeros(3)
+        self._view = None
+        self.n_normal_frames = 0
         if not (math.isfinite(bin_size) and bin_size > 0):
             raise ValueError(f"bin_size {bin_size}: positive and finite")
         if int(n_bins) < 2 or int(n_bins) > 65536 or int(n_bins) & (int(n_bins) - 1):
@@ -246,6 +402,53 @@ class VolumePlanner:
         Tc = (C.c_double * 16)(*np.asarray(T, dtype=np.float64).reshape(-1))
         return d, c, (_lib.ptr(d), DEPTH_DTYPES[d.dtype], H, W, K, Tc, self.max_depth, c_ptr, level)
 
+    # ---- pass 0 ----------------------------------------------------------------------------------------------------
+    def add_normals(self, frame):
+        """Adds one frame's normals to the normal histogram (``align="manhattan"``); False for a frame whose pose is not
+        finite (left out here, skipped and counted by ``add``)."""
+        if self.align != "manhattan":
+            raise ValueError("add_normals: the planner was made without align='manhattan'")
+        if self._hist is not None:
+            raise _lib.BnvError("VolumePlanner.add_normals: pass 1 has begun along the frame found so far")
+        if not _pose_ok(frame):
+            return False
+        lib = self._library()
+        with torch.cuda.device(self._dev):
+            if self._normal_hist is None:
+                self._normal_hist = torch.zeros((6 * self.n_side * self.n_side, 4), dtype=torch.int64, device=self._dev)
+            d, c, args = self._frame_args(frame, frame["T_wc"], "VolumePlanner.add_normals")
+            step = self.normal_step or max(1, int(d.shape[1]) // 80)
+            _lib.check(lib.bnv_plan_normals(*args, min(step, 64), self.jump, self.n_side, _lib.ptr(self._normal_hist),
+                                            _lib.stream_ptr()), "bnv_plan_normals")
+        R = np.asarray(frame["T_wc"], dtype=np.float64)[:3, :3]
+        self._down_sum = self._down_sum + R[:, 1]
+        if self._view is None:
+            self._view = R[:, 2].copy()
+        self.n_normal_frames += 1
+        self._frame = None
+        return True
+
+    def normal_histogram(self):
+        """int64 [6 n_side^2, 4] on the host (the one read of pass 0): per cube-map bin the number of normals and the
+        sums of their components in 2^-20 fixed point."""
+        if self._normal_hist is None:
+            return np.zeros((6 * self.n_side * self.n_side, 4), np.int64)
+        return self._normal_hist.cpu().numpy()
+
+    def manhattan(self):
+        """The ``ManhattanFrame`` of the frames added with ``add_normals``; pass 1 then runs along its axes.  BnvError
+        when the scene has none (``manhattan_from_histogram``)."""
+        if self.align != "manhattan":
+            raise ValueError("manhattan: the planner was made without align='manhattan'")
+        if self._frame is None:
+            self._frame = manhattan_from_histogram(
+                self.normal_histogram(), self.n_side, self.cone, self.min_confidence,
+                self._down_sum if self.down_hint is None else self.down_hint,
+                (0.0, 0.0, 1.0) if self._view is None else self._view, self.n_normal_frames)
+            self.dirs = [np.array(r, np.float64) for r in self._frame.R]
+            self._dirs_c = (C.c_double * 9)(*np.concatenate(self.dirs))
+        return self._frame
+
     # ---- pass 1 ----------------------------------------------------------------------------------------------------
     def add(self, frame):
         """Adds one frame's points to the extent histograms; False for a frame whose pose is not finite (skipped and
@@ -253,6 +456,8 @@ class VolumePlanner:
         if not _pose_ok(frame):
             self.n_skipped += 1
             return False
+        if self.align == "manhattan":
+            self.manhattan()      # (pass 1 counts along the frame's axes)
         lib = self._library()
         with torch.cuda.device(self._dev):
             if self._hist is None:
@@ -277,6 +482,8 @@ class VolumePlanner:
         names = ["x", "y", "z"]
         b = [_bounds(hist[a], self.trim, self.bin_size, names[a]) for a in range(3)]
         R, yaw_deg = np.eye(3), 0.0
+        if self.align == "manhattan":
+            R = self.manhattan().R      # (the three histograms were counted along its rows)
         if self.align_yaw:
             K, best, area_best, bb = self.align_yaw, 0, None, None
             for j in range(K):
@@ -297,7 +504,7 @@ class VolumePlanner:
         shift[:3, 3] = -center
         self._extent = Extent(center=center, dimensions=(b[:, 1] - b[:, 0]) + 2 * self.margin,
                               axis_align_mat=shift @ rot, yaw_deg=yaw_deg, bounds=b, n_points=int(hist[0].sum()),
-                              n_frames=self.n_frames, n_skipped=self.n_skipped, hist=hist)
+                              n_frames=self.n_frames, n_skipped=self.n_skipped, hist=hist, manhattan=self._frame)
         return self._extent
 
     # ---- pass 2 ----------------------------------------------------------------------------------------------------
@@ -390,8 +597,12 @@ class VolumePlanner:
 
 def plan_volume(frames, voxel_sizes=(0.005, 0.01, 0.02, 0.04), min_pts_in_grid=8, **kw):
     """Two passes over a re-iterable frame source (a list or a dataset of depth frame dicts) -> ``VolumePlan``.
-    Keyword arguments: those of ``VolumePlanner``."""
+    Keyword arguments: those of ``VolumePlanner``; with ``align="manhattan"`` a pass 0 over the frames comes first."""
     planner = VolumePlanner(**kw)
+    if planner.align == "manhattan":
+        for f in frames:
+            planner.add_normals(f)
+        planner.manhattan()
     for f in frames:
         planner.add(f)
     return plan_from(planner.extent(), planner.count(frames, voxel_sizes, min_pts_in_grid=min_pts_in_grid),
@@ -405,4 +616,5 @@ def plan_from(extent, candidates, min_pts_in_grid=8):
     return VolumePlan(center=extent.center, dimensions=extent.dimensions, axis_align_mat=extent.axis_align_mat,
                       yaw_deg=extent.yaw_deg, bounds=extent.bounds, n_points=extent.n_points,
                       n_frames=extent.n_frames, n_skipped=extent.n_skipped, candidates=list(candidates),
-                      voxel_size=min(ok) if ok else None, min_pts_in_grid=int(min_pts_in_grid))
+                      voxel_size=min(ok) if ok else None, min_pts_in_grid=int(min_pts_in_grid),
+                      manhattan=getattr(extent, "manhattan", None))

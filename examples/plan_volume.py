@@ -4,6 +4,7 @@ alone (bnv_fusion_amd/plan.py), printed as a table.
     python examples/plan_volume.py --data-dir DATA --scan-id scene3d/lounge                 # a sequence directory
     python examples/plan_volume.py --arkit --data-dir DATA --scan-id room --align-yaw 18    # an iPhone / iPad LiDAR capture
     python examples/plan_volume.py --mesh MESH.ply --frames 60 --noise kinect               # a mesh, scanned on the GPU
+    python examples/plan_volume.py --data-dir DATA --scan-id SCAN --align manhattan         # a world with arbitrary axes
     python examples/plan_volume.py --sweep 24 --scale 0.5 --height 60 --width 80 --voxel-sizes 0.02 0.04 0.08
 
 Neither ``pose/dimensions.txt`` nor ``export.obj`` is read.  The last line of the table is the recommended voxel size:
@@ -41,6 +42,9 @@ def main():
     ap.add_argument("--margin", type=float, default=0.05)
     ap.add_argument("--align-yaw", type=int, help="try this many yaw angles in [0, 90) degrees about --up")
     ap.add_argument("--up", default="y", choices=["x", "y", "z"])
+    ap.add_argument("--align", choices=["manhattan"],
+                    help="manhattan: find the scene's own three axes and its vertical from the frames' normals (a world "
+                         "that is the first camera's frame, or a capture's arbitrary one); not with --align-yaw")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
 
@@ -62,7 +66,8 @@ def main():
                                             device=args.device))
     elif not (args.data_dir and args.scan_id):
         ap.error("give --data-dir and --scan-id, --mesh, or --sweep")
-    options = dict(bin_size=args.bin_size, trim=args.trim, margin=args.margin, align_yaw=args.align_yaw, up=args.up)
+    options = dict(bin_size=args.bin_size, trim=args.trim, margin=args.margin, align_yaw=args.align_yaw, up=args.up,
+                   align=args.align)
     if args.mesh or args.sweep:
         plan = bnv.plan_volume(frames, voxel_sizes=args.voxel_sizes, min_pts_in_grid=args.min_pts_in_grid,
                                device=args.device, max_depth=args.max_depth, **options)

@@ -12,6 +12,7 @@ sequence directory, periodic global optimisation, mesh extraction, final artefac
                                                     # no poses but the first: frame-to-frame odometry, then frame-to-model
     python examples/run_e2e.py ... --depth-filter                                           # smooth every depth image first
     python examples/run_e2e.py ... --plan-volume --plan-voxel-sizes 0.01 0.02 0.04         # extent and voxel size from the frames
+    python examples/run_e2e.py ... --plan-volume --plan-align manhattan                    # ... in the scene's own axes
     python examples/run_e2e.py --sweep 600 --grid 512 --decode-frames --pipelined --no-optimize --out /tmp/sweep
                                                     # a moving-camera room sweep (bnv_fusion_amd/sequence.py), per-frame
                                                     # SDF decode of the touched voxels, two frames in flight
@@ -121,8 +122,12 @@ def main():
     ap.add_argument("--plan-voxel-sizes", type=float, nargs="+", metavar="V",
                     help="implies --plan-volume: count the per-frame points per voxel of these candidate sizes and use the "
                          "smallest with min > 4 and mean >= 8 (the reference README's rule) in place of --voxel-size")
+    ap.add_argument("--plan-align", choices=["manhattan"],
+                    help="implies --plan-volume: plan the volume in the scene's own axes, found from the frames' normals "
+                         "(plan.ManhattanFrame), for a world whose axes are not the room's")
     args = ap.parse_args()
-    args.plan_volume = args.plan_volume or bool(args.plan_voxel_sizes)
+    args.plan_volume = args.plan_volume or bool(args.plan_voxel_sizes) or bool(args.plan_align)
+    plan_options = {"align": args.plan_align} if args.plan_align else None
     if args.color and (args.synthetic or args.sweep or args.synthetic_arkit):
         sys.exit("--color: the sequences --synthetic, --sweep and --synthetic-arkit write hold depth only, there is no "
                  "colour image to take the colours from (a grey mesh is not written instead)")
@@ -166,10 +171,11 @@ def main():
     if args.arkit:
         data = datasets.ARKitDataset(args.data_dir, args.scan_id, confidence_level=args.confidence_level,
                                      skip_images=args.skip_images, device=dev, load_rgb=load_rgb,
-                                     volume="plan" if args.plan_volume else "file")
+                                     volume="plan" if args.plan_volume else "file", plan_options=plan_options)
     else:
         data = datasets.FusionInferenceDataset(args.data_dir, args.scan_id, skip_images=args.skip_images, device=dev,
-                                               load_rgb=load_rgb, volume="plan" if args.plan_volume else "file")
+                                               load_rgb=load_rgb, volume="plan" if args.plan_volume else "file",
+                                               plan_options=plan_options)
     plan = None
     if args.plan_volume:
         # the dataset planned its extent and serves aligned frames; the candidates are counted in that frame

@@ -1462,7 +1462,29 @@ int bnv_mesh_color_resolve(const void* workspace, int64_t ws_bytes, int64_t n_ve
  * length, a confidence level without a map, n_dirs, n_bins, n_sizes or table_slots out of range and a grid with a
  * non-positive or non-finite member or 2^31 voxels or more are BNV_ERR_INVALID_ARGUMENT before any HIP call; a
  * workspace below the size is BNV_ERR_WORKSPACE_TOO_SMALL.  Fixed sequences of launches on stream: no allocation,
- * synchronisation or host read. */
+ * synchronisation or host read.
+ *
+ * Pass 0, bnv_plan_normals: the histogram of surface normals from which the host finds the scene's Manhattan frame
+ * (plan.py: ManhattanFrame) when the world's axes are not the room's.  hist int64 [6 n_side^2, 4], device memory the
+ * caller zeroes once: it accumulates over calls.  Pixel (v, u) counts under these rules, all in float64 with one
+ * rounding per operation in the written order (tests/manhattan_restatement.py restates them in numpy):
+ *     validity  the pixel and its four neighbours (v, u -+ step), (v -+ step, u) lie in the image and are valid: z finite,
+ *               0 < z <= max_depth (uint16: z = d / 1000.0) and, with a map, conf >= conf_level -- inclusive, unlike the
+ *               0 < z < max_depth of passes 1 and 2: a pixel at exactly max_depth votes for a direction here and is
+ *               no point there;
+ *     jump      each neighbour q has |z_q - z_c| <= jump * z_c;
+ *     points    P = ((u - cx) / fx * z, (v - cy) / fy * z, z);
+ *     normal    n = (P(u + step) - P(u - step)) x (P(v + step) - P(v - step)), each component a * b - c * d; negated
+ *               when (n0 Pc0 + n1 Pc1) + n2 Pc2 > 0 (it faces the camera); w_r = (R_r0 n0 + R_r1 n1) + R_r2 n2 with R
+ *               the rotation of T_wc; w / sqrt((w0 w0 + w1 w1) + w2 w2); a length that is 0 or not finite skips the pixel;
+ *     bin       m the index of the largest |w_i| (ties: the lower), face = 2 m + (w_m < 0); for a = (m + 1) % 3 and
+ *               b = (m + 2) % 3: i = clamp(floor(((w_a / |w_m| + 1) * 0.5) * n_side), 0, n_side - 1);
+ *               bin = (face * n_side + i_a) * n_side + i_b;
+ *     sums      hist[bin] += {1, rint(w_0 * 2^20), rint(w_1 * 2^20), rint(w_2 * 2^20)}.
+ * Everything accumulated is an integer: the result does not depend on the schedule, the launch shape or the order of the
+ * frames.  A workgroup sums what shares a bin in LDS and issues four 64-bit global atomics per distinct bin.
+ * 1 <= step <= 64, jump positive and finite, 4 <= n_side <= 64 and the frame arguments as above, else
+ * BNV_ERR_INVALID_ARGUMENT before any HIP call.  One launch on stream: no allocation, synchronisation or host read. */
 #define BNV_PLAN_MAX_DIRS 64
 #define BNV_PLAN_MAX_SIZES 8
 #define BNV_PLAN_ROW_WORDS 72
@@ -1476,6 +1498,9 @@ int bnv_plan_extent(const void* depth, int depth_dtype, int H, int W, const doub
 int bnv_plan_count(const void* depth, int depth_dtype, int H, int W, const double* intr_host, const double* T_wc_host,
                    double max_depth, const uint8_t* conf, int conf_level, const bnv_grid_t* grids_host, int n_sizes,
                    int64_t table_slots, void* workspace, size_t ws_bytes, int64_t* rows_out, bnv_stream_t stream);
+int bnv_plan_normals(const void* depth, int depth_dtype, int H, int W, const double* intr_host, const double* T_wc_host,
+                     double max_depth, const uint8_t* conf, int conf_level, int step, double jump, int n_side,
+                     int64_t* hist, bnv_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,7 @@
 """The cost of volume planning (csrc/plan.hip; bnv_fusion_amd/plan.py) next to the fusion it precedes, one JSON line:
 
+* pass 0 (VolumePlanner.add_normals, align="manhattan") with normal steps 1 and 8, frames/s, and the frame each finds
+  (the sweep's world is the room's own, so the largest axis error is the frame's angle to the identity);
 * pass 1 (VolumePlanner.add) with 3 and with 39 directions (align_yaw=18), frames/s;
 * pass 2 (VolumePlanner.count) with 1 and with 4 candidate voxel sizes, frames/s, and the hash tables' device memory
   per candidate;
@@ -13,6 +15,7 @@ caller sees), after one untimed pass.
 """
 import argparse
 import json
+import math
 import statistics
 import sys
 
@@ -64,6 +67,23 @@ def main():
 
     for name, yaw in (("pass1_3_dirs", None), ("pass1_39_dirs", 18)):
         res[name + "_fps"], res[name + "_all"] = timed(lambda: pass1(yaw), n)
+
+    def pass0(step):
+        planner = bnv.VolumePlanner(device=DEV, align="manhattan", normal_step=step)
+        for f in frames:
+            planner.add_normals(f)
+        return planner
+
+    for name, step in (("pass0_step_1", 1), ("pass0_step_8", 8)):
+        res[name + "_fps"], res[name + "_all"] = timed(lambda: pass0(step), n)
+        try:
+            frame = pass0(step).manhattan()
+        except bnv.BnvError as e:
+            res[name + "_frame"] = {"refused": str(e)}
+            continue
+        res[name + "_frame"] = {"confidence": round(frame.confidence, 3), "normals": frame.n_normals,
+                                "largest_axis_error_deg": round(max(
+                                    math.degrees(math.acos(min(1.0, float(np.abs(r).max())))) for r in frame.R), 3)}
     ext = pass1(None).extent()
     res["dimensions"] = [round(float(d), 2) for d in ext.dimensions]
     res["valid_points"] = ext.n_points
