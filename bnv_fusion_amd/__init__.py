@@ -42,6 +42,8 @@ from . import register  # noqa: F401,E402
 from .register import register_mesh, register_points  # noqa: F401,E402
 from .frontend import DepthFilter, filter_depth  # noqa: F401,E402
 from . import plan  # noqa: F401,E402
+from . import pointcloud  # noqa: F401,E402
+from .pointcloud import estimate_normals, load_cloud  # noqa: F401,E402
 from .plan import ManhattanFrame, VolumePlan, VolumePlanner, plan_volume  # noqa: F401,E402
 
 

@@ -173,6 +173,8 @@ SIGNATURES = {
     "bnv_mesh_sample_surface": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
     "bnv_nn_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
     "bnv_nn_query": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+    "bnv_cloud_normals_bytes": (C.c_int, [i64, C.POINTER(i64)]),
+    "bnv_cloud_normals": (C.c_int, [vp, i64, i32, C.c_float, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]),
     "bnv_tsdf_mesh_workspace_bytes": (C.c_int, [C.POINTER(i32), C.POINTER(i64)]),
     "bnv_tsdf_mesh_count": (C.c_int, [vp, vp, C.POINTER(i32), C.c_float, C.c_int, vp, vp, i64, vp, vp]),
     "bnv_tsdf_mesh_emit": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_float), C.c_float, C.c_float,

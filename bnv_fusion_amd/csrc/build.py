@@ -15,9 +15,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["runtime.hip", "encode.hip", "encode_mlp.hip", "encode_tcnn.hip", "volume.hip", "decode.hip", "decode_pts.hip", "lattice.hip", "frontend.hip", "tsdf.hip", "mesh.hip", "rays.hip", "io.hip",
            "shard.hip", "pipeline.hip", "probe.hip", "eval.hip",
            "render.hip", "meshpost.hip", "meshcomp.hip", "train.hip", "train_tcnn.hip", "meshsdf.hip", "meshray.hip",
-           "track.hip", "depth_filter.hip", "meshcolor.hip", "plan.hip", "odometry.hip", "register.hip", "meshsimplify.hip"]
+           "track.hip", "depth_filter.hip", "meshcolor.hip", "plan.hip", "odometry.hip", "register.hip", "meshsimplify.hip",
+           "cloud.hip"]
 HEADERS = ["bnv_common.hpp", "encode.hpp", "frontend.hpp", "tcnn_mlp.hpp", "sdf_mlp.hpp", "decode_host.hpp", "cell_grid.hpp", "meshsdf.hpp", "meshsdf_query.hpp",
            "workspace.hpp", "scan.hpp", "shard.hpp", "volume_keys.hpp", "train_common.hpp", "icp_solve.hpp", "mesh_face.hpp",
+           "nn_index.hpp",
            os.path.join("..", "..", "include", "bnv_fusion.h")]
 OUT = os.path.join(HERE, "..", "libbnv_fusion_hip.so")
 STAMP = OUT + ".sha256"

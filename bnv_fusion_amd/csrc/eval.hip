@@ -12,6 +12,7 @@
 #include "../../include/bnv_fusion.h"
 #include "bnv_common.hpp"
 #include "cell_grid.hpp"
+#include "nn_index.hpp"
 #include "scan.hpp"
 #include "workspace.hpp"
 
@@ -174,22 +175,8 @@ __global__ __launch_bounds__(256) void k_sample_surface(const float* __restrict_
 // Exact nearest neighbour on a uniform grid
 // =====================================================================================================================
 // Cell size (cell_grid.hpp: grid_cell_edge): the inputs are surface samples, ~kCellTarget of them in an occupied cell.
-// Volumetric sets (the area estimate asks for far more cells than points) are covered by the cap: h grows by 5/4 until
-// the grid has at most max(n_ref, 1) cells.
+// The index (two grids, count / scan / scatter) and the stop test are nn_index.hpp's, shared with csrc/cloud.hip.
 constexpr double kCellTarget = 4.0;
-constexpr double kStopSlack = 1e-5;    // relative slack of the stop test (fp32 d^2 carries ~4 ulp of rounding)
-constexpr int kFineRings = 8;          // rings of the fine grid before a query moves on to the coarse grid
-constexpr double kCoarse = 4.0;        // coarse cell edge / fine cell edge
-constexpr uint32_t kNoCell = 0xffffffffu;
-
-struct NnParams {
-  uint32_t bmin[3], bmax[3];   // order-preserving encodings of the finite reference points' bounding box
-  int32_t dims[3];
-  int32_t n_cells;             // 0: no finite reference point
-  double lo[3], fmin[3], fmax[3];
-  double h, inv_h;
-};
-static_assert(offsetof(NnParams, bmin) == 0 && offsetof(NnParams, bmax) == 12, "grid_bbox writes the first six words");
 
 struct NnWs {
   NnParams* P;           // [2]: the fine grid, the coarse grid
@@ -237,104 +224,12 @@ static size_t nn_ws_layout(int64_t n_ref, int64_t n_query, char* base, NnWs* w) 
   return c.bytes();
 }
 
-// the grid of cell size h (grown by 5/4 until it has at most `cap` cells) over the bounding box in P
-__device__ void nn_grid(NnParams* __restrict__ P, const double L[3], double h, double cap) {
-  double dims[3];
-  for (;;) {
-    for (int d = 0; d < 3; ++d) dims[d] = fmin(floor(L[d] / h) + 1.0, 2147483647.0);
-    if (dims[0] * dims[1] * dims[2] <= cap) break;
-    h *= 1.25;
-  }
-  for (int d = 0; d < 3; ++d) P->dims[d] = (int32_t)dims[d];
-  P->n_cells = (int32_t)(dims[0] * dims[1] * dims[2]);
-  P->h = h;
-  P->inv_h = 1.0 / h;
-}
-
-// P[0]: the fine grid (the cell size rule above); P[1]: the coarse grid, cells kCoarse times larger
-__global__ void k_nn_params(NnParams* __restrict__ P, int64_t n_ref) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (P->bmin[0] > P->bmax[0]) {   // no finite reference point
-    for (int g = 0; g < 2; ++g) {
-      P[g].n_cells = 0;
-      for (int d = 0; d < 3; ++d) {
-        P[g].dims[d] = 1;
-        P[g].lo[d] = P[g].fmin[d] = P[g].fmax[d] = 0.0;
-      }
-      P[g].h = P[g].inv_h = 1.0;
-    }
-    return;
-  }
-  double L[3];
-  for (int d = 0; d < 3; ++d) {
-    P->fmin[d] = P->lo[d] = (double)ord2f(P->bmin[d]);
-    P->fmax[d] = (double)ord2f(P->bmax[d]);
-    L[d] = P->fmax[d] - P->fmin[d];
-  }
-  const double cap = fmax((double)n_ref, 1.0);
-  nn_grid(P, L, grid_cell_edge(L, n_ref, kCellTarget), cap);
-  for (int d = 0; d < 3; ++d) {
-    P[1].bmin[d] = P->bmin[d];
-    P[1].bmax[d] = P->bmax[d];
-    P[1].lo[d] = P->lo[d];
-    P[1].fmin[d] = P->fmin[d];
-    P[1].fmax[d] = P->fmax[d];
-  }
-  nn_grid(P + 1, L, P->h * kCoarse, cap);
-}
-
-// cell of every point (query: the clamped cell; non-finite: the extra bucket n_cells) and its slot in the cell.  The
-// slots follow the order the atomics happen in; results do not depend on it (tie rule), only the layout does.
-__global__ __launch_bounds__(256) void k_nn_count(const float* __restrict__ X, int64_t n, const NnParams* __restrict__ P,
-                                                  int is_query, uint32_t* __restrict__ count,
-                                                  uint32_t* __restrict__ cell_of, uint32_t* __restrict__ slot_of) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float x = X[i * 3], y = X[i * 3 + 1], z = X[i * 3 + 2];
-  uint32_t c;
-  if (!finite3(x, y, z) || P->n_cells == 0) {
-    c = is_query ? (uint32_t)P->n_cells : kNoCell;
-  } else {
-    const int cx = cell_axis(x, P->lo[0], P->inv_h, P->dims[0]);
-    const int cy = cell_axis(y, P->lo[1], P->inv_h, P->dims[1]);
-    const int cz = cell_axis(z, P->lo[2], P->inv_h, P->dims[2]);
-    c = (uint32_t)(((int64_t)cx * P->dims[1] + cy) * P->dims[2] + cz);
-  }
-  cell_of[i] = c;
-  if (c != kNoCell) slot_of[i] = atomicAdd(&count[c], 1u);
-}
-
-__global__ __launch_bounds__(256) void k_nn_scatter(const float* __restrict__ X, int64_t n,
-                                                    const uint32_t* __restrict__ cell_of,
-                                                    const uint32_t* __restrict__ slot_of,
-                                                    const uint32_t* __restrict__ start, float4* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t c = cell_of[i];
-  if (c == kNoCell) return;
-  out[start[c] + slot_of[i]] = make_float4(X[i * 3], X[i * 3 + 1], X[i * 3 + 2], __builtin_bit_cast(float, (int32_t)i));
-}
-
 // (d2, idx) lexicographic: the lowest reference index wins a tie
 __device__ __forceinline__ void nn_take(float d2, int32_t idx, float& best, int32_t& bi) {
   if (d2 < best || (d2 == best && idx < bi)) {
     best = d2;
     bi = idx;
   }
-}
-
-__device__ __forceinline__ float nn_d2(float qx, float qy, float qz, const float4 r) {
-  const float dx = __fsub_rn(qx, r.x), dy = __fsub_rn(qy, r.y), dz = __fsub_rn(qz, r.z);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
-// Can the search stop after ring r?  When the ring covers the grid, or when the lower bound on the real d^2 to every
-// unvisited point (cell_grid.hpp: grid_ring_bound) exceeds the best fp32 d^2 by the relative slack (continue while it
-// is <=).
-__device__ __forceinline__ bool nn_can_stop(const NnParams& P, const int c[3], int r, const double q[3], float best) {
-  double lb;
-  if (!grid_ring_bound(P.lo, P.fmin, P.fmax, P.dims, P.h, c, r, q, lb)) return true;
-  return lb > (double)best * (1.0 + kStopSlack) + 1e-30;
 }
 
 // Ring search of one query on one grid, from ring 0 up to ring `rmax` or until the stop test proves (best, bi) final
@@ -440,36 +335,18 @@ int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_
   NnWs w;
   if (ws_bytes < (int64_t)nn_ws_layout(n_ref, n_query, (char*)workspace, &w)) return BNV_ERR_WORKSPACE_TOO_SMALL;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t n_bins = n_ref + 2;
-  const int64_t tiles = (n_bins + kScanTile - 1) / kScanTile;
-  // everything the build accumulates into starts from a known state on every call (also when replayed from a graph):
-  // the counts, the look-back words (0 = an epoch next_epoch never hands out), the bounding box (grid_bbox)
-  BNV_HIP_CHECK(hipMemsetAsync(w.ref_count, 0, (size_t)n_bins * 4, s));
+  const int64_t n_bins = nn_bins(n_ref), tiles = nn_scan_tiles(n_ref);
+  const NnIndex index = {w.P,        w.ref_count, w.ref_start, w.ref_cell,   w.ref_slot,  w.ref_sorted,
+                         w.rc_count, w.rc_start,  w.rc_cell,   w.rc_slot,    w.rc_sorted, w.scan_state};
+  if (const int e = nn_build_index(ref, n_ref, index, kCellTarget, s)) return e;
+  // the queries in the fine grid's cell order: the same count / scan / scatter, from a known state on every call
   BNV_HIP_CHECK(hipMemsetAsync(w.q_count, 0, (size_t)n_bins * 4, s));
-  BNV_HIP_CHECK(hipMemsetAsync(w.rc_count, 0, (size_t)n_bins * 4, s));
-  BNV_HIP_CHECK(hipMemsetAsync(w.scan_state, 0, (size_t)tiles * 3 * 8, s));
-  const dim3 ref_blocks(blocks_for(n_ref, 256)), q_blocks(blocks_for(n_query, 256));
-  if (const int e = grid_bbox(ref, n_ref, w.P, 2 * sizeof(NnParams), s)) return e;
-  hipLaunchKernelGGL(k_nn_params, dim3(1), dim3(64), 0, s, w.P, n_ref);
-  BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_nn_count, ref_blocks, dim3(256), 0, s, ref, n_ref, w.P, 0, w.ref_count, w.ref_cell, w.ref_slot);
-  BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_nn_count, ref_blocks, dim3(256), 0, s, ref, n_ref, w.P + 1, 0, w.rc_count, w.rc_cell, w.rc_slot);
-  BNV_LAUNCH_CHECK();
+  BNV_HIP_CHECK(hipMemsetAsync(w.scan_state + 2 * tiles, 0, (size_t)tiles * 8, s));
+  const dim3 q_blocks(blocks_for(n_query, 256));
   hipLaunchKernelGGL(k_nn_count, q_blocks, dim3(256), 0, s, query, n_query, w.P, 1, w.q_count, w.q_cell, w.q_slot);
   BNV_LAUNCH_CHECK();
-  uint32_t* counts[3] = {w.ref_count, w.rc_count, w.q_count};
-  uint32_t* starts[3] = {w.ref_start, w.rc_start, w.q_start};
-  for (int k = 0; k < 3; ++k) {
-    hipLaunchKernelGGL(k_grid_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, counts[k], n_bins, starts[k],
-                       w.scan_state + k * tiles, next_epoch());
-    BNV_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_nn_scatter, ref_blocks, dim3(256), 0, s, ref, n_ref, w.ref_cell, w.ref_slot, w.ref_start,
-                     w.ref_sorted);
-  BNV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_nn_scatter, ref_blocks, dim3(256), 0, s, ref, n_ref, w.rc_cell, w.rc_slot, w.rc_start,
-                     w.rc_sorted);
+  hipLaunchKernelGGL(k_grid_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, w.q_count, n_bins, w.q_start,
+                     w.scan_state + 2 * tiles, next_epoch());
   BNV_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_nn_scatter, q_blocks, dim3(256), 0, s, query, n_query, w.q_cell, w.q_slot, w.q_start,
                      w.q_sorted);

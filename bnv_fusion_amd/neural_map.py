@@ -230,6 +230,21 @@ class NeuralMap:
             self._mark_volume_update()
         return fine_coords
 
+    def integrate_cloud(self, points, origins, origin_index=None, **kw):
+        """Fuses a point cloud that comes without normals: ``pointcloud.estimate_normals(points, origins,
+        origin_index, **kw)`` (``points`` fp32 [N, 3] on the GPU; ``origins`` [M, 3] sensor positions, ``origin_index``
+        [N] into them or None for ``origins[0]``; ``k``, ``max_radius``, ``min_neighbors``) followed by
+        ``integrate({"input_pts": ...})``.  One call is one frame of the running average -- a scan station, a sweep, a
+        submap -- unless the cloud has more than ``chunk`` points (default ``pointcloud.CLOUD_CHUNK_POINTS`` = 2^20; the
+        encoder itself refuses more than 2^27 in one frame): it is then cut in index order into frames of ``chunk``
+        points, the normals still estimated over the whole cloud.  No TSDF side update is made: there is no depth image.
+        ``min_pts_in_grid`` and the voxel size have to suit the cloud's density, as they do for depth frames: a voxel
+        the cloud puts fewer than ``min_pts_in_grid`` points into is not encoded, so a sparse cloud needs a larger
+        voxel or a smaller ``min_pts_in_grid`` (a 160 x 120 depth frame a metre away puts about 7 points into a 2 cm
+        voxel).  Returns the voxel coordinates touched ([U', 3] int64) or None."""
+        from . import pointcloud
+        return pointcloud.integrate_cloud(self, points, origins, origin_index, **kw)
+
     def _mark_volume_update(self):
         """An event behind a TSDF update enqueued on the current stream: the encode stream of a later
         fuse_and_decode_async (which also updates the TSDF volume) waits for it."""

@@ -215,6 +215,34 @@ def scan_frames(scanner, poses, K, H, W, noise=None, seed=0, max_depth=math.inf,
             yield frame
 
 
+def scan_cloud(scanner, poses, K, H, W, max_depth=math.inf, near=0.0):
+    """A multi-station point cloud of the mesh: the valid pixels of the clean depth images rendered from ``poses``
+    ([n, 4, 4] camera-to-world), back-projected in float64 as ``render_color`` does and concatenated in pose order,
+    row-major inside a view -> (points fp32 [N, 3] on the scanner's device, origins float64 [n, 3] -- the camera
+    centres --, origin_index int32 [N] on the device: the view every point came from).  What
+    ``pointcloud.estimate_normals`` / ``NeuralMap.integrate_cloud`` take.  Torch elementwise code: it makes a test and
+    demo asset."""
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    K = np.asarray(K, dtype=np.float64)
+    H, W = int(H), int(W)
+    pts, idx = [], []
+    dev = scanner.device
+    c = torch.arange(W, dtype=torch.float64, device=dev)[None, :]
+    r = torch.arange(H, dtype=torch.float64, device=dev)[:, None]
+    for s in range(0, len(poses), MAX_POSES):
+        depth, _ = scanner.render_depth(poses[s:s + MAX_POSES], K, H, W, near=near, max_depth=max_depth)
+        for j in range(depth.shape[0]):
+            d, T = depth[j].double(), poses[s + j]
+            x = (c - float(K[0, 2])) / float(K[0, 0]) * d
+            y = (r - float(K[1, 2])) / float(K[1, 1]) * d
+            world = torch.stack([((x * float(T[a, 0]) + y * float(T[a, 1])) + d * float(T[a, 2])) + float(T[a, 3])
+                                 for a in range(3)], dim=-1)
+            keep = d > 0
+            pts.append(world[keep].float())
+            idx.append(torch.full((int(pts[-1].shape[0]),), s + j, dtype=torch.int32, device=dev))
+    return torch.cat(pts).contiguous(), poses[:, :3, 3].copy(), torch.cat(idx).contiguous()
+
+
 def drift_poses(poses, sigma_t, sigma_r, seed=0):
     """Odometry that drifts: every relative motion ``T_{i-1}^-1 T_i`` of ``poses`` ([n, 4, 4]) is followed by a small
     random motion exp((w, v)) in the camera's frame, w ~ N(0, sigma_r^2) radians and v ~ N(0, sigma_t^2) metres per

@@ -788,6 +788,48 @@ int bnv_nn_workspace_bytes(int64_t n_ref, int64_t n_query, int64_t* bytes);
 int bnv_nn_query(const float* ref, int64_t n_ref, const float* query, int64_t n_query, void* workspace,
                  int64_t ws_bytes, float* d2_out, int32_t* idx_out, bnv_stream_t stream);
 
+/* ---- Point-cloud normals (bnv_fusion_amd/csrc/cloud.hip): the [N, 6] rows the encoder takes, for points that come
+ * without a pixel grid (a LiDAR scan, an exported cloud, a PLY of points).  The reference has no such entry: its
+ * normals come from a depth image.  tests/cloud_restatement.py restates what follows in numpy; the kernel equals it
+ * bit for bit, and two calls give the same bits.
+ *
+ * Neighbours.  A self-join on the index of bnv_nn_query: for point i the finite points j (i itself first) ordered by
+ * (d2, j) lexicographically, d2 the fp32 (dx*dx + dy*dy) + dz*dz of bnv_nn_query -- the lowest index wins a tie.  The
+ * first k of them; with max_radius > 0 those of them with d2 <= r2, r2 = the fp32 product max_radius * max_radius (an
+ * infinite r2 is no radius).  m = how many: at most min(k, finite points).  A point with a NaN / Inf coordinate is
+ * neither a query nor a neighbour.
+ * Plane.  In float64, neighbours in that order, one rounding per written operation: mean = (0 + p_1 + ... + p_m) / m per
+ * axis; the six moments a_xx, a_xy, a_xz, a_yy, a_yz, a_zz = (0 + sum of d_u d_v) / m with d = p - mean; V = I; then
+ * BNV_CLOUD_JACOBI_SWEEPS cyclic Jacobi sweeps over the pairs (0,1), (0,2), (1,2).  The rotation of pair (p, q), r the
+ * third index, skipped when a_pq == 0:  theta = (a_qq - a_pp) / (2 a_pq);  t = (theta >= 0 ? 1 : -1) / (|theta| +
+ * sqrt(theta theta + 1));  c = 1 / sqrt(t t + 1);  s = t c;  h = t a_pq;  a_pp -= h;  a_qq += h;  a_pq = 0;
+ * (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq);  for every row i of V: (v_ip, v_iq) = (c v_ip - s v_iq, s v_ip +
+ * c v_iq).  Eigenvalues = the diagonal: lambda_0 the smallest (the first index among equals), lambda_2 the largest
+ * (the last index among equals), lambda_1 the remaining one; the normal = V's column of lambda_0.
+ * Rejection.  m < min_neighbors; not a plane: !(lambda_1 > 1e-6 lambda_2) (coincident points: lambda_2 = 0; collinear
+ * points: lambda_1 is rounding noise; a NaN anywhere); an origin index outside [0, n_origins).  A rejected row and a
+ * non-finite row are six NaNs (the encoder's bounds mask drops them), variation NaN, n_neighbors m (0: non-finite).
+ * Orientation.  Away from the sensor, as the depth front end's normals point: dot = (n_x (p_x - o_x) + n_y (p_y - o_y))
+ * + n_z (p_z - o_z) in float64, o = origins[origin_index[i]] (origin 0 without origin_index); the normal is negated
+ * when dot < 0, an exact zero keeps the solver's sign.
+ * Outputs, in the input's row order: input_pts_out fp32 [n, 6] = (x, y, z copied, the normal rounded once to fp32);
+ * variation_out (NULL: not written) fp32 [n] = max(lambda_0, 0) / ((lambda_0 + lambda_1) + lambda_2) rounded once;
+ * n_neighbors_out (NULL: not written) int32 [n]; status_out int32 [4] (device): [0] rejected rows (non-finite ones
+ * included), [1] rows whose origin index is out of range, [2], [3] zero.
+ * points fp32 [n, 3], origins fp32 [n_origins, 3], origin_index int32 [n] or NULL (device).  k in [BNV_CLOUD_MIN_K,
+ * BNV_CLOUD_MAX_K], 3 <= min_neighbors <= k, max_radius finite and >= 0 (0: none), n in [1, 2^31 - 3]; anything else
+ * is BNV_ERR_INVALID_ARGUMENT before any HIP call, a workspace below bnv_cloud_normals_bytes (named like
+ * bnv_mesh_simplify_bytes; ~84 B per point) BNV_ERR_WORKSPACE_TOO_SMALL.  No allocation, synchronisation or host read:
+ * the caller reads status_out.  Capturable into a graph. */
+#define BNV_CLOUD_MIN_K 8
+#define BNV_CLOUD_MAX_K 32
+#define BNV_CLOUD_JACOBI_SWEEPS 6
+int bnv_cloud_normals_bytes(int64_t n_points, int64_t* bytes);
+int bnv_cloud_normals(const float* points, int64_t n_points, int32_t k, float max_radius, int32_t min_neighbors,
+                      const float* origins, int64_t n_origins, const int32_t* origin_index, void* workspace,
+                      int64_t ws_bytes, float* input_pts_out, float* variation_out, int32_t* n_neighbors_out,
+                      int32_t* status_out, bnv_stream_t stream);
+
 /* ---- Signed distance to a triangle mesh (bnv_fusion_amd/csrc/meshsdf.hip): the exact distance from arbitrary points
  * to the mesh, everywhere (no truncation band), negative inside for outward-oriented faces.  The reference has no such
  * entry; bnv_fusion_amd/patches.py cuts embedding-training patches with it.
