@@ -89,6 +89,7 @@ SIGNATURES = {
     "bnv_volume_clear": (C.c_int, [C.POINTER(Volume), vp]),
     "bnv_volume_rehash": (C.c_int, [C.POINTER(Volume), vp]),
     "bnv_volume_workspace_bytes": (sz, [i64]),
+    "bnv_volume_integrate_tile_keys": (C.c_int, []),
     "bnv_volume_integrate_batch": (C.c_int, [C.POINTER(Volume), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "bnv_volume_insert": (C.c_int, [C.POINTER(Volume), vp, vp, vp, vp, i64, vp, sz, vp]),
     "bnv_volume_query": (C.c_int, [C.POINTER(Volume), vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]),

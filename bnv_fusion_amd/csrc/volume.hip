@@ -20,7 +20,7 @@ constexpr int kVolTile = kVolThreads * kVolItems;
 
 struct VolWs {
   int32_t* slot_of;        // [n] slot index of each key (or -1: key out of range)
-  int32_t* is_new;         // [n] 1 if this thread's CAS created the slot
+  int32_t* is_new;         // [n] 1 if this occurrence creates the key's row (insert: later, 1 if it wrote the row's values)
   uint32_t* block_sums;    // [n_blocks + 1]
   uint32_t* block_new;     // [ceil(n / 256) + 1] created keys per 256-key block (integrate)
   uint64_t* tile_state;    // [ws_bytes / 2048 + 2] look-back state of k_vol_integrate (epoch-tagged, never cleared; fixed place)
@@ -71,12 +71,16 @@ __device__ __forceinline__ int64_t dev_count(int64_t n, const int32_t* n_dev) {
   return m < n ? m : n;
 }
 
+// the row word of a key that has no row yet, claimed by occurrence i of an insert call: below -1 ("no row") for every i
+__device__ __forceinline__ int32_t first_token(int64_t i) { return (int32_t)(INT32_MIN + i); }
+
 __global__ __launch_bounds__(256) void k_vol_probe_insert(bnv_volume_t v, const int64_t* __restrict__ coords,
                                                           int64_t n, const int32_t* __restrict__ n_dev,
                                                           int32_t* __restrict__ slot_of,
                                                           int32_t* __restrict__ is_new,
                                                           int32_t* __restrict__ error,
-                                                          uint32_t* __restrict__ block_new = nullptr) {
+                                                          uint32_t* __restrict__ block_new = nullptr,
+                                                          int first_claim = 0) {
   n = dev_count(n, n_dev);
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   uint64_t key;
@@ -106,6 +110,14 @@ __global__ __launch_bounds__(256) void k_vol_probe_insert(bnv_volume_t v, const 
     if (slot < 0) *error = 1;  // table full
   } else {
     *error = 2;  // coordinate outside the 21-bit key range
+  }
+  if (first_claim && slot >= 0) {
+    // insert accepts a key several times in one call.  Which occurrence wins the CAS is a race, but the key's row is
+    // numbered at its FIRST occurrence (the reference's map inserts that one and overwrites with the rest): a key
+    // without a row yet holds a negative row word, where its occurrences leave the smallest of their indices
+    const int32_t r = v.slot_rows[slot];
+    if (r < 0) atomicMin(&v.slot_rows[slot], first_token(i));
+    else v.num_hits[r] = __int_as_float(-1);   // (the row's claim word for k_vol_insert_claim: insert overwrites num_hits)
   }
   if (i < n) {
     slot_of[i] = slot;
@@ -169,7 +181,7 @@ __global__ __launch_bounds__(kVolThreads) void k_vol_assign_rows(bnv_volume_t v,
         // a fresh row reads as zeros (SparseVolume.query of an absent key, sparse_volume.py:677-679)
         for (int f = 0; f < v.n_feats; ++f) v.features[row * v.n_feats + f] = 0.f;
         v.weights[row] = 0.f;
-        v.num_hits[row] = 0.f;
+        v.num_hits[row] = __int_as_float(-1);   // the row's claim word (k_vol_insert_claim); the claimant's value follows
         if (v.lattice_have) v.lattice_have[row] = 0u;
       } else {
         *error = 3;
@@ -494,22 +506,59 @@ __global__ __launch_bounds__(256) void k_vol_batch_integrate(bnv_volume_t v, Vol
   if (v.lattice_have) v.lattice_have[row] = 0u;
 }
 
-__global__ __launch_bounds__(256) void k_vol_insert_apply(bnv_volume_t v, const float* __restrict__ feats,
-                                                          const float* __restrict__ weights,
-                                                          const float* __restrict__ hits, int64_t n,
-                                                          const int32_t* __restrict__ n_dev,
-                                                          const int32_t* __restrict__ slot_of) {
+// ---- insert with a key given several times in one call: the row is created at the key's FIRST occurrence (row order)
+// and holds the values of its LAST one, whole -- what inserting the occurrences one after the other gives (the
+// reference's map inserts one and overwrites with the rest, sparse_volume.py:561-585).  Eight floats written by racing
+// occurrences could interleave, so one occurrence per row writes: the largest index, found by an atomicMax in the
+// row's num_hits word (insert overwrites it anyway; k_vol_probe_insert / k_vol_assign_rows set it to -1).
+// is_new[i] = this occurrence is the first of a key without a row
+__global__ __launch_bounds__(256) void k_vol_insert_first(bnv_volume_t v, int64_t n, const int32_t* __restrict__ n_dev,
+                                                          const int32_t* __restrict__ slot_of,
+                                                          int32_t* __restrict__ is_new) {
   n = dev_count(n, n_dev);
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int32_t slot = slot_of[i];
-  if (slot < 0) return;
+  is_new[i] = (slot >= 0 && v.slot_rows[slot] == first_token(i)) ? 1 : 0;
+}
+
+__device__ __forceinline__ int64_t insert_row(const bnv_volume_t& v, const int32_t* __restrict__ slot_of, int64_t i) {
+  const int32_t slot = slot_of[i];
+  if (slot < 0) return -1;
   const int64_t row = v.slot_rows[slot];
-  if (row < 0 || row >= v.row_capacity) return;
+  return row < v.row_capacity ? row : -1;
+}
+
+__global__ __launch_bounds__(256) void k_vol_insert_claim(bnv_volume_t v, int64_t n, const int32_t* __restrict__ slot_of) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t row = insert_row(v, slot_of, i);
+  if (row >= 0) atomicMax((int32_t*)&v.num_hits[row], (int32_t)i);
+}
+
+// the claiming occurrence writes the row; num_hits (still the claim word other occurrences read) follows in
+// k_vol_insert_hits, by the occurrences that note here, in wrote[i], that they did
+__global__ __launch_bounds__(256) void k_vol_insert_apply(bnv_volume_t v, const float* __restrict__ feats,
+                                                          const float* __restrict__ weights, int64_t n,
+                                                          const int32_t* __restrict__ slot_of,
+                                                          int32_t* __restrict__ wrote) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t row = insert_row(v, slot_of, i);
+  const bool mine = row >= 0 && __float_as_int(v.num_hits[row]) == (int32_t)i;
+  wrote[i] = mine ? 1 : 0;
+  if (!mine) return;
   for (int f = 0; f < v.n_feats; ++f) v.features[row * v.n_feats + f] = feats[i * v.n_feats + f];
   v.weights[row] = weights[i];
-  v.num_hits[row] = hits[i];
   if (v.lattice_have) v.lattice_have[row] = 0u;
+}
+
+__global__ __launch_bounds__(256) void k_vol_insert_hits(bnv_volume_t v, const float* __restrict__ hits, int64_t n,
+                                                         const int32_t* __restrict__ slot_of,
+                                                         const int32_t* __restrict__ wrote) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || !wrote[i]) return;
+  v.num_hits[insert_row(v, slot_of, i)] = hits[i];
 }
 
 __global__ __launch_bounds__(256) void k_vol_query(bnv_volume_t v, const int64_t* __restrict__ coords, int64_t n,
@@ -575,7 +624,10 @@ static int vol_upsert_rows(const bnv_volume_t& v, const int64_t* coords, int64_t
                            const VolWs& ws, hipStream_t stream) {
   const int nbt = (int)blocks_for(n, kVolTile);
   hipLaunchKernelGGL(k_vol_probe_insert, dim3(blocks_for(n, 256)), dim3(256), 0, stream, v, coords, n, n_dev, ws.slot_of,
-                     ws.is_new, ws.error);
+                     ws.is_new, ws.error, (uint32_t*)nullptr, 1);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_vol_insert_first, dim3(blocks_for(n, 256)), dim3(256), 0, stream, v, n, n_dev, ws.slot_of,
+                     ws.is_new);
   BNV_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_vol_scan_partial, dim3(nbt), dim3(kVolThreads), 0, stream, ws.is_new, n, n_dev,
                      ws.block_sums);
@@ -603,6 +655,8 @@ size_t bnv_volume_workspace_bytes(int64_t max_keys) {
   for (int it = 0; it < 8; ++it) s = vol_ws_layout(max_keys, nullptr, s, nullptr);
   return s + 512;
 }
+
+int bnv_volume_integrate_tile_keys(void) { return kIntThreads; }
 
 int bnv_volume_clear(const bnv_volume_t* vol, bnv_stream_t stream) {
   if (!vol_ok(vol)) return BNV_ERR_INVALID_ARGUMENT;
@@ -696,7 +750,7 @@ int bnv_volume_integrate_batch(const bnv_volume_t* vol, int n_frames, const int6
 int bnv_volume_insert(const bnv_volume_t* vol, const int64_t* coords, const float* feats,
                       const float* weights, const float* num_hits, int64_t n, void* ws_ptr,
                       size_t ws_bytes, bnv_stream_t stream_) {
-  if (!vol_ok(vol) || n < 0) return BNV_ERR_INVALID_ARGUMENT;
+  if (!vol_ok(vol) || n < 0 || n > 0x7fffff00) return BNV_ERR_INVALID_ARGUMENT;   // (first_token: indices below 2^31)
   if (n == 0) return BNV_OK;
   if (!coords || !feats || !weights || !num_hits || !ws_ptr) return BNV_ERR_INVALID_ARGUMENT;
   VolWs ws;
@@ -705,8 +759,12 @@ int bnv_volume_insert(const bnv_volume_t* vol, const int64_t* coords, const floa
   hipStream_t stream = (hipStream_t)stream_;
   const int rc = vol_upsert_rows(*vol, coords, n, nullptr, ws, stream);
   if (rc != BNV_OK) return rc;
-  hipLaunchKernelGGL(k_vol_insert_apply, dim3(blocks_for(n, 256)), dim3(256), 0, stream, *vol, feats,
-                     weights, num_hits, n, (const int32_t*)nullptr, ws.slot_of);
+  const dim3 grid(blocks_for(n, 256));
+  hipLaunchKernelGGL(k_vol_insert_claim, grid, dim3(256), 0, stream, *vol, n, ws.slot_of);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_vol_insert_apply, grid, dim3(256), 0, stream, *vol, feats, weights, n, ws.slot_of, ws.is_new);
+  BNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_vol_insert_hits, grid, dim3(256), 0, stream, *vol, num_hits, n, ws.slot_of, ws.is_new);
   BNV_LAUNCH_CHECK();
   return BNV_OK;
 }

@@ -351,6 +351,10 @@ int bnv_volume_clear(const bnv_volume_t* vol_host, bnv_stream_t stream);
 /* Rebuild the slot table from row_coords[0:n_rows) (after the caller enlarged it). */
 int bnv_volume_rehash(const bnv_volume_t* vol_host, bnv_stream_t stream);
 size_t bnv_volume_workspace_bytes(int64_t max_keys);
+/* Keys per workgroup of bnv_volume_integrate's single launch as this library was built (BNV_INT_THREADS): new rows are
+ * numbered per workgroup and chained across workgroups, so frame sizes around its multiples are the edges of that
+ * numbering (what tests size their frames by; nothing a caller has to respect). */
+int bnv_volume_integrate_tile_keys(void);
 
 /* LitFusionPointNet._integrate + _update (local_point_fusion.py:647-673) fused with
  * SparseVolume.query/insert (sparse_volume.py:561-585, 661-695): for n UNIQUE keys,
@@ -389,7 +393,9 @@ int bnv_volume_integrate_batch(const bnv_volume_t* vol_host, int n_frames, const
                                const float* const* feats, const int64_t* const* pcounts, const int64_t* n,
                                const int32_t* const* n_dev, uint32_t* slot_mask, int32_t* slot_items,
                                void* workspace, size_t workspace_bytes, bnv_stream_t stream);
-/* SparseVolume.insert (upsert with explicit values), sparse_volume.py:561-585. */
+/* SparseVolume.insert (upsert with explicit values), sparse_volume.py:561-585.  A key may occur several times in one
+ * call: it gets ONE row, numbered at its first occurrence, holding the values of its last occurrence (what inserting
+ * the occurrences one by one gives).  n < 2^31 - 256. */
 int bnv_volume_insert(const bnv_volume_t* vol_host, const int64_t* coords, const float* feats,
                       const float* weights, const float* num_hits, int64_t n, void* ws,
                       size_t ws_bytes, bnv_stream_t stream);
