@@ -39,11 +39,11 @@ from .tracking import Tracker, icp_align  # noqa: F401,E402
 from . import odometry  # noqa: F401,E402
 from .odometry import PreparedFrame, RgbdOdometry, prepare_frame, rgbd_align  # noqa: F401,E402
 from . import register  # noqa: F401,E402
-from .register import register_mesh, register_points  # noqa: F401,E402
+from .register import register_cloud, register_mesh, register_points  # noqa: F401,E402
 from .frontend import DepthFilter, filter_depth  # noqa: F401,E402
 from . import plan  # noqa: F401,E402
 from . import pointcloud  # noqa: F401,E402
-from .pointcloud import estimate_normals, load_cloud  # noqa: F401,E402
+from .pointcloud import CloudIndex, align_scans, estimate_normals, load_cloud  # noqa: F401,E402
 from .plan import ManhattanFrame, VolumePlan, VolumePlanner, plan_volume  # noqa: F401,E402
 
 

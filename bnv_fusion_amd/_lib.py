@@ -231,6 +231,13 @@ SIGNATURES = {
     "bnv_mesh_register": (C.c_int, [vp, i64, vp, i64, C.POINTER(C.c_double), i32, C.POINTER(i32),
                                     C.POINTER(C.c_double), i32, C.c_double, C.c_double, C.c_double, C.c_double, vp, sz,
                                     vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "bnv_cloud_index_bytes": (C.c_int, [i64, C.POINTER(i64)]),
+    "bnv_cloud_index_build": (C.c_int, [vp, i64, vp, i64, vp]),
+    "bnv_cloud_index_nearest": (C.c_int, [vp, i64, vp, i64, vp, vp, vp]),
+    "bnv_cloud_register_bytes": (sz, [i32, C.POINTER(i32)]),
+    "bnv_cloud_register": (C.c_int, [vp, i64, vp, i64, vp, C.POINTER(C.c_double), i32, C.POINTER(i32),
+                                     C.POINTER(C.c_double), C.c_double, i32, C.c_double, C.c_double, C.c_double,
+                                     C.c_double, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
     "bnv_depth_filter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, vp,
                                    C.c_int, vp, vp]),
     "bnv_mesh_normals_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),

@@ -16,7 +16,7 @@ SOURCES = ["runtime.hip", "encode.hip", "encode_mlp.hip", "encode_tcnn.hip", "vo
            "shard.hip", "pipeline.hip", "probe.hip", "eval.hip",
            "render.hip", "meshpost.hip", "meshcomp.hip", "train.hip", "train_tcnn.hip", "meshsdf.hip", "meshray.hip",
            "track.hip", "depth_filter.hip", "meshcolor.hip", "plan.hip", "odometry.hip", "register.hip", "meshsimplify.hip",
-           "cloud.hip"]
+           "cloud.hip", "cloud_register.hip"]
 HEADERS = ["bnv_common.hpp", "encode.hpp", "frontend.hpp", "tcnn_mlp.hpp", "sdf_mlp.hpp", "decode_host.hpp", "cell_grid.hpp", "meshsdf.hpp", "meshsdf_query.hpp",
            "workspace.hpp", "scan.hpp", "shard.hpp", "volume_keys.hpp", "train_common.hpp", "icp_solve.hpp", "mesh_face.hpp",
            "nn_index.hpp",

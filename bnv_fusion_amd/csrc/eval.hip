@@ -175,8 +175,9 @@ __global__ __launch_bounds__(256) void k_sample_surface(const float* __restrict_
 // Exact nearest neighbour on a uniform grid
 // =====================================================================================================================
 // Cell size (cell_grid.hpp: grid_cell_edge): the inputs are surface samples, ~kCellTarget of them in an occupied cell.
-// The index (two grids, count / scan / scatter) and the stop test are nn_index.hpp's, shared with csrc/cloud.hip.
-constexpr double kCellTarget = 4.0;
+// The index (two grids, count / scan / scatter), the stop test and the ring walk of one query (nn_search) are
+// nn_index.hpp's, shared with csrc/cloud.hip and csrc/cloud_register.hip.
+constexpr double kCellTarget = kNnCellTarget;
 
 struct NnWs {
   NnParams* P;           // [2]: the fine grid, the coarse grid
@@ -224,33 +225,6 @@ static size_t nn_ws_layout(int64_t n_ref, int64_t n_query, char* base, NnWs* w) 
   return c.bytes();
 }
 
-// (d2, idx) lexicographic: the lowest reference index wins a tie
-__device__ __forceinline__ void nn_take(float d2, int32_t idx, float& best, int32_t& bi) {
-  if (d2 < best || (d2 == best && idx < bi)) {
-    best = d2;
-    bi = idx;
-  }
-}
-
-// Ring search of one query on one grid, from ring 0 up to ring `rmax` or until the stop test proves (best, bi) final
-// (-> true).  A cell run is read straight from the cell-ordered copy of R (float4: one 16-byte load per point).
-__device__ __forceinline__ bool nn_rings(const NnParams& P, const uint32_t* __restrict__ rstart,
-                                         const float4* __restrict__ Rs, const float4 qv, const double q[3], int rmax,
-                                         float& best, int32_t& bi) {
-  const int c[3] = {cell_axis(qv.x, P.lo[0], P.inv_h, P.dims[0]), cell_axis(qv.y, P.lo[1], P.inv_h, P.dims[1]),
-                    cell_axis(qv.z, P.lo[2], P.inv_h, P.dims[2])};
-  for (int r = 0; r <= rmax; ++r) {
-    grid_ring(c, r, P.dims, rstart, [&](uint32_t k0, uint32_t k1) {
-      for (uint32_t k = k0; k < k1; ++k) {
-        const float4 rv = Rs[k];
-        nn_take(nn_d2(qv.x, qv.y, qv.z, rv), __builtin_bit_cast(int32_t, rv.w), best, bi);
-      }
-    });
-    if (nn_can_stop(P, c, r, q, best)) return true;
-  }
-  return false;
-}
-
 // One thread per query (measured on the fine grid alone against one wave per query, whose lanes split every cell run
 // and reduce the best per ring: 3.0 against 2.4 ms at 1M x 1M, 0.22 against 0.18 ms at 100k x 100k; surface cells
 // hold a handful of points, too few for 64 lanes).  Queries arrive in the fine grid's cell order (q_sorted), so neighbouring threads
@@ -271,14 +245,7 @@ __global__ __launch_bounds__(256) void k_nn_query(const float4* __restrict__ Qs,
   const int32_t qi = __builtin_bit_cast(int32_t, qv.w);
   float best = INFINITY;
   int32_t bi = -1;
-  if (Pp[0].n_cells > 0 && finite3(qv.x, qv.y, qv.z)) {
-    const double q[3] = {(double)qv.x, (double)qv.y, (double)qv.z};
-    const NnParams& F = Pp[0];
-    if (!nn_rings(F, rstart, Rs, qv, q, kFineRings, best, bi)) {
-      const NnParams& G = Pp[1];
-      nn_rings(G, cstart, Rc, qv, q, max(G.dims[0], max(G.dims[1], G.dims[2])), best, bi);
-    }
-  }
+  if (Pp[0].n_cells > 0 && finite3(qv.x, qv.y, qv.z)) nn_search(Pp, Rs, rstart, Rc, cstart, qv, best, bi);
   d2_out[qi] = best;
   idx_out[qi] = bi;
 }

@@ -2,7 +2,9 @@
 // csrc/cloud.hip (bnv_cloud_normals, k-NN self-join).  Two uniform grids (cell_grid.hpp) over the finite reference
 // points -- a fine one and a coarse one with cells kCoarse times larger -- each built by box / parameters / count /
 // scan / scatter into a cell-ordered float4 copy (x, y, z, bitcast(index)).  This is the only place that build is
-// written; a user brings its cell target, its workspace layout, and what it does with a cell run.
+// written; a user brings its cell target, its workspace layout, and what it does with a cell run.  The 1-NN ring walk
+// of one query (nn_take, nn_rings, nn_search) is written here too: bnv_nn_query, bnv_cloud_index_nearest and the
+// cloud-to-cloud aligner (csrc/cloud_register.hip) call the same code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -19,6 +21,7 @@ constexpr double kStopSlack = 1e-5;    // relative slack of the stop test (fp32 
 constexpr int kFineRings = 8;          // rings of the fine grid before a query moves on to the coarse grid
 constexpr double kCoarse = 4.0;        // coarse cell edge / fine cell edge
 constexpr uint32_t kNoCell = 0xffffffffu;
+constexpr double kNnCellTarget = 4.0;  // 1-NN over surface samples: ~4 of them in an occupied cell (grid_cell_edge)
 
 struct NnParams {
   uint32_t bmin[3], bmax[3];   // order-preserving encodings of the finite reference points' bounding box
@@ -141,6 +144,52 @@ __device__ __forceinline__ bool nn_can_stop(const NnParams& P, const int c[3], i
   double lb;
   if (!grid_ring_bound(P.lo, P.fmin, P.fmax, P.dims, P.h, c, r, q, lb)) return true;
   return lb > (double)best * (1.0 + kStopSlack) + 1e-30;
+}
+
+// (d2, idx) lexicographic: the lowest reference index wins a tie
+__device__ __forceinline__ void nn_take(float d2, int32_t idx, float& best, int32_t& bi) {
+  if (d2 < best || (d2 == best && idx < bi)) {
+    best = d2;
+    bi = idx;
+  }
+}
+
+// Ring search of one query on one grid, from ring 0 up to ring `rmax` or until the stop test proves (best, bi) final
+// (-> true).  A cell run is read straight from the cell-ordered copy of R (float4: one 16-byte load per point).
+// (best, bi) come in as the caller's initial bound: (+inf, -1) for the nearest point whatever its distance; a finite
+// `best` with bi = -1 for the nearest point with d2 < best (a point at exactly `best` does not beat index -1), and the
+// stop test then ends the walk as soon as nothing unvisited can be that close.
+__device__ __forceinline__ bool nn_rings(const NnParams& P, const uint32_t* __restrict__ rstart,
+                                         const float4* __restrict__ Rs, const float4 qv, const double q[3], int rmax,
+                                         float& best, int32_t& bi) {
+  const int c[3] = {cell_axis(qv.x, P.lo[0], P.inv_h, P.dims[0]), cell_axis(qv.y, P.lo[1], P.inv_h, P.dims[1]),
+                    cell_axis(qv.z, P.lo[2], P.inv_h, P.dims[2])};
+  for (int r = 0; r <= rmax; ++r) {
+    grid_ring(c, r, P.dims, rstart, [&](uint32_t k0, uint32_t k1) {
+      for (uint32_t k = k0; k < k1; ++k) {
+        const float4 rv = Rs[k];
+        nn_take(nn_d2(qv.x, qv.y, qv.z, rv), __builtin_bit_cast(int32_t, rv.w), best, bi);
+      }
+    });
+    if (nn_can_stop(P, c, r, q, best)) return true;
+  }
+  return false;
+}
+
+// The 1-NN search of one finite query over both grids of an index that holds a point (Pp[0].n_cells > 0): the first
+// kFineRings rings of the fine grid, and a query they do not settle goes on with the best it has on the coarse grid
+// (cells kCoarse times larger): points seen twice change nothing under the tie rule, and the coarse search is exact on
+// its own.  (best, bi): nn_rings' initial bound in, the answer out.
+__device__ __forceinline__ void nn_search(const NnParams* __restrict__ Pp, const float4* __restrict__ Rs,
+                                          const uint32_t* __restrict__ rstart, const float4* __restrict__ Rc,
+                                          const uint32_t* __restrict__ cstart, const float4 qv, float& best,
+                                          int32_t& bi) {
+  const double q[3] = {(double)qv.x, (double)qv.y, (double)qv.z};
+  const NnParams& F = Pp[0];
+  if (!nn_rings(F, rstart, Rs, qv, q, kFineRings, best, bi)) {
+    const NnParams& G = Pp[1];
+    nn_rings(G, cstart, Rc, qv, q, max(G.dims[0], max(G.dims[1], G.dims[2])), best, bi);
+  }
 }
 
 // Enqueues the build of both grids over the n_ref points of `ref` (fp32 [n_ref, 3], device).  Everything the build

@@ -202,12 +202,30 @@ def metrics_from_distances(d_pred_gt, d_gt_pred, threshold=0.025):
     return dict(zip(KEYS, vals[:4] + [f1]))
 
 
-def evaluate(pred_points, gt_points, threshold=0.025):
+def evaluate(pred_points, gt_points, threshold=0.025, align=None):
     """evaluate_bnvf.py:9-31: nearest neighbours both ways -> {"pred_gt", "accuracy", "gt_pred", "recall", "F1"}
-    (accuracy = precision = fraction of predicted points closer than ``threshold`` to the ground truth)."""
-    d_pg, _ = nearest_neighbors(pred_points, gt_points)
-    d_gp, _ = nearest_neighbors(gt_points, pred_points)
-    return metrics_from_distances(d_pg, d_gp, threshold)
+    (accuracy = precision = fraction of predicted points closer than ``threshold`` to the ground truth).
+
+    align: None scores the two sets as they are.  True, or a dict of ``register.register_cloud`` keywords (a
+    ``T_guess`` among them), first registers the predicted points to the ground-truth points (cloud-to-cloud ICP; the
+    ground truth's normals are estimated, unoriented) and scores the transformed points: the result gains
+    ``"T_align"``, ``"align_status"`` and the five figures before alignment under ``"unaligned"``, as
+    ``evaluate_meshes(align=)`` does.  A refused registration scores unaligned."""
+
+    def score(pts):
+        d_pg, _ = nearest_neighbors(pts, gt_points)
+        d_gp, _ = nearest_neighbors(gt_points, pts)
+        return metrics_from_distances(d_pg, d_gp, threshold)
+
+    if align is None or align is False:
+        return score(pred_points)
+    from . import register
+    from .pointcloud import CloudIndex
+    unaligned = score(pred_points)
+    reg = register.register_cloud(pred_points, CloudIndex(gt_points), **({} if align is True else dict(align)))
+    res = score(register.transform_points(reg.T, pred_points)) if reg.status == register.OK else dict(unaligned)
+    res["T_align"], res["align_status"], res["unaligned"] = reg.T, reg.status, unaligned
+    return res
 
 
 def evaluate_meshes(pred, gt, n_samples=100000, threshold=0.025, vertices_only=False, normals=False, generator=None,

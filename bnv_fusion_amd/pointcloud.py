@@ -100,6 +100,106 @@ def estimate_normals(points, origins, origin_index=None, k=16, max_radius=None, 
     return (out, {"variation": var, "n_neighbors": cnt, "status": status}) if return_stats else out
 
 
+class CloudIndex:
+    """A point cloud with normals as a registration target and nearest-neighbour reference, indexed once on the GPU
+    (csrc/cloud_register.hip; include/bnv_fusion.h, "Cloud registration": bnv_cloud_index_build): the index of
+    ``evaluate.nearest_neighbors`` over the positions, kept, next to the unit normals.  ``points`` fp32 [N, 3] with
+    ``normals`` fp32 [N, 3], or ``input_pts`` fp32 [N, 6] / [1, N, 6] (what ``estimate_normals`` returns), on the GPU.
+    Without normals they are estimated (``estimate_normals`` with ``k``); a target's normals need no orientation, so
+    ``origins`` defaults to the cloud's first point.  A row with a non-finite component or a normal shorter than 1e-12
+    is in the index but never anyone's neighbour.  Building reads nothing back.
+
+        d2, idx = CloudIndex(scan_a).nearest(scan_b)
+        res = register.register_cloud(scan_b, CloudIndex(scan_a), T_guess=T0)
+    """
+
+    def __init__(self, points=None, normals=None, *, input_pts=None, k=16, origins=None):
+        if input_pts is not None:
+            if points is not None or normals is not None:
+                raise ValueError("CloudIndex: input_pts carries positions and normals; give it alone")
+            rows = _rows6(input_pts, "input_pts")
+        else:
+            if points is None:
+                raise ValueError("CloudIndex: points, or input_pts")
+            p = _points(points)
+            if normals is None:
+                rows = estimate_normals(p, p[:1] if origins is None else origins, k=k)[0]
+            else:
+                nrm = _points(normals, "normals")
+                if nrm.shape != p.shape or nrm.device != p.device:
+                    raise ValueError(f"normals: expected {tuple(p.shape)} on {p.device}, got {tuple(nrm.shape)} on "
+                                     f"{nrm.device}")
+                rows = torch.cat([p, nrm], 1).contiguous()
+        self.device = rows.device
+        self.n = int(rows.shape[0])
+        lib = _lib.require_device(self.device.index or 0)
+        need = C.c_int64()
+        _lib.check(lib.bnv_cloud_index_bytes(self.n, C.byref(need)), "bnv_cloud_index_bytes")
+        self._ws_bytes = int(need.value)
+        with torch.cuda.device(self.device):
+            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+            _lib.check(lib.bnv_cloud_index_build(_lib.ptr(rows), self.n, _lib.ptr(self._ws), self._ws_bytes,
+                                                 _lib.stream_ptr()), "bnv_cloud_index_build")
+
+    def nearest(self, query):
+        """``query`` fp32 [M, 3] on the index's device -> (d2 fp32 [M], idx int32 [M]): ``evaluate.nn_d2(query,
+        points)`` bit for bit over the rows the index kept, without building the index again."""
+        q = _points(query, "query")
+        if q.device != self.device:
+            raise ValueError(f"query on {q.device}, index on {self.device}")
+        m = int(q.shape[0])
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            d2 = torch.empty(m, dtype=torch.float32, device=self.device)
+            idx = torch.empty(m, dtype=torch.int32, device=self.device)
+            _lib.check(lib.bnv_cloud_index_nearest(_lib.ptr(self._ws), self._ws_bytes, _lib.ptr(q), m, _lib.ptr(d2),
+                                                   _lib.ptr(idx), _lib.stream_ptr()), "bnv_cloud_index_nearest")
+        return d2, idx
+
+
+def _rows6(input_pts, what):
+    if not isinstance(input_pts, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch tensor on the GPU, got {type(input_pts).__name__}")
+    if not input_pts.is_cuda:
+        raise ValueError(f"{what}: a CPU tensor; cloud registration runs on the GPU only (no CPU fallback)")
+    r = input_pts.detach()
+    if r.dim() == 3 and r.shape[0] == 1:
+        r = r[0]
+    if r.dim() != 2 or r.shape[1] != 6 or r.shape[0] == 0 or r.shape[0] > 2 ** 31 - 3:
+        raise ValueError(f"{what}: expected a non-empty [N, 6] tensor of at most 2^31 - 3 rows, got "
+                         f"{tuple(input_pts.shape)}")
+    return r.to(torch.float32).contiguous()
+
+
+def align_scans(scans, T_guess, origins=None, **kw):
+    """Aligns the stations of a multi-station scan to each other before fusion, one after the other: ``scans`` a list
+    of fp32 [N_i, 3] device tensors, each in its own station's frame, ``T_guess`` [n, 4, 4] the rough station poses
+    (station -> common frame).  Scan 0 keeps its pose; scan i is registered (``register.register_cloud``, whose
+    keywords ``kw`` are) to a ``CloudIndex`` over the union of the scans 0 .. i - 1 at their aligned poses ->
+    (poses float64 [n, 4, 4], statuses [n]).  A refused scan keeps its guess (and still joins the union there).
+    ``origins`` [n, 3]: sensor positions in the stations' own frames for the targets' normals (default: none needed).
+    Sequential: an error made early is not revisited (no pose graph)."""
+    from . import register
+    T_guess = np.asarray(T_guess, dtype=np.float64).reshape(-1, 4, 4)
+    if len(scans) == 0 or len(T_guess) != len(scans):
+        raise ValueError(f"align_scans: {len(scans)} scans, {len(T_guess)} poses")
+    clouds = [_points(s, f"scans[{i}]") for i, s in enumerate(scans)]
+    poses, statuses = T_guess.copy(), [register.OK]
+    placed = [register.transform_points(poses[0], clouds[0])]
+    org = None if origins is None else np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+    for i in range(1, len(clouds)):
+        world_origin = None
+        if org is not None:                                # one origin serves: the sign of a target normal is irrelevant
+            world_origin = (poses[0, :3, :3] @ org[0] + poses[0, :3, 3])[None]
+        target = CloudIndex(torch.cat(placed), origins=world_origin)
+        res = register.register_cloud(clouds[i], target, T_guess=poses[i], **kw)
+        statuses.append(res.status)
+        if res.status == register.OK:
+            poses[i] = res.T
+        placed.append(register.transform_points(poses[i], clouds[i]))
+    return poses, statuses
+
+
 def load_cloud(path):
     """The vertices of a PLY file (``mesh.load_ply``: ASCII or binary little-endian; faces, if any, are ignored) ->
     (points float32 [N, 3], normals float32 [N, 3] or None).  With normals in the file (``nx ny nz``) no estimation is

@@ -2,11 +2,16 @@
 
     python examples/fuse_cloud.py CLOUD.ply --origin 0 0 0 --voxel 0.02 --out mesh.ply
     python examples/fuse_cloud.py CLOUD.ply --origins stations.txt --origin-index index.txt --out mesh.ply
+    python examples/fuse_cloud.py --stations stations.txt --register --out mesh.ply
     python examples/fuse_cloud.py --synthetic --out mesh.ply
 
 CLOUD.ply: vertices only are read (bnv_fusion_amd.load_cloud); with ``nx ny nz`` in the file those normals are used
 as they are, unless --estimate is given.  Sensor positions: --origin X Y Z (one station), or --origins FILE with one
-"x y z" per line and --origin-index FILE with one station number per point.  --synthetic: a four-station scan of a
+"x y z" per line and --origin-index FILE with one station number per point.  --stations FILE: a multi-station scan,
+one line per station: a PLY in the station's own frame and the 16 numbers of its row-major 4x4 pose (station ->
+common frame); the sensor sits at each station's origin.  With --register the poses are only rough: the scans are
+aligned to each other first (pointcloud.align_scans: every scan to the union of those before it) and fused at the
+aligned poses.  --synthetic: a four-station scan of a
 box (scan.scan_cloud) instead of a file.  The volume is a cube around the cloud's box (--size to override) centred
 on the cloud, which is shifted to the origin for fusion and back for the mesh.  --voxel and --min-pts have to suit
 the cloud's density: a voxel with fewer than --min-pts points is not encoded."""
@@ -26,6 +31,8 @@ def main():
     ap.add_argument("--origin", type=float, nargs=3, default=None)
     ap.add_argument("--origins", default=None, help="file: one sensor position per line")
     ap.add_argument("--origin-index", default=None, help="file: one station number per point")
+    ap.add_argument("--stations", default=None, help="file: per line a PLY (relative to the file) and its 4x4 pose")
+    ap.add_argument("--register", action="store_true", help="with --stations: align the scans to each other first")
     ap.add_argument("--estimate", action="store_true", help="estimate normals even if the file has them")
     ap.add_argument("-k", type=int, default=16)
     ap.add_argument("--max-radius", type=float, default=None)
@@ -50,9 +57,27 @@ def main():
         poses = scan.orbit_poses([0.0, 0.0, 0.0], 2.0, 4, height=0.7)
         K = np.array([[300.0, 0.0, 159.5], [0.0, 300.0, 119.5], [0.0, 0.0, 1.0]])
         points, origins, origin_index = scan.scan_cloud(scanner, poses, K, 240, 320)
+    elif args.stations:
+        from bnv_fusion_amd import register
+        scans, poses = [], []
+        with open(args.stations) as fh:
+            for line in filter(None, (ln.split("#")[0].split() for ln in fh)):
+                if len(line) != 17:
+                    ap.error(f"--stations: expected 'SCAN.ply' and 16 numbers per line, got {len(line)} fields")
+                path = os.path.join(os.path.dirname(os.path.abspath(args.stations)), line[0])
+                scans.append(torch.from_numpy(bnv.load_cloud(path)[0]).to(dev))
+                poses.append(np.array(line[1:], dtype=np.float64).reshape(4, 4))
+        poses = np.stack(poses)
+        if args.register:
+            poses, statuses = bnv.align_scans(scans, poses)
+            print("stations registered one after the other: " +
+                  ", ".join(register.STATUS_NAMES.get(s, str(s)) for s in statuses))
+        points = torch.cat([register.transform_points(T, s) for T, s in zip(poses, scans)])
+        origins = poses[:, :3, 3].copy()
+        origin_index = torch.cat([torch.full((len(s),), i, dtype=torch.int32, device=dev) for i, s in enumerate(scans)])
     else:
         if not args.cloud:
-            ap.error("a PLY file, or --synthetic")
+            ap.error("a PLY file, --stations, or --synthetic")
         pts, normals = bnv.load_cloud(args.cloud)
         points = torch.from_numpy(pts).to(dev)
         if args.origins:

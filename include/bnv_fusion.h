@@ -1369,6 +1369,71 @@ int bnv_mesh_register(const void* mesh_index, int64_t index_bytes, const float* 
                       double* pose_out, double* poses_out, double* stats_out, int32_t* status_out, float* q_out,
                       float* closest_out, int32_t* face_out, uint8_t* feature_out, bnv_stream_t stream);
 
+/* ---- Cloud registration (bnv_fusion_amd/csrc/cloud_register.hip; bnv_fusion_amd/pointcloud.py: CloudIndex,
+ * align_scans; bnv_fusion_amd/register.py: register_cloud): point-to-plane ICP of a point cloud against another point
+ * cloud that carries normals -- a laser-scan ground truth that exists only as points, the union of the stations
+ * already aligned -- and the persistent index of that target.  Returns the rigid T that maps source points into the
+ * target's frame.  The reference has no such entry; tests/cloud_register_restatement.py restates what follows in
+ * numpy.  Every float64 operation is one IEEE rounding, in the order written (no contraction); division and sqrt are
+ * correctly rounded.
+ *
+ * Index.  input_pts f32 [n_points, 6] (device): positions and normals, the rows bnv_cloud_normals writes and the
+ * encoder takes; 1 <= n_points <= 2^31 - 3.  Row j is rejected when a position or normal component is NaN / Inf (the
+ * all-NaN rows bnv_cloud_normals makes of what it rejects) or when len = sqrt((nx nx + ny ny) + nz nz), in float64 of
+ * the fp32 components, is below 1e-12.  The index holds, under a header (magic, n_points, layout version): the
+ * positions copied (a rejected row: three NaNs), the normals (float)(n / len) (a rejected row: three NaNs), and the
+ * two-level uniform grid of bnv_nn_query (the same cell target) over the copied positions.  The grid leaves out a
+ * non-finite point, so a rejected row is never anyone's nearest neighbour.  Everything lives in the caller's workspace
+ * (bnv_cloud_index_bytes: a function of n_points alone); the workspace IS the index and is passed on as built.
+ * bnv_cloud_index_build makes no allocation, synchronisation or host read (the header is written by a kernel):
+ * capturable into a graph.
+ *
+ * Nearest.  bnv_cloud_index_nearest: query f32 [n_query, 3], taken in the order given -> d2_out f32 [n_query], idx_out
+ * int32 [n_query], exactly what bnv_nn_query answers against the positions the index kept: d2 bitwise the minimum of
+ * the fp32 (dx dx + dy dy) + dz dz, idx the LOWEST index attaining it; (+inf, -1) for a non-finite query, an index
+ * without a kept row, or memory that does not hold an index of at most index_bytes (a header that does not match).
+ *
+ * Register.  points f32 [n_points, 3] (device), source frame, 1 <= n_points <= INT32_MAX; source_normals f32
+ * [n_points, 3] or NULL; T_guess_host, levels_host, dist_host, the sampled points and n_iter as for bnv_mesh_register.
+ * A pair.  At the current estimate T = [R | t], sampled point p = points[i]:
+ *   qd_a = ((R[a][0] p0 + R[a][1] p1) + R[a][2] p2) + t_a,  q = (float)qd;  a non-finite q has no candidate;
+ *   g2 = (float)(dist dist), the product taken in float64;  the candidate j is the kept target row of least fp32
+ *   d2 = (dx dx + dy dy) + dz dz, dx = q.x - c.x, among those with d2 <= g2, the LOWEST index among equals; none: no
+ *   candidate.  (The ring walk starts from the bound nextafterf(g2, +inf) with index -1: the same answer as the
+ *   unbounded search followed by the gate test, but a point far from the target stops after a ring or two.)  An index
+ *   that bnv_cloud_index_nearest would not answer from has no candidate for any point.
+ *   With source_normals, s = source_normals[i]: a non-finite s rejects the pair;  m_a = (R[a][0] s0 + R[a][1] s1) +
+ *   R[a][2] s2,  cs = (m0 n0 + m1 n1) + m2 n2 with n the target's normal as float64;  keep when cs >= min_normal_cos
+ *   (oriented != 0) or |cs| >= min_normal_cos (oriented == 0).  Without source_normals both arguments are ignored.
+ *   Row: c = the target's position j, e_a = (double)c_a - (double)q_a,  r = (n0 e0 + n1 e1) + n2 e2,  J = [q x n, n] on
+ *   the float64 value of the fp32 q, (q x n)_0 = q1 n2 - q2 n1 and cyclic;  pairs += 1 for every kept pair.  The twist
+ *   multiplies on the left: T <- exp(xi^) T.  No robust weights: the gate is the outlier rule.
+ * The sign of a target normal does not matter: negating n negates J and r, and every one of the 29 products is then
+ * the same to the bit (and |cs| too), so a target needs only unoriented normals -- bnv_cloud_normals with any origin.
+ * Sums, Solve, the sticky status, the outputs pose_out, poses_out (or NULL), stats_out, status_out and the workspace
+ * (bnv_cloud_register_bytes = bnv_mesh_register_bytes) are those of bnv_mesh_register, the clamp included.  Two
+ * launches per iteration; nothing is read by the host, allocated or synchronised.
+ * Dumps (device, each optional).  q_out f32 [n_points, 3], index_out int32 [n_points]: every iteration writes, for
+ * sampled point k of its level, row k: q and the candidate j (-1: none; the normal gate does not change it); rows n_s
+ * and up are not touched.
+ * Null pointers (source_normals, poses_out and the dumps excepted), counts out of range, an invalid schedule, a dist
+ * that is not positive and finite, a non-finite T_guess, with source_normals a min_normal_cos outside [-1, 1],
+ * negative or non-finite thresholds, step limits that are not positive and finite and an index_bytes no index fits
+ * into are BNV_ERR_INVALID_ARGUMENT before any HIP call; a workspace below its size entry is
+ * BNV_ERR_WORKSPACE_TOO_SMALL. */
+int bnv_cloud_index_bytes(int64_t n_points, int64_t* bytes);
+int bnv_cloud_index_build(const float* input_pts, int64_t n_points, void* workspace, int64_t ws_bytes,
+                          bnv_stream_t stream);
+int bnv_cloud_index_nearest(const void* cloud_index, int64_t index_bytes, const float* query, int64_t n_query,
+                            float* d2_out, int32_t* idx_out, bnv_stream_t stream);
+size_t bnv_cloud_register_bytes(int32_t n_levels, const int32_t* levels_host);
+int bnv_cloud_register(const void* cloud_index, int64_t index_bytes, const float* points, int64_t n_points,
+                       const float* source_normals, const double T_guess_host[16], int32_t n_levels,
+                       const int32_t* levels_host, const double* dist_host, double min_normal_cos, int32_t oriented,
+                       double min_pair_share, double min_spread, double max_rotation, double max_translation,
+                       void* workspace, size_t ws_bytes, double* pose_out, double* poses_out, double* stats_out,
+                       int32_t* status_out, float* q_out, int32_t* index_out, bnv_stream_t stream);
+
 /* ---- Depth filter (bnv_fusion_amd/csrc/depth_filter.hip; bnv_fusion_amd/frontend.py: filter_depth): edge-preserving
  * smoothing of a depth image in front of the front end and the tracker.  Sensor depth is disparity-quantised (one
  * step of the reference's Kinect model is z^2 / (8 * 35.130): 3.6 mm at 1 m, 32 mm at 3 m) and the front end's 3x3
